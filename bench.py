@@ -47,7 +47,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np
 
-# ---- peaks (MI355X: /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters)
+# ---- peaks (MI355X chip-level parameters)
 HBM_PEAK_GBS = 8000.0
 N_SIMD = 256 * 4
 CLOCK_SPEC_HZ = 2.4e9
@@ -245,6 +245,41 @@ def clone_solver(DPSolver, sysd, solver, dtype, **attrs):
     return s
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this much in all
+DUMP_SEED = 0
+
+
+def timed_outputs(prob):
+    """what a caller of the timed path receives after its last sweep: J, the policy values and the policy
+    indices (DPSolver.value_iteration's J and policy, DPSolver.last_policy_index).  Collective when sharded."""
+    J = prob.get_value()
+    pol, idx = prob.get_policy()
+    return {'J': J, 'policy': pol, 'policy_index': idx}
+
+
+def dump_outputs(outputs, dirname):
+    """--dump-outputs: `outputs` as DIR/<name>.npy in float32 / float64.  When they hold more than DUMP_MAX_BYTES,
+    every array keeps the same fixed, seeded sample of nodes, whose flat C-order ids go to DIR/nodes.npy.
+    Returns what goes into the JSON line."""
+    arrays = {}
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)   # (indices: exact)
+    S = arrays['J'].size
+    per_node = sum(a.nbytes for a in arrays.values()) // S
+    sampled = S * per_node > DUMP_MAX_BYTES
+    if sampled:
+        n = (DUMP_MAX_BYTES - 4096) // (per_node + 8)          # (4096: the .npy headers)
+        nodes = np.sort(np.random.default_rng(DUMP_SEED).choice(S, n, replace=False))
+        arrays = {name: a.reshape((S,) + a.shape[arrays['J'].ndim:])[nodes] for name, a in arrays.items()}
+        arrays['nodes'] = nodes.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a))
+    return {'dir': dirname, 'arrays': sorted(arrays), 'state_nodes': S,
+            'sampled_nodes': int(arrays['nodes'].size) if sampled else None}
+
+
 _REAL_STDOUT = []          # the program's real stdout while descriptor 1 is fenced (main)
 
 
@@ -325,9 +360,13 @@ def run(args):
         # second time -- it is not the content).  `value` is the second run; the first stands beside it (`first_run_from_idle`).
         cold = timed_region(prob) if not args.single_run else None
         elapsed, kernel_ms = timed_region(prob)
+        outputs = timed_outputs(prob) if args.dump_outputs else None      # (before anything else sweeps on prob)
         if rank != 0:
             return None
         out = report(args, locals())
+        if outputs is not None:
+            out['dumped_outputs'] = dump_outputs(outputs, args.dump_outputs)
+            del outputs
         if cold is not None:
             out['first_run_from_idle'] = {
                 'value': args.steps / cold[0], 'ms_per_step': 1e3 * cold[0] / args.steps, 'kernel_ms': cold[1] / args.steps,
@@ -373,7 +412,7 @@ def run_sharded(args, env):
     fault = os.environ.get('SDP_BENCH_FAULT', '')          # test hook: '<exchange>:<raise|hang|reject>:<rank>'
     f_exch, f_kind, f_rank = (fault.split(':') + ['', '', ''])[:3]
     phase_times, notes = {}, []
-    state = {'J_check': None}
+    state = {'J_check': None, 'outputs': {}}      # outputs: --dump-outputs, per measured exchange
     lock = threading.Lock()              # the watchdog thread reads notes / phase_times while this one fills them
 
     def note(text):
@@ -475,6 +514,9 @@ def run_sharded(args, env):
     def measure(exch, plan):
         prob = configure(exch, *plan)
         elapsed, kernel_ms = timed_region(prob)
+        if args.dump_outputs:                       # every rank takes part (the policy is gathered), rank 0 keeps them
+            got = timed_outputs(prob)
+            state['outputs'][exch] = got if rank == 0 else None
         e = dict(env, prob=prob, elapsed=elapsed, kernel_ms=kernel_ms, phase_times=dict(phase_times),
                  peer_note='; '.join(notes) or None)
         out = report(args, e) if rank == 0 else None
@@ -533,6 +575,8 @@ def run_sharded(args, env):
                 elif elapsed < best_elapsed:
                     best_out, best_elapsed = out, elapsed
                     best_cfg = (exch, plan)
+                for k_ in [k_ for k_ in state['outputs'] if k_ != best_cfg[0]]:
+                    del state['outputs'][k_]
         finally:
             dog.cancel()
     # ---- 3. the work-equivalent figure: the same chain with every control the long way (the certified filter
@@ -584,6 +628,8 @@ def run_sharded(args, env):
     if rank == 0:
         best_out['config']['comm_exchange_note'] = '; '.join(notes) or None
         best_out['config']['comm_phase_tuning_ms_per_sweep'] = dict(phase_times)
+        if args.dump_outputs:
+            best_out['dumped_outputs'] = dump_outputs(state['outputs'][best_cfg[0]], args.dump_outputs)
     return best_out
 
 
@@ -962,6 +1008,10 @@ def main():
                          'of the certified expectation-first filter (same bits either way; A/B runs)')
     ap.add_argument('--no-other-configs', action='store_true',
                     help='skip the untimed steady-state runs of the other BASELINE configurations')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last of them computed -- J, the policy values and the '
+                         'policy indices -- as DIR/<name>.npy in float32 / float64; above {} MB in all, a fixed seeded '
+                         'sample of the nodes (their ids in DIR/nodes.npy)'.format(DUMP_MAX_BYTES // 10 ** 6))
     ap.add_argument('--debug-define', action='append', default=[], metavar='NAME=VALUE',
                     help='diagnostic switch of the generated kernels (stodynprog_amd.codegen.DEBUG_NAMES; A/B runs of '
                          'tools/tune.py).  Recorded in config.debug_defines: such a line is not a product figure')

@@ -2,6 +2,7 @@
 and discretisation helpers.  The first block restates the reference's own unit
 tests (stodynprog/tests/test_stodynprog.py) against this package.  No GPU."""
 import io
+import os
 import contextlib
 import pickle
 
@@ -11,7 +12,7 @@ import pytest
 import stodynprog_amd
 from stodynprog_amd import SysDescription, DPSolver, models
 from stodynprog_amd.sysdesc import _zero_cost, _enforce_sig_len
-from conftest import golden
+from conftest import golden, GOLDEN
 
 
 # ---- reference tests/test_stodynprog.py:15-65 --------------------------------
@@ -265,12 +266,13 @@ def test_reference_pickle_format_round_trip(tmp_path):
     assert 'stodynprog.stodynprog' not in sys.modules      # the writer cleans up its shim
 
 
-@pytest.mark.skipif(not __import__('os').path.exists(
-    '/root/reference/examples/20 Searev storage control/P_sto_law.dat'),
-    reason='reference checkout not present (GPU box)')
 def test_load_the_reference_searev_policy_pickle():
+    """the policy law the reference ships with its Searev example (examples/20 Searev storage
+    control/P_sto_law.dat, a Python 2 protocol-0 pickle), stored gzip-compressed in tests/golden/"""
+    import gzip
     from stodynprog_amd import compat
-    it = compat.load_interpolator('/root/reference/examples/20 Searev storage control/P_sto_law.dat')
+    with gzip.open(os.path.join(GOLDEN, 'searev_P_sto_law.dat.gz'), 'rb') as f:
+        it = compat.load_interpolator(f)
     assert it.ndim == 3 and list(it._xshape) == [31, 61, 61]
     assert it.values.shape == (1, 31 * 61 * 61)
     assert np.allclose(it._xmax, [10., 1.016, 0.908])

@@ -71,3 +71,35 @@ def test_every_workload_names_a_model_builder(bench):
         assert hasattr(models, builder) and dtype in ('float64', 'float32')
         assert cfg in (None, 1, 2, 3, 4)
     assert bench.WORKLOADS['synth256'][3] == 3               # the metric's configuration
+
+
+def test_dump_outputs_whole_and_sampled(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 arrays only; past the size cap every array keeps the same seeded sample
+    of nodes (ids in nodes.npy), the files stay under the cap, and the sample is the same from run to run"""
+    import numpy as np
+    shape = (24, 20, 18)
+    J = np.random.default_rng(3).standard_normal(shape)
+    outputs = {'J': J, 'policy': np.stack([J, -J], axis=-1).astype(np.float32),
+               'policy_index': np.arange(J.size, dtype=np.int32).reshape(shape)}
+    whole = bench.dump_outputs(outputs, str(tmp_path / 'whole'))
+    assert whole['arrays'] == ['J', 'policy', 'policy_index'] and whole['sampled_nodes'] is None
+    back = {k: np.load(str(tmp_path / 'whole' / (k + '.npy'))) for k in whole['arrays']}
+    assert back['J'].dtype == np.float64 and np.array_equal(back['J'], J)
+    assert back['policy'].dtype == np.float32 and back['policy'].shape == shape + (2,)
+    assert back['policy_index'].dtype == np.float64 and np.array_equal(back['policy_index'], outputs['policy_index'])
+
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 4096 + 1000 * (8 + 8 + 8 + 8))
+    runs = []
+    for k in range(2):
+        d = tmp_path / 'sampled{}'.format(k)
+        info = bench.dump_outputs(outputs, str(d))
+        assert info['arrays'] == ['J', 'nodes', 'policy', 'policy_index'] and info['sampled_nodes'] == 1000
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= bench.DUMP_MAX_BYTES
+        runs.append({k_: np.load(str(d / (k_ + '.npy'))) for k_ in info['arrays']})
+    nodes = runs[0]['nodes'].astype(np.int64)
+    assert np.array_equal(nodes, np.unique(nodes)) and nodes.size == 1000
+    assert np.array_equal(runs[0]['J'], J.ravel()[nodes])
+    assert np.array_equal(runs[0]['policy'], outputs['policy'].reshape(-1, 2)[nodes])
+    assert np.array_equal(runs[0]['policy_index'], nodes)
+    for k_ in runs[0]:
+        assert np.array_equal(runs[0][k_], runs[1][k_]), k_

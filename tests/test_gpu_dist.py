@@ -193,6 +193,7 @@ def _with_hooks(tmp_path, script):
 
 
 def _run_ranks(script, world, extra_env, timeout=300, argv=(), ok_status=(0,)):
+    assert world <= 5, 'at most six processes may hold the GPU: the ranks and this one'
     port = _free_port()
     procs = []
     for rank in range(world):
@@ -253,16 +254,17 @@ CASES = [('synthetic3d', dict(N=20), 4, F64), ('synthetic3d', dict(N=20), 3, F64
          # 4-byte reals (pair table, wide first pass)
          ('synthetic3d', dict(N=20, stock_noise=0.07), 2, F64),
          ('two_reservoirs', dict(n_a=24, n_b=12, n_y=8, n_w=5, steps=(0.25, 0.25)), 2, F64),
-         ('two_reservoirs', dict(n_a=7, n_b=12, n_y=8, n_w=5, steps=(0.5, 0.25)), 1, F64),   # fewer rows than 8 ranks
+         ('two_reservoirs', dict(n_a=7, n_b=12, n_y=8, n_w=5, steps=(0.5, 0.25)), 1, F64),   # seven rows: uneven parts
          ('synthetic3d', dict(N=24), 2, F32),
          # round 5: a column count that is no multiple of ranks x phases (the reference's Searev grid: 61 x 61 = 3721
          # columns) -- uneven parts in every phase, padded and gathered with ONE all-gather -- over a chain of 20 sweeps
-         ('searev', dict(), 2, F64)]
+         ('searev', dict(), 2, F64),
+         ('two_reservoirs', dict(n_a=4, n_b=12, n_y=8, n_w=5, steps=(0.5, 0.25)), 1, F64)]   # fewer rows than 5 ranks
 if os.environ.get('SDP_TEST_CASES'):
     CASES = [CASES[int(k)] for k in os.environ['SDP_TEST_CASES'].split(',')]
 EXCHANGES = os.environ.get('SDP_TEST_EXCHANGES', 'rccl,peer,sparse,direct,sendrecv').split(',')
 # (SDP_TEST_REST: the exchanges of every case but the first -- the first one takes them all -- and only the sweeps,
-# not the whole API, for those cases: the 8-rank run is about partitions, mappings and the rendezvous)
+# not the whole API, for those cases: the 5-rank run is about partitions, mappings and the rendezvous)
 REST = [e for e in os.environ.get('SDP_TEST_REST', '').split(',') if e]
 REST_FROM = int(os.environ.get('SDP_TEST_REST_FROM', '1'))  # (the first REST_FROM cases take every exchange)
 # (SDP_TEST_FULL: of those first cases only these exchanges run the whole API, the others the sweeps.  With three and
@@ -336,15 +338,17 @@ print('rank', rank, 'all ok', flush=True)
 '''
 
 
-# (8 ranks: the partition / mapping / rendezvous logic with more ranks than rows or columns in some cases -- one
+# (5 ranks: the partition / mapping / rendezvous logic with more ranks than rows or columns in some cases -- one
 # case per kernel family is enough there, every exchange; the blocking stand-in with 2 ranks only: the
-# asynchronous one is the stricter test.  Round 3 ran all cases in all five set-ups: 280 s of the suite.)
-EIGHT = '0,10,12'                    # (a column kernel with every exchange; two stocks with fewer rows than ranks; uneven parts over 20 sweeps)
-REST8 = 'rccl,direct,sendrecv'       # every case but the first: the all-gather, the direct exchange, grouped sends / receives
+# asynchronous one is the stricter test.  Round 3 ran all cases in all five set-ups: 280 s of the suite.
+# Five ranks and the test process itself are the six processes that may hold the one GPU at a time: the largest
+# world a test starts, _run_ranks.)
+MANY = '0,13,12'                     # (a column kernel with every exchange; two stocks with fewer rows than ranks; uneven parts over 20 sweeps)
+REST_MANY = 'rccl,direct,sendrecv'   # every case but the first: the all-gather, the direct exchange, grouped sends / receives
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize('world,asynchronous,cases', [(2, False, ''), (2, True, ''), (3, True, ''), (8, True, EIGHT)])
+@pytest.mark.parametrize('world,asynchronous,cases', [(2, False, ''), (2, True, ''), (3, True, ''), (5, True, MANY)])
 def test_library_exchange_path_with_several_ranks_on_one_gpu(gpu, tmp_path, world, asynchronous, cases):
     """asynchronous: the stand-in only enqueues (staging copies + host-function rendezvous in
     stream order), so the library's events and stream joins carry the ordering, as with RCCL"""
@@ -352,8 +356,8 @@ def test_library_exchange_path_with_several_ranks_on_one_gpu(gpu, tmp_path, worl
     script = tmp_path / 'lib_worker.py'
     script.write_text(LIB_WORKER.format(root=ROOT))
     extra = dict(SDP_RCCL_LIBRARY=mock, SDP_TEST_CASES=cases)
-    if world >= 8:
-        extra['SDP_TEST_REST'] = REST8
+    if world >= 5:
+        extra['SDP_TEST_REST'] = REST_MANY
         extra['SDP_TEST_FULL'] = 'rccl'                           # (the whole API through the all-gather; sweeps through the others)
     elif world == 3:
         extra['SDP_TEST_EXCHANGES'] = 'rccl,sparse,direct,sendrecv'       # (peer copies: the 2-rank runs)
@@ -376,7 +380,8 @@ def test_bench_multi_rank_path_on_one_gpu(gpu, tmp_path, asynchronous):
     mock = _build_mock(tmp_path, asynchronous)
     outs = _run_ranks(_with_hooks(tmp_path, os.path.join(ROOT, 'bench.py')), 2, dict(SDP_RCCL_LIBRARY=mock),
                       argv=['--gpus', '2', '--grid', '48', '--steps', '3', '--warmup', '1',
-                            '--no-cpu-baseline', '--exchanges', 'rccl,sendrecv,direct,sparse,peer'])
+                            '--no-cpu-baseline', '--exchanges', 'rccl,sendrecv,direct,sparse,peer',
+                            '--dump-outputs', str(tmp_path / 'dump')])
     assert outs[1].strip() == ''
     lines = outs[0].strip().splitlines()
     assert len(lines) == 1, outs[0]
@@ -393,6 +398,13 @@ def test_bench_multi_rank_path_on_one_gpu(gpu, tmp_path, asynchronous):
     note = d['config']['comm_exchange_note']
     assert note is None or 'not faster in tuning' in note, note
     assert d['value'] > 0 and d['steps'] == 3 and d['warmup'] == 1
+    # --dump-outputs: rank 0 writes the gathered J / policy / indices of the reported exchange, whole at this size
+    import numpy as np
+    assert d['dumped_outputs']['arrays'] == ['J', 'policy', 'policy_index'] and d['dumped_outputs']['sampled_nodes'] is None
+    J, pol, idx = (np.load(str(tmp_path / 'dump' / (k + '.npy'))) for k in ('J', 'policy', 'policy_index'))
+    assert J.shape == (48, 48, 48) and pol.shape == (48, 48, 48, 1) and idx.shape == J.shape
+    assert J.dtype == pol.dtype == idx.dtype == np.float64 and np.isfinite(J).all()
+    assert idx.min() >= 0 and idx.max() < 64 and np.array_equal(idx, np.round(idx))
     import glob
     for leftover in glob.glob('/dev/shm/sdp_mock_*'):      # bench.py leaves its communicator to the OS
         os.unlink(leftover)
@@ -407,7 +419,7 @@ def test_bench_keeps_the_rccl_result_when_an_optional_exchange_fails(gpu, tmp_pa
     config.comm_exchange_note.  An exception or a wrong J end with status 0; a rank that HANGS is a hung GPU
     process: the line is printed, then every rank leaves with status 3 (a hang must not look like success).  (4 ranks on the asynchronous stand-in for the
     exception case: the 8-rank form of this test stalled once in round 4 -- all ranks silent for 560 s, not reproduced
-    in six further runs, cause not found; eight processes on one GPU are covered by the library test above; the watchdog case waits out its time limit, so it runs with 2 ranks.)"""
+    in six further runs, cause not found; the largest world on one GPU is the library test's above; the watchdog case waits out its time limit, so it runs with 2 ranks.)"""
     import json
     mock = _build_mock(tmp_path, asynchronous=True)
     env = dict(SDP_RCCL_LIBRARY=mock, SDP_BENCH_FAULT='peer:{}:1'.format(kind), SDP_BENCH_OPTIONAL_TIMEOUT='45')
