@@ -1066,18 +1066,22 @@ def column_window_config(n0, w, n_state, dtype, reach_rows):
     `seg_nodes` nodes of a column; its table holds `rows` rows of axis 0, enough
     for the segment plus `reach_rows` (the rows the controls of ONE node span,
     measured by the caller) plus the interpolation partner and a margin.  Two
-    512-thread workgroups per CU while that leaves segments of >= 64 nodes,
-    else one 1024-thread workgroup."""
+    512-thread workgroups per CU, where that leaves segments of >= 64 nodes.
+    (A 1024-thread form with one workgroup per CU is not planned: its image
+    never fitted the LDS before its partial minima were counted, and once they
+    were, its first run gave a wrong J -- tests/test_gpu_call_to_call.py.)"""
     rs = np.dtype(dtype).itemsize
     w = max(int(w), 1)
-    for threads, wgs in ((512, 2), (1024, 1)):
+    for threads, wgs in ((512, 2),):
         budget = COLUMN_LDS_MAX // wgs
-        fixed = _column_lds(w, w, 0, n_state, rs, threads)
+        # (the row window sweeps unfiltered: the image holds a partial minimum per thread, SDP_COL_LDS_PART)
+        fixed = _column_lds(w, w, 0, n_state, rs, threads, partial_minima=True)
         rows = (budget - fixed) // (w * rs)
         rows = min(rows // 32 * 32, n0)
         seg = (rows - int(reach_rows) - 4) // 64 * 64
         if rows >= 128 and seg >= 64:
-            return threads, _column_lds(w, w, rows, n_state, rs, threads), int(rows), int(min(seg, n0))
+            return (threads, _column_lds(w, w, rows, n_state, rs, threads, partial_minima=True), int(rows),
+                    int(min(seg, n0)))
     return None
 
 

@@ -29,7 +29,7 @@ import numpy as np
 from . import _native as nat
 from . import codegen
 from .interp import MlinInterpolator
-from .trace import TraceError, trace_model, trace_box, callable_fingerprint
+from .trace import TraceError, trace_model, trace_box, callable_fingerprint, _fp_value, _NoFingerprint
 
 __all__ = ['DPSolver']
 
@@ -90,6 +90,10 @@ class _DeviceProblem(object):
         self.h = h
         self.node_range = tuple(node_range)
         self.parts = None
+        # sharded: what DPSolver._set_exchange_lists keeps up to date -- the need lists of a sparse exchange, the lead
+        # halo -- and the bits of the constants they were made from
+        self.sparse_needs = self.lead_halo = False
+        self.lists_of = None
         if comm is not None:
             # slab_bounds: [n_phases][nranks+1] partition (dist.phase_partition)
             self.parts = np.ascontiguousarray(slab_bounds, dtype=np.int64)
@@ -933,6 +937,8 @@ class DPSolver(object):
                 prob = self._create_problem(fp, plan)
         if model.param_index is not None:
             prob.set_params(model.param_values())
+            if prob.lists_of is not None and prob.lists_of != np.asarray(model.param_values(), dtype=float).tobytes():
+                self._set_exchange_lists(prob, model, plan)
         self.backend_info = dict(prob.info, time_specialized=model.t_value is not None,
                                  lifted_constants=len(model.param_index or ()),
                                  # how the table of admissible boxes was made: 'traced' (the callback's DAG on the whole grid: exact
@@ -1028,10 +1034,8 @@ class DPSolver(object):
                         nat.check(nat.lib().sdp_problem_attach_comm(prob.h, self.comm.handle,
                                                                     int(prob.parts.shape[0]), nat.ptr(prob.parts)))
                 if exchange == 'peer' and sparse:
-                    off, ranges = self._peer_needs(model, prob.parts, shape)
-                    nat.check(nat.lib().sdp_problem_set_peer_needs(prob.h, nat.ptr(off), nat.ptr(ranges)))
+                    prob.sparse_needs = True
                     exchange = 'peer-sparse'
-                    prob.need_fraction = float((ranges[:, 1] - ranges[:, 0]).sum()) / S / self.comm.nranks
                 if exchange.startswith('peer') and self.comm_exchange == 'direct':
                     if self.comm.nranks <= 8:
                         nat.check(nat.lib().sdp_problem_set_direct_exchange(prob.h, 1))
@@ -1045,16 +1049,13 @@ class DPSolver(object):
                 # it is the RCCL all-gather
                 if sparse:
                     nat.check(nat.lib().sdp_problem_set_sendrecv_exchange(prob.h, 1))
-                    off, ranges = self._peer_needs(model, prob.parts, shape)
-                    nat.check(nat.lib().sdp_problem_set_peer_needs(prob.h, nat.ptr(off), nat.ptr(ranges)))
+                    prob.sparse_needs = True
                     exchange = 'sendrecv'
-                    prob.need_fraction = float((ranges[:, 1] - ranges[:, 0]).sum()) / S / self.comm.nranks
             elif self.comm_exchange != 'rccl':
                 raise ValueError("comm_exchange must be 'rccl', 'sendrecv', 'peer' or 'direct'")
-        if plan.get('lead_axes') and self.comm is not None and self.comm.is_device and self.comm.nranks > 1:
-            # rows of the first stock a node's controls reach (sampled: the kernel notices a node that
-            # reaches further and evaluates it from the value array itself)
-            nat.check(nat.lib().sdp_problem_set_lead_halo(prob.h, self._lead_reach_rows(model, plan, None, around=True) + 1))
+        prob.lead_halo = bool(plan.get('lead_axes') and self.comm is not None and self.comm.is_device
+                              and self.comm.nranks > 1)
+        self._set_exchange_lists(prob, model, plan)
         prob.info = dict(mode='traced', exchange=exchange,
                          kernel='column' if column else ('staged' if plan['staged'] else
                                                          ('lead' if plan.get('lead_axes') else ('line' if plan.get('line') else 'generic'))),
@@ -1080,6 +1081,32 @@ class DPSolver(object):
                          # diagnostic switches this code object was built with (None in the product)
                          debug_defines=codegen.check_debug(self.debug_defines))
         return prob
+
+    def _set_exchange_lists(self, prob, model, plan):
+        """What the sharded exchanges predict from the model: the need lists of the sparse exchanges (the rows of J
+        each rank reads) and the lead halo of the reduced-array sweep (the rows of the first stock a node's controls
+        reach; sampled: the kernel notices a node that reaches further and evaluates it from the value array itself).
+        Both depend on the values of the model's constants, and a problem of lifted constants serves every value: they
+        are made again when a call brings other values (DPSolver._problem), on every rank alike -- every rank computes
+        every rank's list from the same model, so the lists agree."""
+        if not (prob.sparse_needs or prob.lead_halo):
+            return
+        if prob.lists_of is not None:
+            # (the library takes new lists only while J and V are whole: rows another rank sent under the old lists
+            # must not be read under the new ones.  Collective, like the calls of every rank that lead here)
+            prob.complete()
+            prob.swap()
+            prob.complete()
+            prob.swap()
+        if prob.sparse_needs:
+            off, ranges = self._peer_needs(model, prob.parts, prob.shape)
+            nat.check(nat.lib().sdp_problem_set_peer_needs(prob.h, nat.ptr(off), nat.ptr(ranges)))
+            prob.need_fraction = float((ranges[:, 1] - ranges[:, 0]).sum()) / prob.S / self.comm.nranks
+        if prob.lead_halo:
+            nat.check(nat.lib().sdp_problem_set_lead_halo(prob.h, self._lead_reach_rows(model, plan, None, around=True) + 1))
+        # (the constants the lists were made from: a trace of literal constants has a source, and so a problem, of its own)
+        prob.lists_of = (np.asarray(model.param_values(), dtype=float).tobytes() if model.param_index is not None
+                         else b'')
 
     def _peer_needs(self, model, parts, shape):
         """For the sparse peer exchange: per rank the node ranges (device order, whole columns) of
@@ -1679,7 +1706,8 @@ class DPSolver(object):
 
 
 def _params_key(params):
-    """hashable, untruncated image of a params dict (repr() shortens large arrays)"""
+    """hashable, untruncated image of a params dict (repr() shortens large arrays); reals by their bits (0.0 == -0.0,
+    yet np.copysign tells them apart)"""
     out = []
     for k in sorted(params):
         v = params[k]
@@ -1687,10 +1715,13 @@ def _params_key(params):
             out.append((k, v.dtype.str, v.shape, v.tobytes()))
         else:
             try:
-                hash(v)
-                out.append((k, v))
-            except TypeError:
-                out.append((k, repr(v)))
+                out.append((k, _fp_value(v, 0, [1 << 20])))
+            except _NoFingerprint:
+                try:
+                    hash(v)
+                    out.append((k, type(v).__name__, v))
+                except TypeError:
+                    out.append((k, repr(v)))
     return tuple(out)
 
 

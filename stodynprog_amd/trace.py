@@ -14,8 +14,11 @@ Anything that needs a concrete value (`if x > 0:`, `float(x)`, `max(a, b)`,
 indexing an array with x) raises TraceError; the solver then reports the model
 as not traceable (tabulated mode evaluates such callables on the host).
 """
+import functools
 import math
 import numbers
+import struct
+import types
 
 import numpy as np
 
@@ -1170,31 +1173,44 @@ def trace_box(control_box, n_state, n_control, params=None, stationnary=True, t_
 # Is a callable still what it was when it was traced?  The reference evaluates dyn, cost and control_box at call time
 # (stodynprog.py:440, 674-676), so data they read may change between two calls; DPSolver therefore traced them afresh
 # on every call (~0.1 ms each: as much as the kernels of the reference's own problem sizes).  A FINGERPRINT of a
-# callable is everything a pure Python function's result can depend on besides its arguments, by VALUE: its code object,
-# its defaults, the contents of its closure cells and of the globals its code names -- numbers, strings, small arrays
+# callable is everything a pure Python function's result can depend on besides its arguments, by VALUE: its code object
+# and every code object nested in it (bytecode, constants, names), its defaults, the contents of its closure cells and
+# of the globals any of that code names -- numbers (reals by their bits: 0.0 is not -0.0), strings, small arrays
 # (bytes), tuples / lists / dicts of those, other Python functions (recursively), library modules and builtins by
-# identity.  Anything else -- an object with attributes, a module that is not a library, an array beyond 64 KiB,
-# deep nesting -- has NO fingerprint (None) and the callable is traced on every call as before: the cache can only
+# identity.  Anything else -- an object with attributes, a function with attributes of its own, a module that is not a
+# library, an array beyond 64 KiB, deep nesting, code that looks names up at run time (globals(), vars(), eval,
+# getattr, ...) -- has NO fingerprint (None) and the callable is traced on every call as before: the cache can only
 # ever return the trace of a callable that would trace to the same graph.
 # ---------------------------------------------------------------------------
 _FP_LIBRARIES = ('numpy', 'math', 'cmath', 'scipy', 'operator', 'functools', 'itertools', 'builtins')
 _FP_MAX_ARRAY_BYTES = 1 << 16
 _FP_MAX_ITEMS = 512
+# builtins through which code reaches state by a name it computes at run time: out of the fingerprint's sight
+_FP_DYNAMIC = frozenset(('globals', 'locals', 'vars', 'eval', 'exec', 'compile', 'getattr', '__import__', 'dir'))
+_FP_CODE_MEMO = {}                  # id(code) -> (code, its image, the names of its tree, looks names up at run time)
+_FP_CODE_MEMO_MAX = 4096
 
 
 class _NoFingerprint(Exception):
     pass
 
 
+def _fp_real(v):
+    return struct.pack('<d', v)
+
+
 def _fp_value(v, depth, budget):
-    import types
     budget[0] -= 1
     if budget[0] < 0 or depth > 4:
         raise _NoFingerprint
-    if v is None or isinstance(v, (bool, int, float, complex, str, bytes)):
-        return (type(v).__name__, v if v == v else 'nan')
-    if isinstance(v, np.generic):
+    if isinstance(v, np.generic):                                # (before float: np.float64 is a float)
         return ('g', v.dtype.str, v.tobytes())
+    if isinstance(v, float):
+        return ('f', _fp_real(v))
+    if isinstance(v, complex):
+        return ('c', _fp_real(v.real), _fp_real(v.imag))
+    if v is None or isinstance(v, (bool, int, str, bytes)):
+        return (type(v).__name__, v)
     if isinstance(v, np.ndarray):
         if v.nbytes > _FP_MAX_ARRAY_BYTES or v.dtype.kind == 'O':
             raise _NoFingerprint
@@ -1207,20 +1223,47 @@ def _fp_value(v, depth, budget):
         except TypeError:
             raise _NoFingerprint
         return ('d',) + tuple((_fp_value(k, depth + 1, budget), _fp_value(v[k], depth + 1, budget)) for k in keys)
+    if isinstance(v, frozenset):                                 # (`x in {1.0, 2.0}` compiles to one)
+        return ('fs',) + tuple(sorted(repr(_fp_value(x, depth + 1, budget)) for x in v))
     if isinstance(v, types.ModuleType):
         if v.__name__.split('.')[0] in _FP_LIBRARIES:
             return ('m', v.__name__)
         raise _NoFingerprint
     if isinstance(v, (types.BuiltinFunctionType, np.ufunc)) or (isinstance(v, type) and v.__module__ in ('builtins', 'numpy')):
         return ('b', getattr(v, '__module__', None), getattr(v, '__qualname__', getattr(v, '__name__', None)), id(v))
-    if isinstance(v, (types.FunctionType, types.MethodType)) or type(v).__name__ == 'partial':
+    if isinstance(v, (types.FunctionType, types.MethodType, functools.partial)):
         return _fp_callable(v, depth + 1, budget)
     raise _NoFingerprint
 
 
+def _fp_code(code):
+    """image of a code object and of every code object nested in it (def, lambda, comprehension, at any depth), by
+    value -- bytecode, constants, names, free variables -- with the global / attribute names the tree reads and whether
+    it calls a builtin that looks names up at run time.  Code objects are immutable: memoised (the memo keeps each
+    code object alive, so an id() in it is never reused)"""
+    kept = _FP_CODE_MEMO.get(id(code))
+    if kept is not None and kept[0] is code:
+        return kept[1:]
+    names = set(code.co_names)
+    consts = []
+    inner = []
+    for c in code.co_consts:
+        if isinstance(c, types.CodeType):
+            image, sub, _ = _fp_code(c)
+            inner.append(image)
+            names.update(sub)
+        else:
+            consts.append(c)
+    image = ('code', code.co_code, _fp_value(tuple(consts), 0, [1 << 30]), code.co_names, code.co_freevars,
+             code.co_cellvars, code.co_argcount, code.co_kwonlyargcount, code.co_flags, tuple(inner))
+    names = frozenset(names)
+    if len(_FP_CODE_MEMO) >= _FP_CODE_MEMO_MAX:
+        _FP_CODE_MEMO.clear()
+    _FP_CODE_MEMO[id(code)] = (code, image, names, bool(names & _FP_DYNAMIC))
+    return image, names, bool(names & _FP_DYNAMIC)
+
+
 def _fp_callable(fn, depth, budget):
-    import functools
-    import types
     if isinstance(fn, functools.partial):
         return ('partial', _fp_callable(fn.func, depth, budget), _fp_value(tuple(fn.args), depth, budget),
                 _fp_value(dict(fn.keywords or {}), depth, budget))
@@ -1231,27 +1274,23 @@ def _fp_callable(fn, depth, budget):
     code = fn.__code__
     if getattr(fn.__module__, 'split', None) and (fn.__module__ or '').split('.')[0] in _FP_LIBRARIES:
         return ('lib', fn.__module__, fn.__qualname__, id(code))
-    parts = ['f', id(code), code.co_code, _fp_value(code.co_consts if not any(isinstance(c, types.CodeType) for c in code.co_consts)
-                                                   else tuple(c for c in code.co_consts if not isinstance(c, types.CodeType)), depth, budget)]
-    for c in code.co_consts:
-        if isinstance(c, types.CodeType):                    # a nested def / lambda / comprehension: its names count too
-            parts.append(('inner', c.co_code, tuple(c.co_names)))
-    parts.append(_fp_value(fn.__defaults__, depth, budget))
-    parts.append(_fp_value(fn.__kwdefaults__, depth, budget))
+    if fn.__dict__:
+        raise _NoFingerprint                               # (attributes of its own: `dyn.g`, read through its global name)
+    image, names, dynamic = _fp_code(code)
+    glob = fn.__globals__
+    if dynamic and any(n in _FP_DYNAMIC and n not in glob for n in names):
+        raise _NoFingerprint
+    parts = ['f', image, _fp_value(fn.__defaults__, depth, budget), _fp_value(fn.__kwdefaults__, depth, budget)]
     for cell in fn.__closure__ or ():
         try:
             parts.append(_fp_value(cell.cell_contents, depth, budget))
         except ValueError:                                  # an empty cell
             parts.append(('empty',))
-    glob = fn.__globals__
-    names = set(code.co_names)
-    for c in code.co_consts:
-        if isinstance(c, types.CodeType):
-            names.update(c.co_names)
     for name in sorted(names):
         if name in glob:
             v = glob[name]
-            if v is fn:
+            if v is fn:                                     # (recursion: this very function, seen above)
+                parts.append((name, 'self'))
                 continue
             parts.append((name, _fp_value(v, depth, budget)))
         # (a name that is neither a global nor a builtin is an attribute name: it belongs to a value seen elsewhere)
@@ -1261,8 +1300,6 @@ def _fp_callable(fn, depth, budget):
 def callable_fingerprint(*callables_and_data):
     """hashable image of everything the results of these callables (pure Python functions) and data (params dicts,
     numbers) can depend on besides their arguments, or None when that cannot be established (see above)"""
-    import types
-    import functools
     budget = [_FP_MAX_ITEMS]
     try:
         out = []

@@ -485,3 +485,124 @@ def test_bench_under_the_real_launcher(gpu, tmp_path):
     for leftover in glob.glob('/dev/shm/sdp_mock_*'):
         os.unlink(leftover)
     assert not glob.glob('/dev/shm/sdp_rccl_uid_{}_*'.format(port))      # rank 0 removed its file
+
+
+# ---------------------------------------------------------------------------
+# a parameter study on several ranks: one device problem of lifted constants serves every later value of a
+# coefficient, while the need lists of the sparse exchanges (which rows of J a rank reads) and the lead halo are
+# predictions made from the model's constants -- they must follow the values, on every rank alike
+# ---------------------------------------------------------------------------
+STUDY_WORKER = r'''
+import os, sys, io, contextlib
+sys.path.insert(0, {root!r})
+import numpy as np
+from stodynprog_amd import SysDescription, DPSolver, models, dist
+dev, rdv = dist.from_env()
+rank, nranks = dev.rank, dev.nranks
+CASE = os.environ['SDP_STUDY_CASE']
+EXCHANGES = os.environ['SDP_STUDY_EXCHANGES'].split(',')
+
+def quiet(fn, *a, **k):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return fn(*a, **k)
+
+def where(a, b):
+    bad = np.argwhere(np.asarray(a) != np.asarray(b))
+    return 'identical' if not len(bad) else '%d of %d entries differ, index ranges %s' % (
+        len(bad), np.asarray(a).size, [(int(lo), int(hi)) for lo, hi in zip(bad.min(axis=0), bad.max(axis=0))])
+
+def build(coef):
+    if CASE == 'ar1':
+        # storage-separable, the exogenous process an AR(1) whose coefficient moves the columns a rank reads
+        s = SysDescription((2, 1, 1), name='rho study')
+        s.dyn = lambda e, p, u, w: (e + u - 0.02 * abs(u), coef['v'] * p + w)
+        s.cost = lambda e, p, u, w: (p - u) * (p - u) + 0.1 * u * u
+        s.control_box = lambda e, p: ((-1., 1.),)
+        s.perturb_laws = [models.NormalLaw(0, 0.3)]
+        solver = DPSolver(s)
+        solver.discretize_state(0, 4, 21, -2, 2, 40)
+        solver.discretize_perturb(-0.9, 0.9, 5)
+        solver.control_steps = (0.25,)
+    else:
+        # two stocks next to an exogenous inflow (the reduced-array sweep): the inflow's gain moves the rows of the
+        # first stock a node's controls reach -- the lead halo
+        s = SysDescription((3, 2, 1), name='inflow study')
+        s.dyn = lambda a, b, y, u, v, w: (a + coef['v'] * (0.7 + 0.5 * y) - u, b + u - v, 0.3 + 0.7 * (y - 0.3) + w)
+        s.cost = lambda a, b, y, u, v, w: ((v - 0.8) * (v - 0.8) + 0.05 * (u - v) * (u - v)
+                                           + 4.0 * np.where(a > 1.7, a - 1.7, 0.0 * a) + 8.0 * np.where(b < 0.3, 0.3 - b, 0.0 * b))
+        s.control_box = lambda a, b, y: ((0., 1.), (0., 1.))
+        s.perturb_laws = [models.NormalLaw(0, 0.1)]
+        solver = DPSolver(s)
+        solver.discretize_state(0., 2., 24, 0., 2., 12, -0.2, 0.8, 8)
+        solver.discretize_perturb(-0.3, 0.3, 5)
+        solver.control_steps = (0.25, 0.25)
+    return solver
+
+VALUES = dict(ar1=(0.8, 0.5, 0.95, -0.9), reservoirs=(0.9, 0.6, 2.2, -0.85))[CASE]     # (none equals another constant of the model)
+rng = np.random.default_rng(9)
+for exchange in EXCHANGES:
+    coef = dict(v=VALUES[0])
+    one, two = build(coef), build(coef)
+    two.comm = dev
+    two.comm_phases = 1
+    two.comm_exchange = 'peer' if exchange == 'sparse' else exchange
+    two.comm_sparse = exchange in ('sparse', 'direct')
+    counted = []
+    real_needs = two._peer_needs
+    two._peer_needs = lambda *a: counted.append(1) or real_needs(*a)
+    V0 = rng.standard_normal(one._state_grid_shape)
+    probs, needs, calls = [], [], []
+    for v in VALUES + VALUES[:1]:
+        coef['v'] = v
+        J1, p1 = one.value_iteration(V0, report_time=False)
+        K1, _ = quiet(one.value_iterations, V0, 3)
+        E1 = quiet(one.eval_policy, p1, 3, False, V0)
+        K2, _ = quiet(two.value_iterations, V0, 3)
+        E2 = quiet(two.eval_policy, p1, 3, False, V0)
+        assert np.array_equal(K1, K2), (exchange, v, two.backend_info['exchange'], where(K1, K2))
+        assert np.array_equal(E1, E2), (exchange, v, two.backend_info['exchange'], where(E1, E2))
+        prob = [p for k, p in two._cache.items() if k[0] == 'problem'][0]
+        probs.append(prob)
+        calls.append(len(counted))
+        if CASE == 'ar1':
+            off, rg = real_needs(two._trace_now(), prob.parts, two._shape())
+            needs.append([set(c for b, e in rg[off[r]:off[r + 1]] for c in range(b, e)) for r in range(nranks)])
+    info = two.backend_info
+    if CASE == 'ar1':
+        assert info['exchange'] == dict(sendrecv='sendrecv', sparse='peer-sparse', direct='direct-sparse')[exchange], info
+        # the test's teeth: a later value's need list is not contained in the one the lifted problem was made with
+        assert any(not (needs[k][r] <= needs[1][r]) for k in (2, 3) for r in range(nranks)), needs
+        # the lists are made once per value, not once per call
+        assert calls == [1, 2, 3, 4, 5], calls
+    else:
+        assert info['kernel'] == 'lead' == one.backend_info['kernel'], info
+    assert info['lifted_constants'] > 0
+    assert probs[1] is probs[2] is probs[3] is probs[4], 'the lifted problem must serve v2 .. v4 and v1 again'
+    print('rank', rank, CASE, exchange, 'ok', flush=True)
+    held = [two._cache.pop(k) for k in [k for k in list(two._cache) if k[0] == 'problem']]
+    for p in held:
+        p.unmap_peers()                 # (every rank drops its mappings of the peers' buffers before any is freed)
+    dev.barrier()
+    for p in held:
+        p.close()
+    del probs, prob, held
+dev.close()
+print('rank', rank, 'all ok', flush=True)
+'''
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('world,case,exchanges', [(2, 'ar1', 'sendrecv,sparse,direct'),
+                                                  (4, 'ar1', 'sendrecv,sparse,direct'),
+                                                  (2, 'reservoirs', 'rccl,direct')])
+def test_parameter_study_on_several_ranks_follows_the_values(gpu, tmp_path, world, case, exchanges):
+    """value_iterations(V, 3) and eval_policy(pol, 3) of one sharded solver over five values of a coefficient (the
+    second lifts the constants, the later ones reuse that device problem) equal a single-process solver's, bit for bit,
+    on the sparse exchanges (need lists) and on the reduced-array sweep (lead halo); the asynchronous stand-in"""
+    mock = _build_mock(tmp_path, asynchronous=True)
+    script = tmp_path / 'study_worker.py'
+    script.write_text(STUDY_WORKER.format(root=ROOT))
+    outs = _run_ranks(_with_hooks(tmp_path, script), world,
+                      dict(SDP_RCCL_LIBRARY=mock, SDP_STUDY_CASE=case, SDP_STUDY_EXCHANGES=exchanges))
+    for rank, out in enumerate(outs):
+        assert 'rank {} all ok'.format(rank) in out, out

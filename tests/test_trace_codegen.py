@@ -389,6 +389,29 @@ def test_percontrol_and_window_shapes():
     assert codegen.staged_row_stride(19, 32, 2, 8) == 19 and codegen.staged_row_stride(20, 8, 3, 4) == 21
 
 
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+@pytest.mark.parametrize('n0,w,d', [(2048, 11, 2), (1024, 32, 3), (4096, 5, 2)])
+def test_row_window_image_fits_its_workgroups(n0, w, d, dtype):
+    """The row window sweeps unfiltered, so its LDS image (struct SdpColLds) holds a partial minimum per thread:
+    the planned image must count it and fit the LDS share of its workgroups -- 512 threads used to plan past half of
+    the 160 KiB of a CU (one workgroup per CU instead of two), and 1024 threads (a long reach along axis 0) 12 KiB past
+    all of it, a unit hipcc rejects: that form is no longer planned (a reach that long gets no row window)"""
+    from stodynprog_amd import codegen
+    rs = np.dtype(dtype).itemsize
+    seen = set()
+    for reach in range(0, n0, 8):
+        cfg = codegen.column_window_config(n0, w, d, dtype, reach)
+        if cfg is None:
+            continue
+        threads, lds, rows, seg = cfg
+        seen.add(threads)
+        assert lds == codegen._column_lds(w, w, rows, d, rs, threads, partial_minima=True)
+        assert lds <= codegen.COLUMN_LDS_MAX // (2 if threads == 512 else 1), (reach, cfg)
+        assert seg >= 64 and rows - reach - 4 >= seg
+    assert seen == {512}
+    assert codegen.column_window_config(n0, w, d, dtype, n0 - 64) is None
+
+
 def test_certified_filter_planning_without_a_gpu():
     """where the column kernel gets the certified expectation-first filter (SDP_COL_FILTER of
     csrc/sdp_colfilter_kernel.h) and the workgroup shape that goes with it: one lane per node"""
