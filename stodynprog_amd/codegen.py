@@ -432,7 +432,7 @@ def lanes_for(max_controls):
     return lanes
 
 
-def _prologue_lines(model, real, lanes, debug):
+def _prologue_lines(model, real, lanes, debug, peer_stores=False):
     """what every generated unit starts with: the type and shape macros, the diagnostic
     switches of an explicit `debug` dict (none in the product), the device helpers, the
     lifted constants, the interpolation tables and sdp_model_cell"""
@@ -441,7 +441,9 @@ def _prologue_lines(model, real, lanes, debug):
              '#define SDP_D {}'.format(model.n_state),
              '#define SDP_NU {}'.format(model.n_control),
              '#define SDP_HAS_W {}'.format(1 if model.n_perturb else 0),
-             '#define SDP_LANES {}'.format(int(lanes))]
+             '#define SDP_LANES {}'.format(int(lanes)),
+             '#define SDP_PEER_STORES {}     // the backup kernels also store J into other ranks (direct exchange)'.format(
+                 1 if peer_stores else 0)]
     if _dbg(debug, 'SDP_STAMP') in ('1', '2', '3'):
         lines.append('#define SDP_STAMP {}     // diagnostic build: in-kernel clock stamps (tools/clock_probe.py, '
                      'tools/phase_probe.py)'.format(int(_dbg(debug, 'SDP_STAMP'))))
@@ -623,7 +625,7 @@ def line_functions_source(model):
 
 def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
                      per_control=None, filtered=False, utab=None, lead_axes=0, col_cfg=None, debug=None, wres=0,
-                     lead_perm=None, line=0):
+                     lead_perm=None, line=0, peer_stores=False):
     """column: None for the generic node-order kernels, or (N0, W[, controls, columns]) to also
     build the column kernels of csrc/sdp_column_kernel.h for a storage-separable
     model on a grid with N0 points along axis 0 and W perturbation points.
@@ -639,10 +641,12 @@ def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
     csrc/sdp_colfilter_kernel.h; see `column_filter_applies`).
     utab: None, or (frontier nodes, capacity of the control table in controls) of `control_table_plan`
     (filtered kernel only): the first pass reads the column-uniform sub-expressions from a table.
-    debug: None (the product), or a dict of diagnostic switches (see DEBUG_NAMES)."""
+    debug: None (the product), or a dict of diagnostic switches (see DEBUG_NAMES).
+    peer_stores: the unit's backup kernels also store J into the buffers of other ranks (the direct exchange,
+    SdpSweepArgs.peer_J); without it they hold no code for that, and the library refuses the direct exchange."""
     debug = check_debug(debug)
     real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
-    head = _prologue_lines(model, real, lanes, debug)
+    head = _prologue_lines(model, real, lanes, debug, peer_stores)
     if column is not None:
         assert model.column_shareable
         if per_control is not None:

@@ -190,7 +190,7 @@ SDP_DEV sdp_real sdp_col_filter_dcol(SdpColLds &m, int parity)
 {
     if (!SDP_COL_LEAN_ON && !SDP_COL_WIDE_ON) return (sdp_real)0;
     const unsigned long long bits = m.dcol[parity];
-    if (threadIdx.x == 0) m.dcol[parity ^ 1] = 0ull;
+    if (sdp_col_tid() == 0) m.dcol[parity ^ 1] = sdp_col_opaque(0ull);
     return (sdp_real)__longlong_as_double((long long)bits);
 }
 
@@ -576,7 +576,8 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
     // starts, their order, the row count -- from the table made here two units ago; only what follows from h is redone.
     (void)psum; (void)k_rows; (void)x_cap; (void)psum_d; (void)a_known;
     if (count == 0) count = (int)blockDim.x - first;
-    if ((int)threadIdx.x < first || (int)threadIdx.x >= first + count) return;
+    const int tid = sdp_col_tid();
+    if (tid < first || tid >= first + count) return;
     SdpBox box;
     if (box_c) box = *box_c;
     else sdp_load_box(a, 0, box);                           // (one box for every node: checked at launch)
@@ -599,7 +600,7 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
     constexpr sdp_real BNB_DELTA = sizeof(sdp_real) == 8 ? (sdp_real)0x1p-20 : (sdp_real)0x1p-8;      // (4-byte reals: the kernel's own positions are off by ~2^-15 rows)
     constexpr bool BNB_WIDE = sizeof(sdp_real) == 4;       // records: (start as a 4-byte real, -, smallest +-h psum as an 8-byte real)
     sdp_real *rec = utab + SDP_COL_UTAB * SDP_COL_UTAB_N + 4;
-    const int lane_u = (int)threadIdx.x - first;
+    const int lane_u = tid - first;
     bool bnb_fine = count == 64 && SDP_BNB_BLOCK <= 64;
     sdp_real bnb_prev_hi = -INFINITY, bnb_prev_lo = (sdp_real)NAN, bnb_between = (sdp_real)0, bnb_amax = (sdp_real)0;
     for (int c0 = 0; c0 < n_tab; c0 += 64) {               // (every lane of the wave takes part in every round: shuffles)
@@ -712,7 +713,7 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
         }
     }
 #else
-    for (int ci_ = (int)threadIdx.x - first; ci_ < n_tab; ci_ += count) {
+    for (int ci_ = tid - first; ci_ < n_tab; ci_ += count) {
         int ci = ci_;
         asm volatile("" : "+v"(ci));                        // (opaque to the optimiser: see the loop above)
         sdp_real u[SDP_NU], tab[SDP_COL_UTAB];
@@ -736,7 +737,7 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
     fin = sdp_wave_sum(fin);
     if (a_known) {
         // (what this buffer said two units ago about a stands; a poisoned entry stays poisoned)
-        if ((int)threadIdx.x == first) {
+        if (tid == first) {
             sdp_real *st = utab + SDP_COL_UTAB * SDP_COL_UTAB_N;
             const sdp_real before = st[2];
             st[2] = (count == 64 && fin < SDP_COL_FILTER_LIMIT && before == before) ? h_abs : (sdp_real)NAN;
@@ -745,7 +746,7 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
     }
     a_lo = sdp_wave_min(a_lo);
     a_hi = sdp_wave_max(a_hi);
-    if ((int)threadIdx.x == first) {
+    if (tid == first) {
         sdp_real *st = utab + SDP_COL_UTAB * SDP_COL_UTAB_N;
         st[0] = a_lo;
         st[1] = a_hi;

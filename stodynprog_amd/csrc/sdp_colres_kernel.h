@@ -77,7 +77,7 @@ SDP_DEV void sdp_colres_tail(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
 {
     constexpr int N0 = SDP_COL_ROWS, C = SDP_COL_WRES, LW = SDP_COL_A_LW, NV = 1 << SDP_DT;
     const sdp_real *__restrict__ V = (const sdp_real *)a.V + s.r0;
-    const int rl = threadIdx.x % LW, wg = threadIdx.x / LW;
+    const int tid = sdp_col_tid(), rl = tid % LW, wg = tid / LW;
 #pragma unroll
     for (int wi = 0; wi < SDP_HOLD_NW; ++wi) {
         const int tw = wg + wi * SDP_HOLD_WP, w = C + tw;
@@ -478,7 +478,8 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
             box_hold.total = sdp_uniform(box_hold.total);
             box_c = &box_hold;
         }
-        if (lane < Wn) { w_hold = ((const sdp_real *)a.wgrid)[lane]; w_mine = &w_hold; }
+        // (the held tail has no registers to spare for it: phase W loads the point where it uses it)
+        if (lane < Wn && !SDP_COL_TAIL_HOLD) { w_hold = ((const sdp_real *)a.wgrid)[lane]; w_mine = &w_hold; }
     }
 #if SDP_COL_SHIFT
     if (threadIdx.x < 2) sdp_col_shift_reset(sdp_lds, threadIdx.x);
@@ -502,7 +503,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
         const int i_hi = (int)((unsigned)(N0 * (part + 1)) / (unsigned)a.col_splits);
         sdp_real x[SDP_D];
         sdp_col_coords(a, col, x);
-        const int r = (int)threadIdx.x;                    // the table row this thread reduces
+        const int r = sdp_col_tid();                       // the table row this thread reduces
         // ---- tail of the table, partial sums of the reduced table
         SDP_RES_MARK(tm0);
         __syncthreads();                                   // the previous unit has left the table; this unit's cells are published

@@ -227,6 +227,23 @@ constexpr int sdp_bnb_block(int n) { int b = 8; while ((n + b - 1) / b > 64) b *
 #ifndef SDP_COL_LDS_PAD
 #define SDP_COL_LDS_PAD 0        // diagnostic builds: unused bytes in the LDS image (fewer workgroups per CU: occupancy A/B)
 #endif
+// This thread's index, as the building blocks of a unit see it.  In the held-tail form (SDP_COL_TAIL_HOLD of
+// sdp_colres_kernel.h) 32 registers of table entries stay live through most of a unit, and the optimiser hoisted
+// what every building block derives from the index alone -- LDS and table addresses, row and lane numbers -- out of
+// the unit loop into registers the kernel does not have at four waves per SIMD: they went to scratch memory and came
+// back once per unit, each a memory round trip.  There the index is opaque (an empty asm statement the optimiser may
+// neither hoist nor see through), so what follows from it is recomputed where it is used: a few integer operations.
+// (sdp_col_opaque: the same for any other value -- a constant the optimiser would otherwise keep in a register pair
+// across the loop, a uniform value that everything in a unit's bound derives from)
+template <typename T>
+SDP_DEV T sdp_col_opaque(T v)
+{
+#if defined(SDP_COL_TAIL_HOLD) && SDP_COL_TAIL_HOLD
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+SDP_DEV int sdp_col_tid() { return sdp_col_opaque((int)threadIdx.x); }
 #ifndef SDP_COL_HOIST
 // 1: what does not change from unit to unit is fetched ONCE per workgroup instead of once per unit -- the control
 // box of a constant-box problem (its loads and the division of numpy.linspace's step sat at the head of every
@@ -426,11 +443,12 @@ SDP_DEV void sdp_col_phase_w(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
     const sdp_real *__restrict__ wgrid = (const sdp_real *)a.wgrid;
 #endif
     if (count == 0) count = (int)blockDim.x - first;
-    if ((int)threadIdx.x < first || (int)threadIdx.x >= first + count) return;
-    for (int w = (int)threadIdx.x - first; w < Wn; w += count) {
+    const int tid = sdp_col_tid();
+    if (tid < first || tid >= first + count) return;
+    for (int w = tid - first; w < Wn; w += count) {
         sdp_real xn[SDP_D];
 #if SDP_HAS_W
-        sdp_model_trail(x, u, (w_mine && w == (int)threadIdx.x - first) ? *w_mine : wgrid[w], t, xn);
+        sdp_model_trail(x, u, (w_mine && w == tid - first) ? *w_mine : wgrid[w], t, xn);
 #else
         sdp_model_trail(x, u, (sdp_real)0, t, xn);
 #endif
@@ -507,8 +525,9 @@ SDP_DEV void sdp_col_phase_a(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
     // consecutive lanes read LW consecutive rows (LW x sizeof(real) contiguous bytes).
     constexpr int LW = SDP_COL_A_LW;                     // lanes (= consecutive rows) per perturbation point
     const int WPASS = blockDim.x / LW;                   // perturbation points handled side by side (the
-    const int rl = threadIdx.x % LW;                     //  policy-evaluation launch has fewer threads)
-    for (int w = w_begin + threadIdx.x / LW; w < Wn; w += WPASS) {
+    const int tid = sdp_col_tid();
+    const int rl = tid % LW;                             //  policy-evaluation launch has fewer threads)
+    for (int w = w_begin + tid / LW; w < Wn; w += WPASS) {
         const int tw = w - w_begin;                      // row of the table
         int off[SDP_DT];
         sdp_real lam[SDP_DT], oml[SDP_DT];
@@ -1247,7 +1266,7 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
 #if SDP_COL_FILTER
         (SDP_COL_LEAN_ON ? SDP_META_F_LEAN : 0) | (SDP_COL_SHIFT ? SDP_META_F_SHIFT : 0) |
 #endif
-        ((SDP_COL_FILTER || SDP_TRAIL_HAS_U) ? SDP_META_F_CLAIMS : 0) | SDP_META_F_PEER_STORES,
+        ((SDP_COL_FILTER || SDP_TRAIL_HAS_U) ? SDP_META_F_CLAIMS : 0) | SDP_META_PEER_FLAG,
     SDP_COL_FILTER ? SDP_COL_UTAB : 0, SDP_COL_FILTER ? SDP_COL_UTAB_N : 0, SDP_COL_THREADS, SDP_COL_ROWS,
     0, 0,
 #ifdef SDP_COLRES_TAIL_BYTES
@@ -1261,6 +1280,6 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
 #else   // SDP_D < 2: no column kernels; the unit is a node-order one after all
 extern "C" {
 __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
-    SDP_META_MAGIC, (int32_t)sizeof(sdp_real), SDP_D, SDP_NU, SDP_HAS_W, 0, 0, 1, SDP_META_F_PEER_STORES, 0, 0, 256, 0, 0, 0, 0};
+    SDP_META_MAGIC, (int32_t)sizeof(sdp_real), SDP_D, SDP_NU, SDP_HAS_W, 0, 0, 1, SDP_META_PEER_FLAG, 0, 0, 256, 0, 0, 0, 0};
 }
 #endif  // SDP_D >= 2

@@ -23,11 +23,19 @@ SDP_DEV void sdp_trap_unless(bool ok) { if (!ok) __builtin_trap(); }
 // reads the node (`unit`: its column in the column layout, where a mask says who does; ignored otherwise).
 // Plain stores over xGMI into IPC-mapped buffers: they are complete when the kernel is, and the ranks meet
 // (one tiny all-reduce per backup, sdp_hip.hip:finish_pushes) before anybody reads J or overwrites V.
+// SDP_PEER_STORES: the planner sets it to 0 for a unit that no direct exchange launches (one GPU, the other
+// exchanges): the peer stores are then not compiled at all -- the 8 peer pointers and the mask held in scalar
+// registers across a kernel's loop cost it spills -- and the code object does not claim SDP_META_F_PEER_STORES
+// (sdp_problem_set_direct_exchange refuses it).
+#ifndef SDP_PEER_STORES
+#define SDP_PEER_STORES 1
+#endif
+#define SDP_META_PEER_FLAG (SDP_PEER_STORES ? SDP_META_F_PEER_STORES : 0)
 template <typename real>
 SDP_DEV void sdp_store_J(const SdpSweepArgs &a, int64_t node, int64_t unit, real v)
 {
     ((real *)a.J)[node] = v;
-    if (a.n_peer) {
+    if (SDP_PEER_STORES && a.n_peer) {
         const unsigned m = a.peer_mask ? (unsigned)a.peer_mask[unit] : 0xffu;
 #pragma unroll
         for (int q = 0; q < SDP_MAX_PEERS; ++q)

@@ -300,15 +300,15 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
 #endif
 #if defined(SDP_LINE)
     // (one state variable, the filter on the shifted lattice: sdp_lead_reduce fills aux_a with 2 S + 64 (A', B') pairs at most)
-    SDP_META_F_LEAD | SDP_META_F_FILTER | SDP_META_F_SHIFT | SDP_META_F_PEER_STORES, 0, 0, 256, 0, 1, 0,
+    SDP_META_F_LEAD | SDP_META_F_FILTER | SDP_META_F_SHIFT | SDP_META_PEER_FLAG, 0, 0, 256, 0, 1, 0,
 #elif defined(SDP_STG_THREADS)
-    SDP_META_F_STAGED | SDP_META_F_PEER_STORES, 0, 0, SDP_STG_THREADS, 0, 0, 0,
+    SDP_META_F_STAGED | SDP_META_PEER_FLAG, 0, 0, SDP_STG_THREADS, 0, 0, 0,
 #elif defined(SDP_LEAD_AXES)
-    SDP_META_F_LEAD | SDP_META_F_FILTER | SDP_META_F_PEER_STORES, 0, 0, 256, 0, SDP_LEAD_AXES,
+    SDP_META_F_LEAD | SDP_META_F_FILTER | SDP_META_PEER_FLAG, 0, 0, 256, 0, SDP_LEAD_AXES,
     // (state variable of logical axis j in nibble j: the host sizes the plane-major arrays with it)
     SDP_LP[0] | (SDP_LP[1] << 4) | (SDP_LP[2] << 8) | (SDP_LP[3] << 12),
 #else
-    SDP_META_F_PEER_STORES, 0, 0, 256, 0, 0, 0,
+    SDP_META_PEER_FLAG, 0, 0, 256, 0, 0, 0,
 #endif
     0};
 }

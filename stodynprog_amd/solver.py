@@ -703,6 +703,12 @@ class DPSolver(object):
         self._cache[memo] = plan
         return plan
 
+    def _plans_direct_exchange(self):
+        """whether _problem may turn the direct exchange on (the kernels then store J into the other ranks): only
+        such a unit carries the peer stores"""
+        return bool(self.comm is not None and self.comm.is_device and 1 < self.comm.nranks <= 8
+                    and self.comm_exchange == 'direct')
+
     def _kernel_plan_now(self, box_t, model, bp, lanes, debug, W):
         shape = self._shape()
         dt = self.dtype
@@ -844,7 +850,7 @@ class DPSolver(object):
                                           window=window, per_control=per_control_cfg if per_control else None,
                                           filtered=filtered, utab=utab, lead_axes=lead_axes,
                                           col_cfg=col_cfg, debug=debug, wres=wres if filtered else 0,
-                                          lead_perm=lead_perm, line=line)
+                                          lead_perm=lead_perm, line=line, peer_stores=self._plans_direct_exchange())
         filtered = filtered or bool(lead_axes) or bool(line)
         return dict(model=model, source=source, column=column, lanes=lanes, staged=staged, filtered=filtered,
                     lead_axes=lead_axes, lead_perm=lead_perm, line=bool(line),
