@@ -205,8 +205,26 @@ def value_iteration(spec, J_next, rel_dp=False, t_k=None, nodes=None):
     return J_k, pol_k, idx_k, mar_k
 
 
-def eval_policy(spec, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False):
-    """sdp.py:693-775 with the expectation summed sequentially in w order."""
+def eval_policy(spec, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False, nodes=None):
+    """sdp.py:693-775 with the expectation summed sequentially in w order.
+
+    `nodes`: optional flat C-order node ids; then one step (n_iter == 1, no rel_dp) at those nodes only, a 1-D
+    result (the same operations per node as the whole grid: sampled parity on big grids)."""
+    if nodes is not None:
+        assert n_iter == 1 and not rel_dp
+        nodes = np.asarray(nodes, dtype=np.int64)
+        ind = np.unravel_index(nodes, spec.shape)
+        interp = Interp(*spec.state_grid)
+        interp.set_values(np.zeros(spec.shape) if J_zero is None else J_zero)
+        args = tuple(g[i].reshape(-1, 1) for g, i in zip(spec.state_grid, ind))
+        args = args + tuple(pol[ind + (c,)].reshape(-1, 1) for c in range(pol.shape[-1])) + (spec.perturb_grid[0],)
+        x_next = spec.dyn(*args, **spec.params)
+        g = spec.cost(*args, **spec.params)
+        J_k_grid = np.broadcast_to(g + interp(*x_next), (len(nodes), len(spec.perturb_grid[0])))
+        J = np.zeros(len(nodes))
+        for w in range(len(spec.perturb_proba[0])):
+            J = J + J_k_grid[:, w] * spec.perturb_proba[0][w]
+        return J
     dims = spec.shape
     nb_state = len(dims)
     J_pol = np.zeros(dims) if J_zero is None else J_zero
@@ -233,3 +251,47 @@ def eval_policy(spec, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False):
     if rel_dp:
         return J_pol, (J_ref if J_ref_full else J_ref[-1])
     return J_pol
+
+
+def simulate(spec, pol, x0, w, T, t0=0, dtype=np.float64):
+    """The closed loop of the reference's examples (examples/20 Searev storage control/storage_control.py:242-251):
+
+        for k in range(T):
+            u[k] = [interp_on_state(pol[..., c])(*x[k]) for c in range(nb_control)]
+            x[k+1] = dyn(*x[k], *u[k], w[k])
+
+    batched over B trajectories.  The policy lookup is mlinterp_np (the compiled reference's bits in float32 and
+    float64); dyn and cost run on numpy arrays of `dtype`, one element per trajectory (numpy >= 2: Python float
+    constants are weak, so 4-byte arithmetic stays in float32).  A non-stationary model gets the time index t0 + k
+    first, as a scalar of `dtype`.
+
+    pol: state_dims + (nb_control,); x0: (B, nb_state); w: (>= T, B), or None for a deterministic model.
+    Returns x (T+1, B, nb_state), u (T, B, nb_control), g (T, B), all of `dtype`."""
+    dt = np.dtype(dtype).type
+    pol = np.asarray(pol)
+    x0 = np.atleast_2d(np.asarray(x0, dtype=float))
+    B, d = x0.shape
+    nu = pol.shape[-1]
+    assert pol.shape == spec.shape + (nu,) and d == len(spec.shape)
+    smin = [g[0] for g in spec.state_grid]
+    smax = [g[-1] for g in spec.state_grid]
+    values = np.ascontiguousarray(np.moveaxis(pol, -1, 0).reshape(nu, -1), dtype=dt)
+    x = np.zeros((T + 1, B, d), dtype=dt)
+    u = np.zeros((T, B, nu), dtype=dt)
+    g = np.zeros((T, B), dtype=dt)
+    x[0] = x0.astype(dt)
+    for k in range(T):
+        u[k] = mlinterp_np(smin, smax, spec.shape, values, x[k].T).T                # storage_control.py:246
+        args = tuple(x[k, :, i] for i in range(d)) + tuple(u[k, :, c] for c in range(nu))
+        if w is not None:
+            args = args + (np.asarray(w[k], dtype=dt),)
+        if not spec.stationnary:
+            args = (dt(t0 + k),) + args
+        xn = spec.dyn(*args, **spec.params)                                         # storage_control.py:248
+        gk = spec.cost(*args, **spec.params)
+        for v in tuple(xn) + (gk,):         # (a wider result would be rounded twice on the store)
+            assert not isinstance(v, np.ndarray) or v.dtype == dt, (v.dtype, dt)
+        for i in range(d):
+            x[k + 1, :, i] = xn[i]
+        g[k] = gk
+    return x, u, g

@@ -52,9 +52,26 @@ def test_simulation_equals_the_hand_written_host_loop(gpu):
         E[k + 1], S[k + 1], A[k + 1] = wec.dyn(E[k], S[k], A[k], P[k], w[k])
     x, u, _ = solver.simulate(pol, (10 / 3., 0., 0.), w)
     assert np.array_equal(x, np.column_stack([E, S, A])) and np.array_equal(u[:, 0], P)
-    # float32 solver: same loop through the float32 interpolator and numpy float32 arithmetic
-    xb, ub, _ = solver.simulate(pol, np.tile([10 / 3., 0., 0.], (70, 1)), np.tile(w[:, None], (1, 70)))
-    assert all(np.array_equal(xb[:, b], x) for b in range(70))     # more lanes than a wavefront
+    # more lanes than a wavefront, each with its own start and perturbations (lane 0: the loop above), against the
+    # same loop batched in numpy (oracle/vi_numpy.simulate: the reference's interpolator, not the device's)
+    from oracle import vi_numpy
+    x0 = np.column_stack([rng.uniform(0, 10, 70), rng.uniform(-0.5, 0.5, 70), rng.uniform(-0.5, 0.5, 70)])
+    x0[0] = (10 / 3., 0., 0.)
+    wb = rng.normal(0., models.SEAREV['innov_std'], (T, 70))
+    wb[:, 0] = w
+    xb, ub, gb = solver.simulate(pol, x0, wb)
+    assert np.array_equal(xb[:, 0], x) and np.array_equal(ub[:, 0, 0], P)
+    assert len({xb[-1, b, 0] for b in range(70)}) == 70
+    xo, uo, go = vi_numpy.simulate(vi_numpy.Spec.from_solver(solver), pol, x0, wb, T)
+    assert np.array_equal(xb, xo) and np.array_equal(ub, uo) and np.array_equal(gb, go)
+    # float32 solver: the same loop through the float32 interpolator and numpy float32 arithmetic
+    from policies import as_dtype
+    s32 = as_dtype(solver, np.float32)
+    x32, u32, g32 = s32.simulate(pol, x0, wb)
+    assert x32.dtype == u32.dtype == g32.dtype == np.float32
+    xo, uo, go = vi_numpy.simulate(vi_numpy.Spec.from_solver(s32), pol, x0, wb, T, dtype=np.float32)
+    assert np.array_equal(x32, xo) and np.array_equal(u32, uo) and np.array_equal(g32, go)
+    assert not np.array_equal(x32.astype(float), xb)
 
 
 def test_deterministic_time_dependent_system(gpu):
