@@ -182,6 +182,32 @@ int sdp_problem_eval_policy(sdp_problem *p, int32_t n_iter, int rel_dp, int64_t 
                             double *J_ref_out);
 
 /*
+ * Sweep loops that stop at a tolerance (no reference counterpart: its users judge
+ * convergence by eye).  sdp_problem_vi_until runs the loop of sdp_problem_vi_sweep +
+ * sdp_problem_swap (J_ref_out[k]: reference cost of sweep k), sdp_problem_eval_policy_until
+ * that of sdp_problem_eval_policy (fused relative shift included), at most n_max sweeps,
+ * queued back to back.  After sweeps check_every, 2 check_every, ... and after sweep n_max
+ * the library reduces the last two cost-to-go arrays a = J^(k), b = J^(k-1) (with rel_dp
+ * both shifted, J - J[ref], as the host loop returns them; J^(0) is the starting value):
+ *     d = 0 where a == b, else a - b rounded in the problem's real type
+ *     stats[2 i] = min d, stats[2 i + 1] = max d     (check i, widened to double; both NaN
+ *                                                     if any d is NaN)
+ * and stops after the first check with  max d - min d <= tol  (never on NaN).  *n_done:
+ * sweeps run; J, policy and J_ref_out[0 .. n_done) are those of a plain call with
+ * n_iter = *n_done.  stats: room for ceil(n_max / check_every) checks; J_ref_out: n_max
+ * doubles (may be NULL).  tol >= 0, check_every >= 1, else SDP_EINVAL.  With a
+ * communicator attached every rank reduces the nodes it computes and the per-rank
+ * statistics are all-gathered: every rank holds the same bits and stops at the same sweep
+ * (collective: every rank must call it).  A check reads back 24 bytes per rank once.
+ */
+int sdp_problem_vi_until(sdp_problem *p, int32_t n_max, int rel_dp, int64_t ref_index,
+                         int32_t check_every, double tol, int32_t *n_done,
+                         double *stats /* [n_checks][2] */, double *J_ref_out /* [n_max] */);
+int sdp_problem_eval_policy_until(sdp_problem *p, int32_t n_max, int rel_dp, int64_t ref_index,
+                                  int32_t check_every, double tol, int32_t *n_done,
+                                  double *stats /* [n_checks][2] */, double *J_ref_out /* [n_max] */);
+
+/*
  * The whole of one DPSolver.value_iteration call with host arrays in and out
  * (stodynprog.py:466-534; the reference takes J_next and returns fresh J_k, pol_k
  * every call): upload of host_V (NULL: keep the device's value buffer), backup,

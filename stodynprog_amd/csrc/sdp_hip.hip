@@ -433,6 +433,125 @@ __global__ void __launch_bounds__(256) k_shift(real *__restrict__ J, int64_t n,
 }
 
 // ---------------------------------------------------------------------------
+// built-in kernel: convergence statistics of two consecutive cost-to-go arrays
+// (stodynprog_amd/convergence.py: diff_stats is the definition).  Per node
+//     a = J[i] (- J[ra]),  b = V[i] (- V[rb])     (ra / rb < 0: no shift; else each rounded once in `real`)
+//     d = 0 where a == b, else a - b rounded in `real`
+// and dmin / dmax of d over a list of node ranges, NaN flagged apart.  Min and max do not depend on the
+// order, so any grid, split or rank count gives the same bits.  Accumulated as order-preserving 64-bit
+// keys of the doubles: acc[0] = max of ~key(dmin), acc[1] = max of key(dmax), acc[2] = NaN seen; all three
+// start at 0 (one stream-ordered memset), and 0 is the identity of every one of them.
+// ---------------------------------------------------------------------------
+#define SDP_STAT_RANGES 8
+struct SdpStatRanges {
+    int64_t b[SDP_STAT_RANGES], e[SDP_STAT_RANGES];
+    int n;
+};
+
+__device__ __host__ inline unsigned long long sdp_order_key(double x)
+{
+    unsigned long long u;
+    memcpy(&u, &x, 8);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+static double sdp_key_value(unsigned long long k)
+{
+    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double x;
+    memcpy(&x, &u, 8);
+    return x;
+}
+
+// (branch-free: d is NaN exactly where a or b is, and a NaN d leaves mn / mx as they are)
+template <typename real>
+__device__ inline void stat_node(real a, real b, real &mn, real &mx, int &nan)
+{
+    const real d = a == b ? real(0) : a - b;
+    nan |= d != d;
+    mn = d < mn ? d : mn;
+    mx = d > mx ? d : mx;
+}
+
+template <typename real>
+__global__ void __launch_bounds__(256) k_diff_stats(const real *__restrict__ J, const real *__restrict__ V,
+                                                    int64_t ra, int64_t rb, SdpStatRanges r,
+                                                    unsigned long long *__restrict__ acc)
+{
+    constexpr int VEC = 16 / sizeof(real);                 // 16-byte loads: 2 doubles or 4 floats
+    struct alignas(16) Pack { real v[VEC]; };
+    const real ja = ra >= 0 ? J[ra] : real(0), vb = rb >= 0 ? V[rb] : real(0);
+    real mn = real(INFINITY), mx = real(-INFINITY);
+    int nan = 0;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    for (int k = 0; k < r.n; ++k) {
+        const int64_t b = r.b[k], e = r.e[k];
+        int64_t vb0 = (b + VEC - 1) / VEC * VEC;           // J and V share their alignment (same element index)
+        if (vb0 > e) vb0 = e;
+        const int64_t ve = vb0 + (e - vb0) / VEC * VEC;
+        for (int64_t i = b + tid; i < vb0; i += nth) {      // head and tail: fewer than VEC nodes each
+            const real a = ra >= 0 ? J[i] - ja : J[i], c = rb >= 0 ? V[i] - vb : V[i];
+            stat_node(a, c, mn, mx, nan);
+        }
+        for (int64_t i = ve + tid; i < e; i += nth) {
+            const real a = ra >= 0 ? J[i] - ja : J[i], c = rb >= 0 ? V[i] - vb : V[i];
+            stat_node(a, c, mn, mx, nan);
+        }
+        // four 16-byte loads of each array in flight per lane, then the arithmetic
+        constexpr int UNROLL = 4;
+        const int64_t step = nth * VEC;
+        int64_t i = vb0 + tid * VEC;
+        for (; i + (UNROLL - 1) * step < ve; i += UNROLL * step) {
+            Pack pa[UNROLL], pc[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                pa[u] = *(const Pack *)(J + i + u * step);
+                pc[u] = *(const Pack *)(V + i + u * step);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    const real a = ra >= 0 ? pa[u].v[j] - ja : pa[u].v[j];
+                    const real c = rb >= 0 ? pc[u].v[j] - vb : pc[u].v[j];
+                    stat_node(a, c, mn, mx, nan);
+                }
+        }
+        for (; i < ve; i += step) {
+            const Pack pa = *(const Pack *)(J + i), pc = *(const Pack *)(V + i);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                const real a = ra >= 0 ? pa.v[j] - ja : pa.v[j], c = rb >= 0 ? pc.v[j] - vb : pc.v[j];
+                stat_node(a, c, mn, mx, nan);
+            }
+        }
+    }
+    // wavefront, then block (four wavefronts through LDS), then one atomic per word and block
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        const real omn = __shfl_xor(mn, off), omx = __shfl_xor(mx, off);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        nan |= __shfl_xor(nan, off);
+    }
+    __shared__ real s_mn[4], s_mx[4];
+    __shared__ int s_nan[4];
+    const int wave = threadIdx.x / warpSize;
+    if (threadIdx.x % warpSize == 0) { s_mn[wave] = mn; s_mx[wave] = mx; s_nan[wave] = nan; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int waves = (blockDim.x + warpSize - 1) / warpSize;
+        for (int w = 1; w < waves; ++w) {
+            mn = s_mn[w] < mn ? s_mn[w] : mn;
+            mx = s_mx[w] > mx ? s_mx[w] : mx;
+            nan |= s_nan[w];
+        }
+        atomicMax(acc + 0, ~sdp_order_key((double)mn));
+        atomicMax(acc + 1, sdp_order_key((double)mx));
+        if (nan) atomicMax(acc + 2, 1ull);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // built-in kernels: tabulated backup (stodynprog.py:677-690)
 //   k_tab_cells : one lane per lattice cell, coalesced x_next / g reads,
 //                 jc = g + interp(V, x_next)
@@ -794,6 +913,8 @@ struct sdp_problem {
     int32_t orders[SDP_MAXD] = {0, 0, 0, 0};
     int32_t axis_off[SDP_MAXD] = {0, 0, 0, 0};
     DevBuf axes, wgrid, proba, box_lo, box_hi, box_n, V, J, pol, idx, pol_in, refs, scratch, stamps, claim, tail;
+    DevBuf stats, stats_all;               // convergence check: this rank's 3 key words, every rank's (diff_stats)
+    hipEvent_t ev_stats = nullptr;         // .. the statistics are ready for the all-gather
     DevBuf gstage;                         // gather buffer of phases with uneven parts (gather_phase_of)
     size_t gstage_bytes = 0;
     DevBuf stage[3];                       // layout-conversion buffers of the fused host call (J, pol, idx)
@@ -890,6 +1011,7 @@ struct sdp_problem {
         if (ev2) (void)hipEventDestroy(ev2);
         if (ev3) (void)hipEventDestroy(ev3);
         if (ev_comm) (void)hipEventDestroy(ev_comm);
+        if (ev_stats) (void)hipEventDestroy(ev_stats);
         release_peers();
         if (ev_copy) (void)hipEventDestroy(ev_copy);
         for (auto &e : ev_host) if (e) (void)hipEventDestroy(e);
@@ -1831,6 +1953,140 @@ extern "C" int sdp_problem_eval_policy(sdp_problem *p, int32_t n_iter, int rel_d
     p->last_kernel_ms = ms;
     if (rel_dp && J_ref_out) HIP_TRY(hipMemcpy(J_ref_out, p->refs.p, (size_t)n_iter * 8, hipMemcpyDeviceToHost));
     return SDP_OK;
+}
+
+// dmin / dmax of J (the last backup) against V (the one before) over the nodes this rank computes -- the ranges of
+// its parts, or [node_begin, node_end) -- with J / V shifted by their node ra / rb (device order, < 0: not shifted;
+// k_diff_stats).  Several ranks: every rank's 3 key words are all-gathered and combined the same way on every rank,
+// so all of them hold the same bits and take the same decision.  Reads back a few bytes: one synchronisation.
+static int diff_stats(sdp_problem *p, int64_t ra, int64_t rb, double &dmin, double &dmax)
+{
+    const int n = p->comm ? p->comm->nranks : 1, me = p->comm ? p->comm->rank : 0;
+    int rc;
+    if (!p->stats.p && (rc = p->stats.alloc(3 * 8))) return rc;
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    if (!p->comm) {
+        ranges.emplace_back(p->node_begin, p->node_end);
+    } else {
+        for (int ph = 0; ph < p->n_phases; ++ph) {
+            const int64_t *b = p->parts.data() + (size_t)ph * (n + 1);
+            if (b[me + 1] > b[me]) ranges.emplace_back(b[me], b[me + 1]);
+        }
+    }
+    HIP_TRY(hipMemsetAsync(p->stats.p, 0, 3 * 8, p->stream));
+    const int vec = p->dtype == SDP_F32 ? 4 : 2;
+    for (size_t k0 = 0; k0 < ranges.size() || k0 == 0; k0 += SDP_STAT_RANGES) {
+        SdpStatRanges r;
+        r.n = 0;
+        int64_t nodes = 0;
+        for (size_t k = k0; k < ranges.size() && r.n < SDP_STAT_RANGES; ++k, ++r.n) {
+            r.b[r.n] = ranges[k].first;
+            r.e[r.n] = ranges[k].second;
+            nodes += ranges[k].second - ranges[k].first;
+        }
+        // (four workgroups per CU: 64 us at 256^3 fp64 against 110 us with sixteen, which also meet 4 x as many atomics
+        // on the three words)
+        int64_t blocks = (nodes / vec + 255) / 256;
+        if (blocks > (int64_t)p->cus * 4) blocks = (int64_t)p->cus * 4;
+        if (blocks < 1) blocks = 1;
+        unsigned long long *acc = (unsigned long long *)p->stats.p;
+        if (p->dtype == SDP_F32)
+            hipLaunchKernelGGL(k_diff_stats<float>, dim3((unsigned)blocks), dim3(256), 0, p->stream,
+                               (const float *)p->J.p, (const float *)p->V.p, ra, rb, r, acc);
+        else
+            hipLaunchKernelGGL(k_diff_stats<double>, dim3((unsigned)blocks), dim3(256), 0, p->stream,
+                               (const double *)p->J.p, (const double *)p->V.p, ra, rb, r, acc);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<unsigned long long> keys((size_t)n * 3, 0ull);
+    if (n > 1) {
+        if (!p->stats_all.p && (rc = p->stats_all.alloc((size_t)n * 3 * 8))) return rc;
+        if (!p->ev_stats) HIP_TRY(hipEventCreateWithFlags(&p->ev_stats, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(p->ev_stats, p->stream));
+        HIP_TRY(hipStreamWaitEvent(p->comm->stream, p->ev_stats, 0));
+        NCCL_TRY(g_rccl.AllGather(p->stats.p, p->stats_all.p, 3, NCCL_FLOAT64, p->comm->comm, p->comm->stream));
+        HIP_TRY(hipMemcpyAsync(keys.data(), p->stats_all.p, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, p->comm->stream));
+        HIP_TRY(hipStreamSynchronize(p->comm->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(keys.data(), p->stats.p, 3 * 8, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    unsigned long long kmin = 0, kmax = 0, knan = 0;
+    for (int q = 0; q < n; ++q) {
+        kmin = std::max(kmin, keys[(size_t)q * 3]);
+        kmax = std::max(kmax, keys[(size_t)q * 3 + 1]);
+        knan |= keys[(size_t)q * 3 + 2];
+    }
+    dmin = knan ? NAN : sdp_key_value(~kmin);
+    dmax = knan ? NAN : sdp_key_value(kmax);
+    return SDP_OK;
+}
+
+// The loops of sdp_problem_vi_sweep + sdp_problem_swap and of sdp_problem_eval_policy, queued back to back, with the
+// convergence check after sweeps c, 2c, ... and after the last allowed one.
+static int iterate_until(sdp_problem *p, bool evalpol, int32_t n_max, int rel_dp, int64_t ref_index,
+                         int32_t check_every, double tol, int32_t *n_done, double *stats, double *J_ref_out)
+{
+    if (!p || !n_done || !stats) return fail(SDP_EINVAL, "NULL argument");
+    if (n_max < 1) return fail(SDP_EINVAL, "n_max must be at least 1");
+    if (check_every < 1) return fail(SDP_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0)) return fail(SDP_EINVAL, "tol must be a number >= 0");
+    if (evalpol && !p->pol_in.p) return fail(SDP_EINVAL, "no policy set (sdp_problem_set_policy)");
+    int rc;
+    if ((rc = check_ref(p, rel_dp, ref_index))) return rc;
+    if ((rc = ensure_refs(p, n_max))) return rc;
+    p->peer_fence = true;                // first backup of a call (open_pushes)
+    double *refs = (double *)p->refs.p;
+    int32_t done = 0, checks = 0;
+    HIP_TRY(hipEventRecord(p->ev0, p->stream));
+    for (int32_t k = 0; k < n_max; ++k) {
+        if (k > 0) swap_buffers(p);
+        if (evalpol) {
+            // the fused relative shift of sdp_problem_eval_policy: step k > 0 reads V - V[ref], J holds raw values
+            const bool fused = rel_dp && k > 0;
+            if ((rc = run_backup(p, true, 0.0, fused ? ref_index : -1, fused ? refs + (k - 1) : nullptr))) return rc;
+            if ((rc = join_comm(p))) return rc;
+        } else {
+            p->peer_fence = true;        // every sweep is one sdp_problem_vi_sweep call of the host loop
+            if ((rc = run_backup(p, false, 0.0))) return rc;
+            if ((rc = join_comm(p))) return rc;
+            if (rel_dp && (rc = rel_shift(p, ref_index, k))) return rc;
+        }
+        done = k + 1;
+        if (done % check_every == 0 || done == n_max) {
+            // the statistics are those of the shifted sequence: the evaluation shifts both buffers here
+            const int64_t ra = evalpol && rel_dp ? ref_index : -1, rb = evalpol && rel_dp && k > 0 ? ref_index : -1;
+            double dmin, dmax;
+            if ((rc = diff_stats(p, ra, rb, dmin, dmax))) return rc;
+            stats[2 * checks] = dmin;
+            stats[2 * checks + 1] = dmax;
+            ++checks;
+            if (dmax - dmin <= tol) break;                  // NaN never converges
+        }
+    }
+    if (evalpol && rel_dp && (rc = rel_shift(p, ref_index, done - 1))) return rc;
+    HIP_TRY(hipEventRecord(p->ev1, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+    p->last_kernel_ms = ms;
+    *n_done = done;
+    if (rel_dp && J_ref_out) HIP_TRY(hipMemcpy(J_ref_out, p->refs.p, (size_t)done * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_problem_vi_until(sdp_problem *p, int32_t n_max, int rel_dp, int64_t ref_index,
+                                    int32_t check_every, double tol, int32_t *n_done, double *stats,
+                                    double *J_ref_out)
+{
+    return iterate_until(p, false, n_max, rel_dp, ref_index, check_every, tol, n_done, stats, J_ref_out);
+}
+
+extern "C" int sdp_problem_eval_policy_until(sdp_problem *p, int32_t n_max, int rel_dp, int64_t ref_index,
+                                             int32_t check_every, double tol, int32_t *n_done, double *stats,
+                                             double *J_ref_out)
+{
+    return iterate_until(p, true, n_max, rel_dp, ref_index, check_every, tol, n_done, stats, J_ref_out);
 }
 
 // ---------------------------------------------------------------------------

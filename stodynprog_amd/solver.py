@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _native as nat
 from . import codegen
+from . import convergence as conv
 from .interp import MlinInterpolator
 from .trace import TraceError, trace_model, trace_box, callable_fingerprint, _fp_value, _NoFingerprint
 
@@ -160,6 +161,21 @@ class _DeviceProblem(object):
                                                     int(ref_index), nat.ptr(refs)))
         return refs[:int(n_iter)]
 
+    def until(self, evalpol, n_max, rel_dp, ref_index, check_every, tol):
+        """the loop of `sweep` + `swap` (evalpol False) or of `eval_policy` (True) with the convergence check inside
+        the library (sdp_problem_vi_until / sdp_problem_eval_policy_until).  Returns (sweeps done, checked sweeps,
+        [n_checks][2] dmin / dmax, reference costs of the sweeps done)"""
+        schedule = conv.check_schedule(int(n_max), int(check_every))
+        stats = np.zeros((len(schedule), 2))
+        refs = np.zeros(int(n_max))
+        n_done = C.c_int32(0)
+        fn = nat.lib().sdp_problem_eval_policy_until if evalpol else nat.lib().sdp_problem_vi_until
+        nat.check(fn(self.h, int(n_max), int(bool(rel_dp)), int(ref_index), int(check_every), float(tol),
+                     C.byref(n_done), nat.ptr(stats), nat.ptr(refs)))
+        n = n_done.value
+        checked = [k for k in schedule if k <= n]
+        return n, checked, stats[:len(checked)], refs[:n]
+
     def backup_host(self, V, t_k=0.0, rel_dp=False, ref_index=0, overlap=True):
         """value_iteration's device work with host arrays in and out in ONE library call
         (sdp_problem_backup_host): upload, sweep, relative-DP shift, download of J and of
@@ -286,6 +302,9 @@ class DPSolver(object):
         self._idx_cache = None             # see last_policy_index
         self._idx_source = None
         self.backend_info = {}
+        # what the last value_iterations / eval_policy / policy_iteration call made with `tol` did
+        # (convergence.SweepConvergence / PolicyIterationConvergence); None after a call without `tol`
+        self.last_convergence = None
 
     @property
     def last_policy_index(self):
@@ -1204,7 +1223,8 @@ class DPSolver(object):
             J_k = J_k, J_ref
         return J_k, pol_k
 
-    def value_iterations(self, J_next, n_iter, rel_dp=False, report_time=True, J_ref_full=False):
+    def value_iterations(self, J_next, n_iter, rel_dp=False, report_time=True, J_ref_full=False, tol=None,
+                         check_every=1):
         """`n_iter` successive calls of `value_iteration`, each fed with the
         result of the previous one -- the loop every user of the reference
         writes by hand (doc/example_inventory.py:98-109, AR1 notebook) -- but
@@ -1214,9 +1234,18 @@ class DPSolver(object):
             for k in range(n_iter): J, pol = self.value_iteration(J, rel_dp)
 
         Returns (J_k, pol_k) of the last sweep; J_k is (J_diff, J_ref) with
-        `rel_dp` (J_ref: last reference cost, or all of them if J_ref_full)."""
+        `rel_dp` (J_ref: last reference cost, or all of them if J_ref_full).
+
+        tol: stop at the first checked sweep whose span max(d) - min(d) of
+        d = J_k - J_{k-1} is <= tol (stodynprog_amd.convergence); `n_iter` is then
+        the maximum number of sweeps, checked are sweeps check_every, 2 check_every,
+        ... and the last allowed one.  The result equals the call with n_iter = the
+        sweeps run; self.last_convergence tells what the checks found."""
         t_start = datetime.now()
         assert n_iter >= 1
+        if tol is not None:
+            tol, check_every = conv.validate(tol, check_every)
+        self.last_convergence = None
         if rel_dp:
             J_next, J_ref = J_next
             assert J_next[self._state_ref_ind] == 0.
@@ -1225,27 +1254,59 @@ class DPSolver(object):
         host_comm = self.comm is not None and not self.comm.is_device
         refs = np.zeros(n_iter)
         model = self._trace_now(None)
+        checks = []
         if isinstance(model, TraceError) or host_comm:
             J_k = J_next                    # host callbacks / host exchange: sweep by sweep
             for k in range(n_iter):
+                J_prev = J_k
                 J_k, pol_k, r = self._backup(J_k, None, rel_dp)
                 refs[k] = 0.0 if r is None else r
+                if tol is not None and self._host_check(checks, k + 1, n_iter, check_every, tol, J_k, J_prev):
+                    break
+            n_done = k + 1
         else:
             prob = self._problem(None, model)
             prob.set_value(J_next)
             ref_flat = self._ref_flat(prob) if rel_dp else 0
-            for k in range(n_iter):
-                if k:
-                    prob.swap()             # J of the previous sweep becomes J_next
-                refs[k] = prob.sweep(0.0, rel_dp, ref_flat)
+            if tol is None:
+                for k in range(n_iter):
+                    if k:
+                        prob.swap()             # J of the previous sweep becomes J_next
+                    refs[k] = prob.sweep(0.0, rel_dp, ref_flat)
+                n_done = n_iter
+            else:
+                n_done, checked, stats, r = prob.until(False, n_iter, rel_dp, ref_flat, check_every, tol)
+                refs[:n_done] = r
+                checks = [(k, a, b) for k, (a, b) in zip(checked, stats)]
             J_k = prob.get_value()
             pol_k, self.last_policy_index = prob.get_policy()
+        refs = refs[:n_done]
+        if tol is not None:
+            self.last_convergence = self._sweep_record(tol, check_every, n_done, checks, refs, rel_dp)
         if report_time:
             exec_time = (datetime.now() - t_start).total_seconds()
-            print('{:d} value iterations run in {:.2f} s'.format(n_iter, exec_time))
+            print('{:d} value iterations run in {:.2f} s'.format(n_done, exec_time))
         if rel_dp:
             return (J_k, refs if J_ref_full else refs[-1]), pol_k
         return J_k, pol_k
+
+    @staticmethod
+    def _host_check(checks, k, n_iter, check_every, tol, J_k, J_prev):
+        """the convergence check of the loops that hold full host arrays every sweep: after sweep k (1-based) when it
+        is a checked one, appends (k, dmin, dmax) to `checks`; True when the loop stops here"""
+        if not conv.is_check(k, n_iter, check_every):
+            return False
+        J_k = np.asarray(J_k)
+        dmin, dmax = conv.diff_stats(J_k, J_prev, J_k.dtype)
+        checks.append((k, dmin, dmax))
+        return conv.converged(dmin, dmax, tol)
+
+    @staticmethod
+    def _sweep_record(tol, check_every, n_done, checks, refs, rel_dp):
+        checked = [c[0] for c in checks]
+        return conv.SweepConvergence(tol, check_every, n_done, checked, [c[1] for c in checks],
+                                     [c[2] for c in checks],
+                                     [refs[k - 1] for k in checked] if rel_dp else None)
 
     def _backup(self, J_next, t_k, rel_dp):
         """One sweep: fused kernel when the model is traceable, else tabulated."""
@@ -1443,7 +1504,7 @@ class DPSolver(object):
 
     # ------------------------------------------------------------ policy evaluation
     def eval_policy(self, pol, n_iter, rel_dp=False, J_zero=None,
-                    report_time=True, J_ref_full=False):
+                    report_time=True, J_ref_full=False, tol=None, check_every=1):
         """evaluate the policy `pol`: cost of each state after `n_iter` steps
         (reference sdp.py:693-775).  If rel_dp is True the relative DP
         algorithm is used.
@@ -1451,8 +1512,16 @@ class DPSolver(object):
         Returns J_pol (array of shape self._state_grid_shape), or
         (J_pol, J_ref) if `rel_dp` is True (J_ref: the last reference cost,
         or all of them when J_ref_full).
+
+        tol, check_every: stop early, as in `value_iterations` (n_iter is then the
+        maximum; J_ref_full gives the references of the iterations run).
         """
         t_start = datetime.now()
+        if tol is not None:
+            tol, check_every = conv.validate(tol, check_every)
+            if n_iter < 1:
+                raise ValueError('eval_policy with tol needs n_iter >= 1, not {!r}'.format(n_iter))
+        self.last_convergence = None
         state_dims = self._state_grid_shape
         if J_zero is None:
             J_zero = np.zeros(state_dims)
@@ -1463,13 +1532,14 @@ class DPSolver(object):
         model = self._trace_now(t_pol)
         if isinstance(model, TraceError):
             return self._eval_policy_tabulated(pol, n_iter, rel_dp, J_zero, report_time,
-                                               J_ref_full, t_start)
+                                               J_ref_full, t_start, tol, check_every)
         prob = self._problem(t_pol, model)
         prob.set_value(J_zero)
         prob.set_policy(pol)
         for k in range(n_iter):
             # progress line of the reference; the iterations themselves run in one device call
             print('\rpolicy evaluation: iter. {:d}/{:d}'.format(k, n_iter), end='')
+        checks = []
         if self.comm is not None and not self.comm.is_device:
             # host-side (gloo) communicator: one device call per iteration, the
             # slabs meet in host memory in between (test path; RCCL stays on device)
@@ -1481,13 +1551,24 @@ class DPSolver(object):
                 prob.eval_policy(1, False, 0)
                 Jd = prob._to_device_order(prob.get_value()).reshape(-1)
                 self.comm.all_gather_slabs(Jd, bounds)
-                J_pol = prob._from_device_order(Jd)
+                J_prev, J_pol = J_pol, prob._from_device_order(Jd)
                 if rel_dp:
                     J_ref[k] = J_pol[self._state_ref_ind]          # sdp.py:757-760
                     J_pol -= J_pol[self._state_ref_ind]
-        else:
+                if tol is not None and self._host_check(checks, k + 1, n_iter, check_every, tol, J_pol, J_prev):
+                    break
+            if tol is not None:
+                J_ref = J_ref[:k + 1]
+        elif tol is None:
             J_ref = prob.eval_policy(n_iter, rel_dp, self._ref_flat(prob) if rel_dp else 0)
             J_pol = prob.get_value()
+        else:
+            n_done, checked, stats, J_ref = prob.until(True, n_iter, rel_dp, self._ref_flat(prob) if rel_dp else 0,
+                                                       check_every, tol)
+            checks = [(k, a, b) for k, (a, b) in zip(checked, stats)]
+            J_pol = prob.get_value()
+        if tol is not None:
+            self.last_convergence = self._sweep_record(tol, check_every, len(J_ref), checks, J_ref, rel_dp)
         exec_time = (datetime.now() - t_start).total_seconds()
         if report_time:
             print('\rpolicy evaluation run in {:.2f} s     '.format(exec_time))
@@ -1498,7 +1579,7 @@ class DPSolver(object):
         return J_pol
 
     def _eval_policy_tabulated(self, pol, n_iter, rel_dp, J_zero, report_time, J_ref_full,
-                               t_start):
+                               t_start, tol=None, check_every=1):
         """eval_policy for callables that cannot be traced: dyn and cost are
         evaluated on the host over the whole (S x W) lattice exactly as the
         reference does (sdp.py:732-754, once: they do not change between
@@ -1533,7 +1614,9 @@ class DPSolver(object):
         J_pol = np.ascontiguousarray(J_zero, dtype=float)
         J_ref = np.zeros(n_iter)
         idx = np.zeros(S, dtype=np.int64)
+        checks = []
         for k in range(n_iter):
+            J_prev = J_pol
             print('\rpolicy evaluation: iter. {:d}/{:d}'.format(k, n_iter), end='')
             h = C.c_void_p()
             nat.check(nat.lib().sdp_tab_create(d, nat.ptr(smin), nat.ptr(smax), nat.ptr(orders),
@@ -1549,6 +1632,12 @@ class DPSolver(object):
             if rel_dp:
                 J_ref[k] = J_pol[self._state_ref_ind]               # sdp.py:760-762
                 J_pol -= J_ref[k]
+            if tol is not None and self._host_check(checks, k + 1, n_iter, check_every, tol, J_pol, J_prev):
+                break
+        if tol is not None:
+            J_ref = J_ref[:k + 1]
+        if tol is not None:
+            self.last_convergence = self._sweep_record(tol, check_every, len(J_ref), checks, J_ref, rel_dp)
         exec_time = (datetime.now() - t_start).total_seconds()
         if report_time:
             print('\rpolicy evaluation run in {:.2f} s     '.format(exec_time))
@@ -1556,27 +1645,45 @@ class DPSolver(object):
             return J_pol, (J_ref if J_ref_full else J_ref[-1])
         return J_pol
 
-    def policy_iteration(self, pol_init, n_val, n_pol=1, rel_dp=False):
+    def policy_iteration(self, pol_init, n_val, n_pol=1, rel_dp=False, tol=None, check_every=1):
         """policy iteration algorithm (reference sdp.py:777-812).
 
         pol_init : initial policy to evaluate
         n_val : number of value iterations to evaluate the policy
         n_pol : number of policy iterations (default to 1)
+        tol, check_every : (not in the reference) every evaluation stops at `tol` as in
+              `eval_policy` (n_val is its maximum), and the loop ends early when an
+              improvement step returns exactly the policy it was given;
+              self.last_convergence then holds one record per evaluation
 
         Returns (J_pol, pol); J_pol is a tuple (J_diff, J_ref) if rel_dp.
         """
+        if tol is not None:
+            tol, check_every = conv.validate(tol, check_every)
+        ev = dict(tol=tol, check_every=check_every) if tol is not None else {}
+        evaluations = []
         pol = pol_init
-        J_pol = self.eval_policy(pol, n_val, rel_dp)
+        J_pol = self.eval_policy(pol, n_val, rel_dp, **ev)
+        evaluations.append(self.last_convergence)
         if rel_dp:
             J_diff, J_ref = J_pol
             print('ref policy cost: {:g}'.format(J_ref))
+        stable, n_improvements = False, 0
         for k in range(n_pol):
             print('policy iteration {:d}/{:d}'.format(k + 1, n_pol))
-            _, pol = self.value_iteration(J_pol, rel_dp=rel_dp)
-            J_pol = self.eval_policy(pol, n_val, rel_dp)
+            _, pol_new = self.value_iteration(J_pol, rel_dp=rel_dp)
+            n_improvements += 1
+            if tol is not None and np.array_equal(pol_new, pol):
+                stable, pol = True, pol_new     # J_pol is already the evaluation of this policy
+                break
+            pol = pol_new
+            J_pol = self.eval_policy(pol, n_val, rel_dp, **ev)
+            evaluations.append(self.last_convergence)
             if rel_dp:
                 J_ref = J_pol[1]
                 print('ref policy cost: {:g}'.format(J_ref))
+        self.last_convergence = (conv.PolicyIterationConvergence(evaluations, n_improvements, stable)
+                                 if tol is not None else None)
         return J_pol, pol
 
     # ------------------------------------------------------------ closed-loop simulation
