@@ -557,14 +557,18 @@ class DPSolver(object):
         # (round 6: a callable whose FINGERPRINT -- code, defaults, closure cells and the globals it names, by value -- is
         # what it was at the last call traces to the same graph: the trace is kept.  No fingerprint (an object, a large
         # array, a module of the user's in sight): traced afresh, as before.  trace.callable_fingerprint)
+        # A time-dependent system traced with a SYMBOLIC time index gives the same graph at every step: one kept trace
+        # serves the whole horizon.  A trace for one concrete step (t_value) is not kept, nor is the failure of one: the
+        # next step may trace where this one did not.
         fp = callable_fingerprint(s.dyn, s.cost, s.params) if self.trace_cache else None
+        key = ('trace now', s.stationnary)
         if fp is not None:
-            kept = self._cache.get(('trace now', s.stationnary, None if s.stationnary else t_k))
+            kept = self._cache.get(key)
             if kept is not None and kept[0] == fp:
                 return kept[1]
         model = self._trace_now_uncached(t_k)
-        if fp is not None and (s.stationnary or getattr(model, 't_value', None) is None):
-            self._cache[('trace now', s.stationnary, None if s.stationnary else t_k)] = (fp, model)
+        if fp is not None and (s.stationnary or (not isinstance(model, TraceError) and model.t_value is None)):
+            self._cache[key] = (fp, model)
         return model
 
     def _trace_now_uncached(self, t_k=None):
