@@ -18,12 +18,16 @@ import numpy as np
 _I32_MIN = -2 ** 31
 
 
-def mlinterp_np(smin, smax, orders, values, s):
+def mlinterp_np(smin, smax, orders, values, s, wide=True):
     """pyx:17-49 dispatcher + pyx:51-300 point kernels, vectorised over points.
 
     Each numpy operator below is one IEEE operation per element, in the order
     of the Cython source, so results are bit-identical to the compiled
     reference for float32 and float64.
+
+    wide=False: the lerp tree in the type of `values` from top to bottom -- what the sweep
+    kernels evaluate (csrc/sdp_device.h: sdp_interp_point<real, D, wide = real>); the cell and
+    lam are the same lines.  For float64 values the two forms are the same operations.
     """
     values = np.ascontiguousarray(values)
     dt = values.dtype.type
@@ -52,8 +56,23 @@ def mlinterp_np(smin, smax, orders, values, s):
     # evaluated in double -- except the innermost `lam*v` product, float x
     # float -- and rounded to float once, on the store.
     lam64 = [l.astype(np.float64) for l in lam]
+    # wide=False: oml = (real)1 - lam (sdp_device.h:sdp_locate_axis), then per axis, last axis
+    # innermost, `oml * lo + lam * hi` with every operator in `dt` (sdp_device.h:SdpLerp)
+    oml = [dt(1) - l for l in lam]
     for v in range(values.shape[0]):
         V = values[v]
+
+        def rec_narrow(k, base):
+            if k == d - 1:
+                lo = V[base + M[k] * q[k]]
+                hi = V[base + M[k] * (q[k] + 1)]
+            else:
+                lo = rec_narrow(k + 1, base + M[k] * q[k])
+                hi = rec_narrow(k + 1, base + M[k] * (q[k] + 1))
+            return oml[k] * lo + lam[k] * hi
+        if not wide:
+            out[v] = rec_narrow(0, np.zeros(n_s, dtype=np.int64))
+            continue
 
         def rec(k, base):
             if k == d - 1:
@@ -131,8 +150,13 @@ def control_grids(spec, state_k, t_k=None):
     return grids, tuple(dims)
 
 
-def backup_node(spec, x_k, J_next_interp, t_k=None, full=False):
-    """sdp.py:639-691 (_value_at_state_vect) plus index and margin."""
+def backup_node(spec, x_k, J_next_interp, t_k=None, full=False, dtype=None):
+    """sdp.py:639-691 (_value_at_state_vect) plus index and margin.
+
+    `dtype` given: the direct kernel's definition in that type (`backup_node_real`; J_next_interp
+    is then an InterpReal)."""
+    if dtype is not None:
+        return backup_node_real(spec, x_k, J_next_interp, t_k, full)
     u_grids, control_dims = control_grids(spec, x_k, t_k)
     nb_control = len(u_grids)
     for i in range(nb_control):
@@ -169,12 +193,18 @@ def backup_node(spec, x_k, J_next_interp, t_k=None, full=False):
     return J_opt, u_opt, flat, margin
 
 
-def value_iteration(spec, J_next, rel_dp=False, t_k=None, nodes=None):
+def value_iteration(spec, J_next, rel_dp=False, t_k=None, nodes=None, dtype=None):
     """sdp.py:466-534.  Returns (J_k | (J_k, J_ref)), pol_k, idx_k, margin_k.
 
     `nodes`: optional iterable of flat C-order node ids; then 1-D outputs for
     those nodes only (used for sampled parity on big grids).
+
+    `dtype`: None is the reference's path in float64, the code below.  np.float32 or np.float64
+    is the direct kernel's definition restated in that type (`value_iteration_real`): J and the
+    policy come back in `dtype`.
     """
+    if dtype is not None:
+        return value_iteration_real(spec, J_next, dtype, rel_dp, t_k, nodes)
     if rel_dp:
         J_next, _ = J_next
         assert J_next[spec.ref_ind] == 0.                               # sdp.py:488
@@ -205,11 +235,18 @@ def value_iteration(spec, J_next, rel_dp=False, t_k=None, nodes=None):
     return J_k, pol_k, idx_k, mar_k
 
 
-def eval_policy(spec, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False, nodes=None):
+def eval_policy(spec, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False, nodes=None, dtype=None,
+                t_k=None):
     """sdp.py:693-775 with the expectation summed sequentially in w order.
 
     `nodes`: optional flat C-order node ids; then one step (n_iter == 1, no rel_dp) at those nodes only, a 1-D
-    result (the same operations per node as the whole grid: sampled parity on big grids)."""
+    result (the same operations per node as the whole grid: sampled parity on big grids).
+
+    `dtype`: None is the reference's path in float64, the code below; a type is the fixed-policy kernel's definition
+    restated in it (`eval_policy_real`; `t_k` is the time index of a non-stationary model there)."""
+    if dtype is not None:
+        return eval_policy_real(spec, pol, n_iter, dtype, rel_dp, J_zero, J_ref_full, nodes, t_k)
+    assert t_k is None
     if nodes is not None:
         assert n_iter == 1 and not rel_dp
         nodes = np.asarray(nodes, dtype=np.int64)
@@ -248,6 +285,202 @@ def eval_policy(spec, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False, 
         if rel_dp:
             J_ref[k] = J_pol[spec.ref_ind]                              # sdp.py:761
             J_pol -= J_ref[k]
+    if rel_dp:
+        return J_pol, (J_ref if J_ref_full else J_ref[-1])
+    return J_pol
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The definition the direct kernel implements (stodynprog_amd/csrc/sdp_sweep_kernel.h with sdp_device.h), restated
+# in one real type `dt`.  The sweep kernels are compiled with -ffp-contract=off -fno-fast-math: one IEEE operation
+# per source operator, and so is every numpy operator on arrays of `dt`.  Each line cites the kernel line it follows
+# (sweep.h = csrc/sdp_sweep_kernel.h, device.h = csrc/sdp_device.h, solver.py = stodynprog_amd/solver.py).
+#
+# In float64 these are the operations of the reference's path above: the lattice is numpy.linspace's own arithmetic
+# (step = delta / (n - 1), y = arange(n) * step + start, y[-1] = stop), the lerp tree is in double either way.
+# In float32 it is what nothing else in this module states: constants rounded ONCE from the solver's float64 values,
+# the callables on float32 arrays (numpy >= 2: Python float constants are weak), the whole tree in float32.
+# ---------------------------------------------------------------------------------------------------------------
+class InterpReal:
+    """J_next on the state grid as the sweep kernels read it: axes rounded once to `dt` (solver.py:_create_problem),
+    smin = axes[0], smax = axes[-1] in `dt` (sweep.h:sdp_grid_from_args), the pure-`dt` tree
+    (sweep.h:sdp_expected_cost -> device.h:sdp_interp_point<real, D, wide = real>)."""
+
+    def __init__(self, spec, values, dtype):
+        self.dt = dt = np.dtype(dtype).type
+        self.axes = [np.ascontiguousarray(g, dtype=dt) for g in spec.state_grid]      # solver.py:_create_problem
+        self.smin = [a[0] for a in self.axes]                                         # sweep.h:sdp_grid_from_args
+        self.smax = [a[-1] for a in self.axes]
+        self.orders = [len(a) for a in self.axes]
+        values = np.asarray(values)
+        assert values.dtype == dt, (values.dtype, dt)           # (the caller rounds: DPSolver casts J_next once)
+        self.values = np.ascontiguousarray(values).reshape(1, -1)
+
+    def __call__(self, *x_next):
+        dt = self.dt
+        for v in x_next:            # a wider result would be rounded twice; a Python float is weak and may pass
+            assert not isinstance(v, (np.ndarray, np.generic)) or v.dtype == dt, (v.dtype, dt)
+        x_mesh = np.broadcast_arrays(*[np.asarray(v, dtype=dt) for v in x_next])
+        shape = x_mesh[0].shape
+        s = np.vstack([x.ravel() for x in x_mesh])
+        # (the power-of-two spans' product with the reciprocal, device.h:sdp_div_span, is the true division's bits:
+        # stated as the division here, so that claim is checked too)
+        return mlinterp_np(self.smin, self.smax, self.orders, self.values, s, wide=False).reshape(shape)
+
+
+def control_lattice_real(spec, x_k, t_k, dt):
+    """Per control (lo, hi, n) as the host hands them to the kernel and the points the kernel makes of them.
+
+    solver.py:_box_lattice (the reference's control_grids, sdp.py:446-457) in float64: n from the width and the step
+    hint; a single point is the centre, stored as lo = hi.  Then ONE rounding of lo and hi to `dt`
+    (solver.py:_create_problem).  Points: sweep.h:sdp_load_box / sdp_control_value."""
+    state = tuple(x_k) if t_k is None else (t_k,) + tuple(x_k)
+    intervals = spec.control_box(*state, **spec.params)                             # float64, as the host calls it
+    grids, dims = [], []
+    with np.errstate(all='ignore'):
+        for (u_min, u_max), hint in zip(intervals, spec.control_steps):
+            n_interv = (u_max - u_min) / hint                                       # solver.py:_box_lattice
+            if n_interv < 0.1:
+                n = 1
+                lo = hi = dt((u_min + u_max) / 2)
+            else:
+                n = int(np.ceil(n_interv) + 1)
+                lo, hi = dt(u_min), dt(u_max)
+            if n == 1:
+                u = np.array([lo], dtype=dt)                                        # sdp_control_value: n == 1 -> lo
+            else:
+                delta = hi - lo                                                     # sdp_load_box: delta
+                step = delta / dt(n - 1)                                            # sdp_load_box: step
+                k = np.arange(n).astype(dt)                                         # (sdp_real)k
+                if step == dt(0):                                                   # sdp_control_value: step == 0
+                    u = (k / dt(n - 1)) * delta + lo
+                else:
+                    u = k * step + lo                                               # sdp_control_value: k * step + lo
+                u[n - 1] = hi                                                       # sdp_control_value: last point
+            assert u.dtype == dt
+            grids.append(u)
+            dims.append(n)
+    return grids, tuple(dims)
+
+
+def _check_real(values, dt):
+    """every result of a callable is of type `dt` (or a weak Python number): a wider one would be rounded twice"""
+    for v in values:
+        assert not isinstance(v, (np.ndarray, np.generic)) or v.dtype == dt, \
+            'the model returns {} from {} arguments'.format(v.dtype, np.dtype(dt))
+
+
+def _expectation_real(spec, J_cell, shape, dt):
+    """sweep.h:sdp_expected_cost: acc = 0; acc = acc + jc * p_w for w ascending, every operator in `dt`; a deterministic
+    system is g + J(f) itself.  J_cell: shape + (W,) (broadcastable)."""
+    if len(spec.perturb_grid) == 0:
+        return np.array(np.broadcast_to(J_cell, shape + (1,))[..., 0], dtype=dt)     # (the w axis has length 1)
+    proba = np.ascontiguousarray(spec.perturb_proba[0], dtype=dt)                  # solver.py:_create_problem
+    Jb = np.broadcast_to(J_cell, shape + (len(proba),))
+    acc = np.zeros(shape, dtype=dt)
+    for w in range(len(proba)):
+        acc = acc + Jb[..., w] * proba[w]
+    assert acc.dtype == dt
+    return acc
+
+
+def backup_node_real(spec, x_k, interp, t_k=None, full=False):
+    """One node of sweep.h:sdp_sweep.  x_k: the node's float64 coordinates (the box is the host's, in float64; the
+    kernel reads the axes rounded to `dt`: sdp_node_coords)."""
+    dt = interp.dt
+    u_grids, control_dims = control_lattice_real(spec, x_k, t_k, dt)
+    nb_control = len(u_grids)
+    u_mesh = [u.reshape((1,) * i + (-1,) + (1,) * (nb_control - i)) for i, u in enumerate(u_grids)]   # C order, control 0 slowest
+    args = tuple(dt(x) for x in x_k) + tuple(u_mesh)                                # sdp_node_coords
+    if len(spec.perturb_grid):
+        args = args + (np.ascontiguousarray(spec.perturb_grid[0], dtype=dt),)       # solver.py:_create_problem
+    if t_k is not None:
+        args = (dt(t_k),) + args                                                    # sdp_sweep: t = (sdp_real)a.t_k
+    x_next = spec.dyn(*args, **spec.params)
+    g = spec.cost(*args, **spec.params)
+    _check_real(tuple(x_next) + (g,), dt)
+    J_cell = g + interp(*x_next)                                                    # sdp_expected_cost: jc = g + interp
+    J = _expectation_real(spec, J_cell, control_dims, dt)
+    flat = int(J.argmin())          # first occurrence, the first NaN wins (device.h:sdp_better_seq / sdp_better_idx)
+    ind_opt = np.unravel_index(flat, control_dims)
+    J_opt = J[ind_opt]
+    u_opt = [u_grids[i][ind_opt[i]] for i in range(nb_control)]                     # sdp_controls_at(box, ibest)
+    Jr = J.ravel()
+    if Jr.size > 1:
+        margin = float(np.partition(Jr, 1)[1] - Jr[flat]) if not np.isnan(Jr).any() else 0.0
+    else:
+        margin = np.inf
+    if full:
+        return J_opt, u_opt, flat, margin, J
+    return J_opt, u_opt, flat, margin
+
+
+def value_iteration_real(spec, J_next, dtype, rel_dp=False, t_k=None, nodes=None):
+    """sweep.h:sdp_sweep on every node (or on `nodes`).  J_next is rounded to `dtype` once, as DPSolver does
+    (solver.py:_DeviceProblem.set_value); J and the policy come back in `dtype`, the margin in float64."""
+    dt = np.dtype(dtype).type
+    if rel_dp:
+        J_next, _ = J_next
+    interp = InterpReal(spec, np.asarray(J_next).astype(dt, copy=False), dt)
+    if rel_dp:
+        assert interp.values[0, np.ravel_multi_index(spec.ref_ind, spec.shape)] == 0.
+    nu = len(spec.control_steps)
+    whole = nodes is None
+    nodes = np.arange(int(np.prod(spec.shape))) if whole else np.asarray(nodes, dtype=np.int64)
+    J = np.zeros(len(nodes), dtype=dt); pol = np.zeros((len(nodes), nu), dtype=dt)
+    idx = np.zeros(len(nodes), dtype=np.int64); mar = np.zeros(len(nodes))
+    for n, flat in enumerate(nodes):
+        ind = np.unravel_index(flat, spec.shape)
+        x_k = tuple(g[i] for g, i in zip(spec.state_grid, ind))
+        J[n], pol[n], idx[n], mar[n] = backup_node_real(spec, x_k, interp, t_k)
+    if not whole:
+        assert not rel_dp
+        return J, pol, idx, mar
+    J, pol = J.reshape(spec.shape), pol.reshape(spec.shape + (nu,))
+    idx, mar = idx.reshape(spec.shape), mar.reshape(spec.shape)
+    if rel_dp:
+        J_ref = J[spec.ref_ind]
+        return (J - J_ref, float(J_ref)), pol, idx, mar                            # one subtraction in `dt` per node
+    return J, pol, idx, mar
+
+
+def eval_policy_real(spec, pol, n_iter, dtype, rel_dp=False, J_zero=None, J_ref_full=False, nodes=None, t_k=None):
+    """sweep.h:sdp_evalpol, n_iter times.  The policy and J_zero are rounded to `dtype` once
+    (solver.py:_DeviceProblem.set_policy / set_value).  Relative DP: step k reads every vertex as V - V[ref], ONE
+    rounding per vertex before the lerp (device.h:SdpLerp<.., SHIFT = true>) -- the bits of the reference's in-place
+    `J_pol -= J_ref[k]` (sdp.py:760-762) done in `dtype`, which is how it is stated here; J_ref per step is V[ref]."""
+    dt = np.dtype(dtype).type
+    dims = spec.shape
+    nb_state = len(dims)
+    pol = np.asarray(pol).astype(dt, copy=False)
+    nb_control = pol.shape[-1]
+    J_pol = np.zeros(dims, dtype=dt) if J_zero is None else np.asarray(J_zero).astype(dt, copy=False)
+    axes = [np.ascontiguousarray(g, dtype=dt) for g in spec.state_grid]            # sdp_node_coords
+    if nodes is not None:
+        assert n_iter == 1 and not rel_dp
+        ind = np.unravel_index(np.asarray(nodes, dtype=np.int64), dims)
+        out_dims = (len(nodes),)
+        x = tuple(a[i].reshape(-1, 1) for a, i in zip(axes, ind))
+        u = tuple(pol[ind + (c,)].reshape(-1, 1) for c in range(nb_control))
+    else:
+        out_dims = dims
+        x = tuple(np.reshape(axes[i], (1,) * i + (-1,) + (1,) * (nb_state - i)) for i in range(nb_state))
+        u = tuple(pol[..., c].reshape(dims + (1,)) for c in range(nb_control))
+    args = x + u
+    if len(spec.perturb_grid):
+        args = args + (np.ascontiguousarray(spec.perturb_grid[0], dtype=dt),)
+    if t_k is not None:
+        args = (dt(t_k),) + args
+    J_ref = np.zeros(n_iter)
+    for k in range(n_iter):
+        interp = InterpReal(spec, J_pol, dt)
+        x_next = spec.dyn(*args, **spec.params)
+        g = spec.cost(*args, **spec.params)
+        _check_real(tuple(x_next) + (g,), dt)
+        J_pol = _expectation_real(spec, g + interp(*x_next), out_dims, dt)          # sdp_expected_cost<SHIFT>
+        if rel_dp:
+            J_ref[k] = J_pol[spec.ref_ind]
+            J_pol = J_pol - J_pol[spec.ref_ind]                                     # SdpLerp<.., SHIFT = true>
     if rel_dp:
         return J_pol, (J_ref if J_ref_full else J_ref[-1])
     return J_pol

@@ -77,7 +77,15 @@ def _against_oracle(case, geometry, V, out, nodes, what, finite, smooth=False):
         else:
             assert np.array_equal(idx, io_), what + ': policy index differs from the oracle'
         return
-    # 4-byte reals: the bar of test_fp32_512cubed_against_fp64_oracle
+    # 4-byte reals: bit for bit the float32 oracle (the direct kernel's definition restated in numpy float32) ...
+    V32 = np.asarray(V, dtype=np.float32)
+    with np.errstate(all='ignore'):
+        J32, p32, i32_, _ = vi_numpy.value_iteration(vi_numpy.Spec.from_solver(ref), V32, nodes=nodes, dtype=np.float32)
+    assert np.array_equal(J, J32, equal_nan=True), what + ': J differs from the float32 oracle'
+    assert np.array_equal(idx, i32_), what + ': policy index differs from the float32 oracle'
+    assert np.array_equal(out[1].reshape(-1, p32.shape[-1])[nodes], p32, equal_nan=True), \
+        what + ': policy differs from the float32 oracle'
+    # ... and the bar of test_fp32_512cubed_against_fp64_oracle against the 8-byte one
     scale = np.abs(Jo).max()
     rel = np.abs(J - Jo).max() / scale
     assert rel < 1e-5, (what, rel)

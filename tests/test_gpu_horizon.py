@@ -111,6 +111,13 @@ def _check_oracle(s, J_next, k, got, nodes, what, dtype, finite=True):
         else:
             assert np.array_equal(idx, io_), what + ': policy index differs from the oracle'
         return
+    # 4-byte reals: bit for bit the float32 oracle at step k, next to the bar against the 8-byte one
+    with np.errstate(all='ignore'):
+        J32, p32, i32, _ = vi_numpy.value_iteration(spec, np.asarray(J_next, dtype=np.float32), t_k=k, nodes=nodes,
+                                                    dtype=np.float32)
+    assert np.array_equal(J, J32.ravel(), equal_nan=True), what + ': J differs from the float32 oracle'
+    assert np.array_equal(idx, i32.ravel()), what + ': policy index differs from the float32 oracle'
+    assert np.array_equal(pol, p32.reshape(-1, p32.shape[-1]), equal_nan=True), what + ': policy differs from the float32 oracle'
     rel = np.abs(J - Jo).max() / np.abs(Jo).max()
     assert rel < 1e-5, (what, rel)
     clear = mo > 1e-5 * np.maximum(1.0, np.abs(Jo))

@@ -890,6 +890,11 @@ def test_fp32_512cubed_against_fp64_oracle(gpu):
                                      node_ids=nodes, n_threads=8)
     rel = np.abs(J32.ravel()[nodes] - Jo).max() / np.abs(Jo).max()
     assert rel < 1e-5, rel
+    # bit for bit the float32 oracle (the direct kernel's definition restated in numpy float32) on the same nodes
+    Jf, pf, if_, _ = vi_numpy.value_iteration(vi_numpy.Spec.from_solver(ref), V0.astype(np.float32), nodes=nodes,
+                                              dtype=np.float32)
+    assert np.array_equal(J32.ravel()[nodes], Jf) and np.array_equal(idx32.ravel()[nodes], if_)
+    assert np.array_equal(u32.reshape(-1, 1)[nodes], pf)
     # indices: exact wherever the fp64 margin is above fp32 resolution
     clear = mo > 1e-5 * np.maximum(1.0, np.abs(Jo))
     assert (idx32.ravel()[nodes][clear] == io[clear]).all()

@@ -269,3 +269,128 @@ def test_simulation_oracle_time_index_and_deterministic_model():
     assert x.shape == (4, 2, 1) and u.shape == (3, 2, 1) and g.shape == (3, 2)
     assert np.array_equal(x[:, 0, 0], [1.0, 0.25, 0.0625, 0.015625])      # u = -x / 4 on the grid
     assert u[0, 1, 0] == -1.0 and x[1, 1, 0] == 1.0                        # extrapolated past x = 2
+
+
+# ---------------------------------------------------------------- the kernel's definition restated in one real type
+# (vi_numpy.value_iteration_real / eval_policy_real: what tests/test_gpu_fp32_oracle.py compares the 4-byte kernels with)
+def _same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
+
+
+def test_restated_definition_in_float64_is_the_reference_path_bit_for_bit():
+    """The structure of the restatement is right: in float64 it gives the bits of the functions pinned on the
+    reference's fixtures -- the kernel's lattice (k * step + lo, last point hi) is numpy.linspace's arithmetic, the
+    narrow lerp tree is the double tree.  On the problems of the G2, G3 and G5 fixtures, from their own inputs."""
+    g2, g3, g5 = golden('g2_inventory'), golden('g3_ar1_ref'), golden('g5_synth')
+    cases = []
+    _, inv = models.inventory()
+    cases.append((inv, g2['J'][1], None))
+    _, ar1 = models.storage_ar1()
+    rng = np.random.default_rng(3)
+    cases.append((ar1, g3['J1'], np.unique(np.concatenate([rng.integers(0, 41 * 61, 60), [0, 41 * 61 - 1]]))))
+    _, syn = models.synthetic3d(N=20)
+    cases.append((syn, g5['s_J1'], np.arange(0, 8000, 13)))
+    for solver, V, nodes in cases:
+        spec = vi_numpy.Spec.from_solver(solver)
+        old = vi_numpy.value_iteration(spec, V, nodes=nodes)
+        new = vi_numpy.value_iteration(spec, V, nodes=nodes, dtype=np.float64)
+        for a, b, what in zip(old, new, ('J', 'policy', 'index', 'margin')):
+            assert _same_bits(a, b), (solver.sys.name, what)
+        # the lattice itself, node by node
+        for flat in (range(int(np.prod(spec.shape))) if nodes is None else nodes[:40]):
+            x_k = tuple(g[i] for g, i in zip(spec.state_grid, np.unravel_index(flat, spec.shape)))
+            ga, da = vi_numpy.control_grids(spec, x_k)
+            gb, db = vi_numpy.control_lattice_real(spec, x_k, None, np.float64)
+            assert da == db and all(_same_bits(a, b) for a, b in zip(ga, gb)), (solver.sys.name, flat)
+    # the fixed-policy backup, with and without the relative-DP shift, on the problem of the G6 fixture
+    spec = vi_numpy.Spec.from_solver(ar1)
+    pol = models.storage_ar1_empirical_policy(ar1)
+    for rel in (False, True):
+        old = vi_numpy.eval_policy(spec, pol, 4, rel_dp=rel, J_zero=g3['J1'] * 0.1, J_ref_full=True)
+        new = vi_numpy.eval_policy(spec, pol, 4, rel_dp=rel, J_zero=g3['J1'] * 0.1, J_ref_full=True, dtype=np.float64)
+        if rel:
+            assert _same_bits(old[0], new[0]) and _same_bits(old[1], new[1])
+        else:
+            assert _same_bits(old, new)
+    # a time-dependent model (the G8 fixture's)
+    _, fh = models.finite_horizon()
+    spec = vi_numpy.Spec.from_solver(fh)
+    g8 = golden('g8_bellman')
+    for a, b in zip(vi_numpy.value_iteration(spec, g8['J_fin'], t_k=3),
+                    vi_numpy.value_iteration(spec, g8['J_fin'], t_k=3, dtype=np.float64)):
+        assert _same_bits(a, b)
+
+
+def _restated_models():
+    return [('synthetic3d', dict(N=24)), ('storage_ar1', dict(n_E=33, n_P=20, steps=(0.05, 0.1))),
+            ('searev', dict(n_E=17, n_S=12, n_A=9, step=0.01)), ('inventory', {}), ('nas_demo', {}),
+            ('two_reservoirs', dict(n_a=12, n_b=10, n_y=8)), ('synthetic3d_coupled', dict(N=16)),
+            ('inventory_markov', dict(n_x=48, n_d=12))]
+
+
+def _smooth_V(solver):
+    V = np.zeros(solver._state_grid_shape)
+    for k, g in enumerate(solver.state_grid):
+        g = np.asarray(g, dtype=float)
+        shape = [1] * V.ndim
+        shape[k] = -1
+        z = (g - g[0]) / (g[-1] - g[0])
+        V = V + (1.0 + 0.5 * k) * ((z - 0.4) * (z - 0.4)).reshape(shape)
+    return V
+
+
+@pytest.mark.parametrize('name,kw', _restated_models(), ids=[m[0] for m in _restated_models()])
+def test_restated_definition_in_float32_is_within_the_float32_bar_of_float64(name, kw):
+    """float32 against the float64 oracle on sampled nodes: within 1e-5 of max |J| (the project's bar for 4-byte
+    results), from a standard-normal and from a smooth cost-to-go; every result of the callables is float32
+    (asserted inside), and the model is one the tracer calls bit-exact."""
+    _, solver = getattr(models, name)(**kw)
+    assert solver._traced().bit_exact and not solver._traced().inexact_ops()
+    spec = vi_numpy.Spec.from_solver(solver)
+    S = int(np.prod(spec.shape))
+    nodes = np.unique(np.concatenate([np.random.default_rng(1).integers(0, S, 150), [0, S - 1]]))
+    for V in (np.random.default_rng(2).standard_normal(spec.shape), _smooth_V(solver)):
+        V32 = V.astype(np.float32)
+        with np.errstate(all='ignore'):
+            J64, _, i64, m64 = vi_numpy.value_iteration(spec, V32.astype(float), nodes=nodes)
+            J32, p32, i32, _ = vi_numpy.value_iteration(spec, V32, nodes=nodes, dtype=np.float32)
+        assert J32.dtype == np.float32 and p32.dtype == np.float32
+        assert np.abs(J32 - J64).max() <= 1e-5 * np.abs(J64).max(), (name, np.abs(J32 - J64).max() / np.abs(J64).max())
+        clear = m64 > 1e-4 * np.maximum(1.0, np.abs(J64))
+        assert (i32[clear] == i64[clear]).all(), name
+    # the fixed-policy backup too, on the small grids: two steps of the float32 sweep's own policy
+    if S <= 2500:
+        with np.errstate(all='ignore'):
+            _, pol, _, _ = vi_numpy.value_iteration(spec, V32, dtype=np.float32)
+            E64 = vi_numpy.eval_policy(spec, pol.astype(float), 2, J_zero=V32.astype(float))
+            E32 = vi_numpy.eval_policy(spec, pol, 2, J_zero=V32, dtype=np.float32)
+        assert E32.dtype == np.float32 and np.abs(E32 - E64).max() <= 1e-5 * np.abs(E64).max()
+
+
+def test_restated_definition_refuses_a_model_that_widens():
+    """a callable that returns float64 from float32 arguments (a numpy float64 parameter) would be rounded twice:
+    the width assertion trips instead of a comparison being made"""
+    from stodynprog_amd import SysDescription, DPSolver
+    gain = np.float64(0.3)
+    s = SysDescription((1, 1, 1), name='widening')
+
+    def dyn(x, u, w):
+        return (0.9 * x + gain * u + w,)
+
+    def cost(x, u, w):
+        return x * x + 0.1 * u * u
+    s.dyn, s.cost = dyn, cost
+    s.control_box = lambda x: ((-1., 1.),)
+    s.perturb_laws = [models.NormalLaw(0, 0.1)]
+    solver = DPSolver(s)
+    solver.discretize_state(-1, 1, 9)
+    solver.discretize_perturb(-0.3, 0.3, 3)
+    solver.control_steps = (0.25,)
+    spec = vi_numpy.Spec.from_solver(solver)
+    V = np.zeros(9, dtype=np.float32)
+    vi_numpy.value_iteration(spec, V, dtype=np.float64)            # nothing to widen to in float64
+    with pytest.raises(AssertionError, match='float64'):
+        vi_numpy.value_iteration(spec, V, dtype=np.float32)
+    with pytest.raises(AssertionError, match='float64'):
+        vi_numpy.eval_policy(spec, np.zeros((9, 1), dtype=np.float32), 1, dtype=np.float32)
