@@ -246,6 +246,31 @@ int sdp_problem_simulate(sdp_problem *p, const void *host_pol, int64_t B, int64_
                          const void *host_x0, const void *host_w, double t0,
                          void *host_x, void *host_u, void *host_g);
 
+/*
+ * Monte Carlo evaluation of a policy without leaving the device: B closed-loop trajectories of T
+ * steps as above, but the perturbation of every step is DRAWN on the device and only reductions
+ * come back.  The draw of trajectory row b at step k (k = 0..T-1, absolute over the whole call):
+ *     Philox4x32-10, key = (seed low word, seed high word),
+ *                    counter = (id low, id high, k low, k high),  id = traj_offset + b
+ *     u = ((r0 >> 5) * 2^26 + (r1 >> 6)) * 2^-53       output words 0 and 1; a double in [0, 1)
+ *     j = number of i in [0, n_law - 2] with u >= host_cum[i];   w = host_law_grid[j]
+ * host_cum [n_law] doubles: running sum of the law's probabilities (its last entry is not read);
+ * host_law_grid [n_law] reals, n_law in 1..4096.  A draw depends on (seed, id, k) alone: B, the
+ * launch grid and steps_per_launch (the run is cut into kernel launches of at most that many
+ * steps, the state kept on the device between them) do not change a bit of the results.
+ * Over the steps k >= n_burn: host_cost_sum [B] reals, acc = acc + g[k] in k order;
+ * host_n_outside [B] int64, steps whose x[k] has a component below the first / above the last
+ * grid point or NaN; host_occupancy [S] uint64 or NULL, visits of the grid node nearest to x[k]
+ * (per axis the interpolation cell + (weight >= 0.5), clamped; C order).  host_x_final [d][B]:
+ * the state after step T-1.  host_pol, host_x0, t0: as for the simulation above.  Stochastic
+ * systems on one GPU only (SDP_EINVAL otherwise).
+ */
+int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int64_t B, int64_t T, int64_t n_burn,
+                           uint64_t seed, uint64_t traj_offset, const void *host_x0,
+                           const double *host_cum, int32_t n_law, const void *host_law_grid, double t0,
+                           int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                           void *host_x_final, uint64_t *host_occupancy);
+
 /* Make the last J_k the next J_next without leaving the device. */
 int sdp_problem_swap(sdp_problem *p);
 

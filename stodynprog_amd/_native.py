@@ -111,6 +111,8 @@ def _declare(lib):
         'sdp_problem_backup_host': (C.c_int, [vp, vp, dbl, C.c_int, i64, vp, vp, vp, P(dbl)]),
         'sdp_problem_set_host_overlap': (C.c_int, [vp, C.c_int]),
         'sdp_problem_simulate': (C.c_int, [vp, vp, i64, i64, vp, vp, dbl, vp, vp, vp]),
+        'sdp_problem_montecarlo': (C.c_int, [vp, vp, i64, i64, i64, C.c_uint64, C.c_uint64, vp, vp, i32, vp, dbl,
+                                             i64, vp, vp, vp, vp]),
         'sdp_host_alloc': (C.c_int, [C.c_size_t, P(vp)]),
         'sdp_host_free': (C.c_int, [vp]),
         'sdp_comm_library': (C.c_char_p, []),

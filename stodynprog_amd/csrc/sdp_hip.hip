@@ -935,7 +935,7 @@ struct sdp_problem {
     int64_t stamp_words = 0;
     size_t scratch_bytes = 0;
     hipModule_t mod = nullptr;
-    hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr;
+    hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr;
     // several controlled state variables (csrc/sdp_lead_kernel.h): the kernel that reduces V over w, launched
     // before every sweep, and its outputs (A[S] and a copy of V, both plane-major; E[nodes per trailing block];
     // bits of max |V|)
@@ -1218,6 +1218,10 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if (hipModuleGetFunction(&p->f_simulate, p->mod, "sdp_simulate") != hipSuccess) {
         (void)hipGetLastError();
         p->f_simulate = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_montecarlo, p->mod, "sdp_montecarlo") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_montecarlo = nullptr;
     }
     // lifted model constants (codegen: `__constant__ sdp_real sdp_model_prm[]`), if any
     if (hipModuleGetGlobal(&p->prm_dev, &p->prm_bytes, p->mod, "sdp_model_prm") != hipSuccess) {
@@ -2290,6 +2294,84 @@ extern "C" int sdp_problem_simulate(sdp_problem *p, const void *host_pol, int64_
     HIP_TRY(hipMemcpy(host_x, dx.p, (size_t)(T + 1) * p->d * B * rs, hipMemcpyDeviceToHost));
     if (T > 0) HIP_TRY(hipMemcpy(host_u, du.p, (size_t)T * p->nu * B * rs, hipMemcpyDeviceToHost));
     if (host_g && T > 0) HIP_TRY(hipMemcpy(host_g, dg.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// Monte Carlo policy evaluation on the device (kernel sdp_montecarlo of the model's code object):
+// see include/sdp_hip.h.  The policy goes up once, the run is cut into launches of at most
+// steps_per_launch steps with the state in device buffers between them, the reductions come back once.
+extern "C" int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int64_t B, int64_t T, int64_t n_burn,
+                                      uint64_t seed, uint64_t traj_offset, const void *host_x0,
+                                      const double *host_cum, int32_t n_law, const void *host_law_grid, double t0,
+                                      int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                                      void *host_x_final, uint64_t *host_occupancy)
+{
+    if (!p || !host_pol || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (p->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw: use sdp_problem_simulate");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    if (p->comm && p->comm->nranks > 1) return fail(SDP_EINVAL, "Monte Carlo evaluation runs on one GPU");
+    if (!p->f_montecarlo) return fail(SDP_EMODULE, "the model's code object has no sdp_montecarlo kernel");
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(p->dtype);
+    DevBuf dpol, dx, dacc, dout, dcum, dlaw, docc;
+    int rc;
+    if ((rc = upload(dpol, host_pol, (size_t)p->nu * p->S * rs))) return rc;
+    if ((rc = upload(dx, host_x0, (size_t)p->d * B * rs))) return rc;
+    if ((rc = upload(dcum, host_cum, (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, (size_t)n_law * rs))) return rc;
+    if ((rc = dacc.alloc((size_t)B * rs))) return rc;
+    if ((rc = dout.alloc((size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, (size_t)B * rs, p->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, (size_t)B * 8, p->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc((size_t)p->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, (size_t)p->S * 8, p->stream));
+    }
+    SdpMcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.axes = p->axes.p; a.cum = (const double *)dcum.p; a.law_grid = dlaw.p;
+    a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.S = p->S; a.seed = seed; a.traj_offset = traj_offset; a.n_burn = n_burn; a.t0 = t0; a.n_law = n_law;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    // one lane per trajectory; at most the workgroups of 256 that are resident at once (the kernel's registers and the
+    // draw table decide how many a CU holds: 8 for the small models, 5 or 6 for the large ones), the rest in a
+    // grid-stride loop
+    const int threads = 256;
+    const unsigned lds = (unsigned)((size_t)(n_law - 1) * 8 + (size_t)n_law * rs);      // cumulative table, then the values
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p->f_montecarlo, threads, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 8) per_cu = 8;
+    int64_t blocks = (B + threads - 1) / threads;
+    if (blocks > (int64_t)p->cus * per_cu) blocks = (int64_t)p->cus * per_cu;
+    HIP_TRY(hipStreamSynchronize(p->stream));        // lifted constants set on the problem stream
+    HIP_TRY(hipEventRecord(p->ev0, p->stream));
+    for (int64_t k = 0; k < T; k += steps_per_launch) {
+        a.step_begin = k;
+        a.step_end = (T - k < steps_per_launch) ? T : k + steps_per_launch;
+        HIP_TRY(hipModuleLaunchKernel(p->f_montecarlo, (unsigned)blocks, 1, 1, threads, 1, 1, lds, p->stream, nullptr, extra));
+    }
+    HIP_TRY(hipEventRecord(p->ev1, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+    p->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, (size_t)p->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, (size_t)p->S * 8, hipMemcpyDeviceToHost));
     return SDP_OK;
 }
 

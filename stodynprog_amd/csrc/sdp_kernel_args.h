@@ -116,6 +116,32 @@ struct SdpSimArgs {
     int32_t axis_off[SDP_MAXD];
 };
 
+// Monte Carlo policy evaluation (sdp_mc_kernel.h): the same closed loop with the perturbation drawn on
+// the device (Philox4x32-10 keyed by the seed, counter = trajectory id and absolute step) and reduced
+// per trajectory; one launch runs the steps [step_begin, step_end) and leaves the state in the buffers.
+struct SdpMcArgs {
+    const void *pol;       // [nu][S] policy, like SdpSimArgs
+    const void *axes;      // concatenated state-grid axes
+    const double *cum;     // [n_law] float64 running sum of the law's probabilities (the last entry is not read)
+    const void *law_grid;  // [n_law] perturbation values (reals)
+    void *x;               // [d][B] states: x at step_begin in, x at step_end out
+    void *acc;             // [B] running cost sums (reals)
+    long long *n_outside;  // [B] steps k >= n_burn whose x_k lies outside the state grid or is NaN
+    unsigned long long *occupancy;   // [S] visits of the node nearest to x_k, k >= n_burn (null: not counted)
+    int64_t B;             // trajectories
+    int64_t S;             // state nodes
+    uint64_t seed;         // Philox key
+    uint64_t traj_offset;  // id of row 0 (Philox counter words 0 and 1 hold traj_offset + row)
+    int64_t step_begin;    // absolute step index (Philox counter words 2 and 3) of this launch's first step
+    int64_t step_end;      // one past its last step
+    int64_t n_burn;        // steps before this one advance the state only
+    double t0;             // time index of step 0 (non-stationary systems)
+    int32_t n_law;         // points of the law (>= 1)
+    int32_t pad_;
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+};
+
 // Stand-alone multilinear interpolation (multilinear_cython.pyx:17-49).
 struct SdpInterpArgs {
     const void *values;    // [n_v][S]

@@ -287,6 +287,10 @@ extern "C" __global__ void __launch_bounds__(64) sdp_simulate(SdpSimArgs a)
     }
 }
 
+#if SDP_HAS_W
+#include "sdp_mc_kernel.h"      // sdp_montecarlo: the same loop with the perturbation drawn on the device, reduced per trajectory
+#endif
+
 // what this code object was generated for (sdp_kernel_args.h, SDP_META_*); units that include
 // sdp_column_kernel.h define it at the end of that file, where the column macros are complete
 #if !defined(SDP_COL_N0)

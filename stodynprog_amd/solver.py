@@ -29,6 +29,7 @@ import numpy as np
 from . import _native as nat
 from . import codegen
 from . import convergence as conv
+from . import montecarlo as mc
 from .interp import MlinInterpolator
 from .trace import TraceError, trace_model, trace_box, callable_fingerprint, _fp_value, _NoFingerprint
 
@@ -248,6 +249,12 @@ class DPSolver(object):
     # code, defaults, closure cells and the globals they name, by value; callables that have none are traced on every call);
     # False: trace on every call, as rounds 1-5 did
     trace_cache = True
+    # monte_carlo: a run of n_steps is cut into kernel launches of at most this many steps (the state stays on the
+    # device between them; the draws are keyed by the absolute step, so the cut changes no bit).  The default is an
+    # estimate (a few microseconds per step and lane): no launch has been timed yet.
+    steps_per_launch = 1024
+    # .. and the host loop of untraceable models draws and keeps this many steps at a time
+    MC_HOST_BLOCK = 64
     _debug_after_create = None
     STAGED_MIN_NODES = 32768          # 'auto': grids of at most this many nodes run the direct kernel, not the staged tiles (see _kernel_plan_now);
     STAGED_MIN_WORK = 1024            #         up to 4 x as many where a node has this many control x perturbation points or more
@@ -1777,6 +1784,147 @@ class DPSolver(object):
                 x[k + 1, :, i] = xn[i]
             g[k] = self.sys.cost(*args, **self.sys.params)
         return x, u, g
+
+    # ------------------------------------------------------------ Monte Carlo policy evaluation
+    def _mc_law(self, law):
+        if not self.sys.stochastic:
+            raise ValueError('a deterministic system has nothing to draw: use simulate(pol, x0, n_steps=...)')
+        if len(self.sys.perturb) != 1:
+            raise NotImplementedError('monte_carlo draws one perturbation variable')
+        if law is None:
+            law = (self.perturb_grid[0], self.perturb_proba[0])
+        if len(law) != 2:
+            raise ValueError('law must be (grid, proba)')
+        return mc.check_law(*law)
+
+    @staticmethod
+    def _mc_ids(n_traj, traj_offset):
+        n_traj, traj_offset = int(n_traj), int(traj_offset)
+        if n_traj < 1:
+            raise ValueError('n_traj must be at least 1')
+        if traj_offset < 0 or traj_offset + n_traj > 1 << 64:
+            raise ValueError('trajectory ids must lie in [0, 2**64)')
+        return np.arange(n_traj, dtype=np.uint64) + np.uint64(traj_offset)
+
+    def monte_carlo_draws(self, seed, n_traj, n_steps, law=None, traj_offset=0):
+        """The perturbations `monte_carlo` draws on the device, from their definition in numpy
+        (`stodynprog_amd.montecarlo`): trajectories traj_offset .. traj_offset + n_traj - 1, steps
+        0 .. n_steps - 1.  Returns (indices, w): (n_steps, n_traj) int32 indices
+        into the law and the values law_grid[indices] in the problem's reals, so that
+        `simulate(pol, x0, w)` replays the run.  NOT in the reference API."""
+        grid, proba = self._mc_law(law)
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError('n_steps must not be negative')
+        ids = self._mc_ids(n_traj, traj_offset)
+        steps = np.arange(n_steps, dtype=np.uint64)
+        idx = mc.draws(seed, ids, steps, proba)
+        return idx, grid.astype(self.dtype)[idx]
+
+    def monte_carlo(self, pol, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False,
+                    traj_offset=0, t0=0):
+        """Monte Carlo evaluation of the policy `pol`: the closed loop of `simulate` for a batch of
+        trajectories, with every step's perturbation drawn ON THE DEVICE from the discretised law and
+        only per-trajectory reductions coming back -- the `cost.mean()` at the end of the
+        reference's examples (examples/20 Searev storage control/storage_control.py:197-265)
+        without T x B reals up and (T+1) d B + T nu B + T B reals down.  NOT in the reference API.
+
+        pol      : policy array, shape state_dims + (nb_control,)
+        x0       : start state (nb_state,) -- then give n_traj -- or one per trajectory (B, nb_state)
+        n_steps  : steps per trajectory
+        seed     : the run is a function of (seed, trajectory id, step) alone (Philox4x32-10, see
+                   `stodynprog_amd.montecarlo`): batch size, launch configuration and how a batch is
+                   split over calls (traj_offset = id of row 0) do not change a bit
+        n_burn   : the first n_burn steps advance the state but enter no reduction
+        law      : (grid, proba) of the perturbation, at most 4096 points; default: the solver's
+                   own perturb_grid / perturb_proba, the chain the DP optimised against
+        occupancy: also count, per grid node, the visits of the node nearest to x_k (k >= n_burn)
+        t0       : time index of the first step (non-stationary systems)
+
+        Returns a `montecarlo.MonteCarloResult`: cost_sum, cost_mean, n_outside, x_final,
+        occupancy, mean, stderr.  Models that `simulate` runs on the host (untraceable ones) run
+        the same host loop here, fed by `montecarlo.draws`."""
+        dims = self._state_grid_shape
+        d, nu = len(dims), len(self.sys.control)
+        grid, proba = self._mc_law(law)
+        if self.comm is not None and self.comm.nranks > 1:
+            raise NotImplementedError('monte_carlo runs on one GPU')
+        pol = np.asarray(pol)
+        if pol.shape != dims + (nu,):
+            raise ValueError('pol must have shape {}, not {}'.format(dims + (nu,), pol.shape))
+        x0 = np.asarray(x0, dtype=float)
+        if x0.ndim == 1:
+            if x0.shape != (d,):
+                raise ValueError('x0 must have shape ({},) or (B, {})'.format(d, d))
+            if n_traj is None:
+                raise ValueError('give n_traj with a single start state')
+            x0 = np.broadcast_to(x0, (int(n_traj), d))
+        elif x0.ndim != 2 or x0.shape[1] != d:
+            raise ValueError('x0 must have shape ({},) or (B, {})'.format(d, d))
+        elif n_traj is not None and int(n_traj) != x0.shape[0]:
+            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[0]))
+        B = x0.shape[0]
+        n_steps, n_burn = int(n_steps), int(n_burn)
+        if n_steps < 1 or not 0 <= n_burn < n_steps:
+            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
+        seed = mc.check_seed(seed)
+        ids = self._mc_ids(B, traj_offset)
+        spl = int(self.steps_per_launch)
+        if spl < 1:
+            raise ValueError('steps_per_launch must be at least 1')
+        dt = self.dtype
+        t_trace = None if self.sys.stationnary else t0
+        model = self._trace_now(t_trace)
+        if isinstance(model, TraceError) or (model.t_value is not None):
+            cost_sum, n_out, x_final, occ = self._monte_carlo_host(pol, x0, n_steps, n_burn, seed, ids, grid, proba,
+                                                                   occupancy, t0)
+            path = 'host'
+        else:
+            prob = self._problem(t_trace, model)
+            pol_d = np.ascontiguousarray(np.moveaxis(pol, -1, 0), dtype=dt)        # [nu][S]
+            x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
+            cum = np.ascontiguousarray(mc.cumulative(proba))
+            law_d = np.ascontiguousarray(grid, dtype=dt)
+            cost_sum = np.empty(B, dtype=dt)
+            n_out = np.empty(B, dtype=np.int64)
+            x_final = np.empty((d, B), dtype=dt)
+            occ = np.empty(int(np.prod(dims)), dtype=np.uint64) if occupancy else None
+            nat.check(nat.lib().sdp_problem_montecarlo(
+                prob.h, nat.ptr(pol_d), B, n_steps, n_burn, seed, int(traj_offset), nat.ptr(x0_d), nat.ptr(cum),
+                len(proba), nat.ptr(law_d), float(t0), spl, nat.ptr(cost_sum), nat.ptr(n_out), nat.ptr(x_final),
+                nat.ptr(occ)))
+            x_final = np.ascontiguousarray(x_final.T)
+            if occ is not None:
+                occ = occ.astype(np.int64).reshape(dims)
+            path = 'device'
+        return mc.MonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seed, int(traj_offset), t0, path)
+
+    def _monte_carlo_host(self, pol, x0, n_steps, n_burn, seed, ids, grid, proba, occupancy, t0):
+        """the reductions of the kernel in numpy over `_simulate_host`, a block of steps at a time"""
+        dims = self._state_grid_shape
+        dt = self.dtype
+        B = x0.shape[0]
+        smin = np.array([g[0] for g in self.state_grid], dtype=float)
+        smax = np.array([g[-1] for g in self.state_grid], dtype=float)
+        x = np.array(x0, dtype=float)
+        acc = np.zeros(B, dtype=dt)
+        n_out = np.zeros(B, dtype=np.int64)
+        occ = np.zeros(dims, dtype=np.int64) if occupancy else None
+        wgrid = grid.astype(dt)
+        for k0 in range(0, n_steps, self.MC_HOST_BLOCK):
+            n = min(self.MC_HOST_BLOCK, n_steps - k0)
+            steps = np.arange(k0, k0 + n, dtype=np.uint64)
+            w = wgrid[mc.draws(seed, ids, steps, proba)].astype(float)
+            xs, _, g = self._simulate_host(pol, x, w, n, t0 + k0)
+            for i in range(n):
+                if k0 + i < n_burn:
+                    continue
+                acc = acc + g[i].astype(dt)
+                n_out += ~np.all((xs[i] >= smin) & (xs[i] <= smax), axis=1)
+                if occ is not None:
+                    np.add.at(occ, tuple(mc.nearest_nodes(xs[i], self.state_grid, np.float64).T), 1)   # (host states are float64)
+            x = xs[n]
+        return acc, n_out, x.astype(dt), occ
 
     # ------------------------------------------------------------------ reporting
     def print_summary(self):
