@@ -29,13 +29,14 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 # SDP_LEAD_FILTER = 0 switch a form off, SDP_COL_THREADS / SDP_COL_WCHUNK /
 # SDP_STG_CU / SDP_COL_WPAIR force a shape).  A solver that carries such a dict says
 # so in backend_info['debug_defines'], and bench.py in config.debug_defines.
+# Only switches that a header still reads are listed: the A/B forks whose outcome is settled (docs/NOTEBOOK.md,
+# "Retired switches") are gone from the headers, and their names are refused here like any typo.
 # ---------------------------------------------------------------------------
-# macros copied into the generated unit as they are (integers)
-DEBUG_INT_MACROS = ('SDP_COL_SHARE_X2', 'SDP_COL_MIN_WAVES', 'SDP_COL_BATCH', 'SDP_COL_WMODE', 'SDP_COL_UNROLL_U', 'SDP_COL_UNROLL_W',
-                    'SDP_COL_A_GROUP', 'SDP_COL_A_ORDER', 'SDP_COL_FILTER_UNROLL', 'SDP_COL_B_PRIO',
-                    'SDP_COL_FILTER_TOP2', 'SDP_COL_TILE', 'SDP_COL_FILTER_RUNROLL', 'SDP_COL_LEAN', 'SDP_COL_WIDE',
-                    'SDP_COL_A_WIDE_LOADS', 'SDP_COLU_WIDE_LOADS', 'SDP_COLU_A_GROUP', 'SDP_COL_LDS_PAD', 'SDP_COL_HOIST',
-                    'SDP_COL_TAIL_KEEP', 'SDP_COL_KEEP_BATCH', 'SDP_COL_KEEP_LOADS', 'SDP_COL_TAIL_HOLD', 'SDP_SHORT_GROUP', 'SDP_BNB_CHUNK')
+# macros copied into the generated unit as they are (integers): tuning parameters and the forms tests and tools select
+DEBUG_INT_MACROS = ('SDP_COL_MIN_WAVES', 'SDP_COL_BATCH', 'SDP_COL_UNROLL_U', 'SDP_COL_UNROLL_W',
+                    'SDP_COL_A_GROUP', 'SDP_COL_FILTER_UNROLL', 'SDP_COL_FILTER_TOP2', 'SDP_COL_FILTER_RUNROLL',
+                    'SDP_COL_A_WIDE_LOADS', 'SDP_COLU_WIDE_LOADS', 'SDP_COLU_A_GROUP',
+                    'SDP_COL_TAIL_HOLD', 'SDP_SHORT_GROUP', 'SDP_BNB_CHUNK')
 # (SDP_COL_LEAN2 = 0 keeps the resident-chunk kernel on the first pass of section 3.1c: an A/B switch of short_pass_source)
 # (SDP_COL_WRES is a planning switch: it sizes the LDS image -- column_config)
 # every name a `debug` dict may carry (a typo must not pass silently)
@@ -507,7 +508,7 @@ def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, 
         if _dbg(debug, 'SDP_COL_FILTER_SCALE'):
             lines.append('#define SDP_COL_FILTER_SCALE {}'.format(float(_dbg(debug, 'SDP_COL_FILTER_SCALE'))))
     # how the table build deals its entries to the threads
-    if per_control is None and not _dbg(debug, 'SDP_COL_A_ORDER'):
+    if per_control is None:
         wide = column_wide_loads(column[0], dtype, window, debug)
         order = column_build_order(int(col_cfg[0]), column[1], int(window[2]) if window is not None else column[0],
                                    (16 // rs) if wide else 1)
@@ -527,8 +528,7 @@ def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, 
                 # bits) -- where they are whole rounds of points and rows and at most 32 registers per thread
                 # (on the shifted lattice too since the second pass is no longer unrolled there: 2.23 -> 2.12 ms, box 11 of
                 # profiles/r06_column_ab.txt; with the unrolled pass it had lost, 2.96 against 2.71 ms)
-                if (wres and rs == 8 and not wpair and window is None and _dbg(debug, 'SDP_COL_TAIL_HOLD') is None
-                        and not _dbg(debug, 'SDP_COL_TAIL_KEEP')):
+                if wres and rs == 8 and not wpair and window is None and _dbg(debug, 'SDP_COL_TAIL_HOLD') is None:
                     tail, groups = int(column[1]) - int(wres), int(col_cfg[0]) // lw
                     if (tail > 0 and tail % groups == 0 and int(column[0]) % (2 * lw) == 0
                             and (tail // groups) * (int(column[0]) // (2 * lw)) * 4 <= 32):
@@ -552,14 +552,13 @@ def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, 
         if not model.cost_depends_on_w and window is None and per_control is None \
                 and _dbg(debug, 'SDP_COL_LEAN2') != '0' and (not shifted or rs == 8):
             # (round 6: on the shifted lattice too -- final sums only, additive_control_split)
-            if rs == 8 and wres and _dbg(debug, 'SDP_COL_LEAN') != '0':
+            if rs == 8 and wres:
                 short = short_pass_source(model, utab[0], 'SDP_COL_LEAN2')
                 if short and _dbg(debug, 'SDP_COL_BNB') != '0':
                     short += ('\n#define SDP_COL_BNB 1          // the short first pass as a certified branch and bound over '
                               'blocks of controls (sdp_lean2_bnb)')
 
-            elif rs == 4 and not wres and _dbg(debug, 'SDP_COL_WIDE') != '0' and _dbg(debug, 'SDP_COL_LEAN') in (None, '0') \
-                    and _dbg(debug, 'SDP_COL_FILTER_TOP2') in (None, '1'):
+            elif rs == 4 and not wres and _dbg(debug, 'SDP_COL_FILTER_TOP2') in (None, '1'):
                 short = short_pass_source(model, utab[0], 'SDP_COL_WIDE2')
                 if short and _dbg(debug, 'SDP_COL_BNB') != '0':
                     short += ('\n#define SDP_COL_BNB 1          // the short wide first pass as a certified branch and bound over '
@@ -936,7 +935,7 @@ def column_resident_points(model, n0, w, n_state, dtype, filtered, shift, wpair,
     rs = np.dtype(dtype).itemsize
     w = int(w)
     ok = (filtered and rs == 8 and not wpair and not model.cost_depends_on_w and w >= 4
-          and int(threads) >= int(n0) and _dbg(debug, 'SDP_COL_LEAN', '-1') != '0')
+          and int(threads) >= int(n0))
     forced = _dbg(debug, 'SDP_COL_WRES')
     if forced is not None:
         k = int(forced)
@@ -981,7 +980,7 @@ def column_wide_loads(n0, dtype, window, debug=None):
 
 def column_build_order(threads, w, rows, rows_per_lane=1):
     """How phase A of the column kernel deals the W x rows table entries to the threads
-    (SDP_COL_A_ORDER / SDP_COL_A_LW of csrc/sdp_column_kernel.h): (2, lanes_per_w) when the
+    (SDP_COL_A_ORDER / SDP_COL_A_LW of csrc/sdp_column_kernel.h, generated): (2, lanes_per_w) when the
     perturbation points fill the workgroup's thread groups -- a thread then keeps its w, reads
     the trailing cell once and walks the rows with constant address steps (measured on MI355X:
     256^3 x 64 x 32 fp64 -2 %, fp32 -3.5 %) -- else (0, 0): entries dealt round-robin (with 9
@@ -1029,7 +1028,7 @@ def _column_lds(tw, w, rows, n_state, rs, threads, reduced=False, shift=False, s
     part = threads if partial_minima else 1
     members = [(rs, tw * rows, 16),                          # T
                (rs, w * dt, rs), (rs, w * dt, rs),           # w_lam, w_oml
-               (rs, 1, rs), (rs, 1, rs),                     # pw, gw (SDP_COL_WMODE 2 only: not generated)
+               (rs, 2, rs),                                  # reserve_
                (rs, part, rs), (4, part, 4),                 # part_J, part_i
                (4, w * dt, 4),                               # w_off
                (4, 4, 4), (4, 1, 4), (8, 2, 8),              # win, next_unit, dcol

@@ -15,7 +15,7 @@
 //          = g sum_w p_w + oml0 A[q0] + lam0 A[q0+1],      A[r] = sum_w p_w T[w][r],
 // i.e. ONE lerp on a table reduced over w instead of W of them.  The reference's
 // value E(u) (the W x 6 separately rounded operations of sdp_col_expected_cost)
-// and the short form F(u) (sdp_col_filter_eval) are both roundings of R(u) --
+// and the short form F(u) (the first passes below) are both roundings of R(u) --
 // same q0, lam0, oml0, g and table entries, which are computed once -- so with
 // u = the unit roundoff and S(u) = sum_w |p_w| (|g| + |oml0 T[w][q0]| + |lam0 T[w][q0+1]|):
 //     |E - R| <= gamma_{W+4} S,   |F - R| <= gamma_{W+3} S,   gamma_n = n u / (1 - n u)
@@ -68,11 +68,10 @@ struct SdpColFilter {
     // branch and bound of the short first passes: rows of axis 0 per unit of x0, and what |X| + max |a| may be at most
     sdp_real k_rows, x_cap;
 };
-constexpr bool SDP_COL_LEAN_ON = SDP_COL_LEAN < 0 ? sizeof(sdp_real) == 8 : SDP_COL_LEAN != 0;
-constexpr bool SDP_COL_WIDE_ON = sizeof(sdp_real) == 4 && !SDP_COL_LEAN_ON && SDP_COL_WIDE != 0;
+// the first pass: lean for 8-byte reals, wide for 4-byte reals (see sdp_column_kernel.h)
+constexpr bool SDP_COL_LEAN_ON = sizeof(sdp_real) == 8;
+constexpr bool SDP_COL_WIDE_ON = sizeof(sdp_real) == 4;
 static_assert(!SDP_COL_SHIFT || SDP_COL_LEAN_ON, "the shifted lattice is a form of the lean first pass (8-byte reals)");
-static_assert(!SDP_COST_HAS_W || SDP_COL_LEAN_ON || SDP_COL_WIDE_ON,
-              "a cost that depends on the perturbation needs the lean / wide first pass (sdp_col_cost_expect)");
 // type of the filter values F and of the radius
 typedef std::conditional<SDP_COL_WIDE_ON, double, sdp_real>::type sdp_fkey;
 // roundings the term of perturbation point w passes through on the reference's path: the two products
@@ -171,24 +170,16 @@ SDP_DEV void sdp_col_filter_reduce(const SdpSweepArgs &a, SdpColLds &m, const Sd
         // (>= tiny / cu: the radius never drops below `tiny`; a NaN entry, which the max skips,
         // shows in acc and makes the row's bound infinite)
         const sdp_real d = acc == acc ? f.pcap * big + f.floor : (sdp_real)INFINITY;
-        if (SDP_COL_LEAN_ON) {
-            m.ad[r] = acc;
-            dmax = sdp_vmax(dmax, d);
-        } else {
-            m.ad[2 * r] = acc;
-            m.ad[2 * r + 1] = d;
-        }
+        m.ad[r] = acc;
+        dmax = sdp_vmax(dmax, d);
     }
-    if (SDP_COL_LEAN_ON) {
-        dmax = sdp_wave_max(dmax);                          // (>= 0, or +inf; never a NaN)
-        if ((threadIdx.x & 63) == 0)
-            atomicMax(&m.dcol[parity], (unsigned long long)__double_as_longlong((double)dmax));
-    }
+    dmax = sdp_wave_max(dmax);                              // (>= 0, or +inf; never a NaN)
+    if ((threadIdx.x & 63) == 0)
+        atomicMax(&m.dcol[parity], (unsigned long long)__double_as_longlong((double)dmax));
 }
 // after the barrier that follows the reduction: the column's bound; the slot of the next unit is cleared
 SDP_DEV sdp_real sdp_col_filter_dcol(SdpColLds &m, int parity)
 {
-    if (!SDP_COL_LEAN_ON && !SDP_COL_WIDE_ON) return (sdp_real)0;
     const unsigned long long bits = m.dcol[parity];
     if (sdp_col_tid() == 0) m.dcol[parity ^ 1] = sdp_col_opaque(0ull);
     return (sdp_real)__longlong_as_double((long long)bits);
@@ -397,42 +388,19 @@ SDP_DEV void sdp_col_shift_reduce(const SdpSweepArgs &a, SdpColLds &m, const Sdp
 }
 #endif  // SDP_COL_SHIFT
 
-// F(u) and S^(u) of one control (x0' cell and cost exactly as sdp_col_expected_cost computes them).
-// AXIS, a template argument so that the loop of the first pass carries no branch: 0 the true
+// AXIS of the first passes, a template argument so that their loops carry no branch: 0 the true
 // division of pyx:75; 1 a power-of-two span (product with the reciprocal: sdp_div_span); 2 the
-// axis [0, 1] (x - 0.0 and x * 1.0 are x, bit for bit).  `pmax` collects |p|: the truncation
+// axis [0, 1] (x - 0.0 and x * 1.0 are x, bit for bit).  The passes collect |p| (or |lam0|): the truncation
 // to an int has x86 semantics beyond 2^31 (sdp_trunc_i32) -- a node that gets there takes the
 // long way instead of paying for the check on every control.
-template <int AXIS>
-SDP_DEV void sdp_col_filter_eval(const sdp_real *ad_tab, const SdpColFilter &f, const SdpLeadAxis &l,
-                                 const sdp_real *x, const sdp_real *u, sdp_real t, sdp_real &F, sdp_real &S,
-                                 sdp_real &pmax)
-{
-    const sdp_real xn0 = sdp_model_lead(x, u, (sdp_real)0, t);
-    const sdp_real sn = AXIS == 2 ? xn0 : (AXIS == 1 ? (xn0 - l.smin) * l.rspan : (xn0 - l.smin) / l.span);
-    const sdp_real p = sn * l.nm1;
-    pmax = sdp_vmax(pmax, fabs(p));
-    const int q0 = max(min((int)p, l.ordm2), 0);            // (saturating conversion; NaN -> 0)
-    const sdp_real lam0 = p - (sdp_real)q0;
-    const sdp_real oml0 = (sdp_real)1 - lam0;
-    const sdp_real g = sdp_model_cost(x, u, (sdp_real)0, t);
-    const sdp_real *ad = ad_tab + 2 * q0;
-    const sdp_real a0 = ad[0], d0 = ad[1], a1 = ad[2], d1 = ad[3];
-    F = g * f.psum + (oml0 * a0 + lam0 * a1);
-    S = fma(fabs(g), f.pcap, (fabs(oml0) + fabs(lam0)) * sdp_vmax(d0, d1));
-}
 SDP_DEV int sdp_col_axis_mode(const SdpLeadAxis &l)
 {
-#ifdef SDP_COL_AXIS_MODE                                   // generated where the host knows axis 0 of the grid: one form of the passes instead of three
-    (void)l;
-    return SDP_COL_AXIS_MODE;
-#endif
     if (!l.pow2) return 0;
     return (l.smin == (sdp_real)0 && l.span == (sdp_real)1) ? 2 : 1;
 }
 
 // ---------------------------------------------------------------------------
-// Lean first pass (SDP_COL_LEAN).  Vector issue is what binds the first pass, and on gfx950
+// Lean first pass (SDP_COL_LEAN_ON).  Vector issue is what binds the first pass, and on gfx950
 // every vector instruction of a mixed stream costs ~4.2-4.4 clocks of its SIMD whatever its
 // type (profiles/r03_ubench_valu_rate.txt), so the pass is as fast as it is short.  Per control
 // it keeps only what must be per control:
@@ -757,7 +725,7 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
 #endif
 
 // ---------------------------------------------------------------------------
-// Wide first pass (SDP_COL_WIDE, 4-byte reals).  q0, lam0, oml0 = fl(1 - lam0) and g are the
+// Wide first pass (SDP_COL_WIDE_ON, 4-byte reals).  q0, lam0, oml0 = fl(1 - lam0) and g are the
 // reference's 4-byte values (inputs of E); everything after them runs in 8-byte arithmetic:
 //     F = g P + oml0 A[q0] + lam0 A[q0+1]        P, A accumulated in 8-byte reals
 // so |F - R| is of the order of the 8-byte roundoff (~1e-15 of the terms) and the radius has to
@@ -839,9 +807,6 @@ struct SdpColBounds {
     sdp_real b_max;                  // shifted lattice: the largest B' of the cells the controls fall in
     int i1, i2;
 };
-// 8-byte reals: the SUM of the S^ serves as the node's bound (no running maximum; a radius
-// U times the necessary one, ~1e-12 relative, still leaves one survivor); 4-byte reals keep the maximum
-constexpr bool SDP_COL_RADIUS_FROM_SUM = sizeof(sdp_real) == 8;
 // one more value (of control ci) into the running two / three smallest
 SDP_DEV void sdp_col_bounds_insert(SdpColBounds &b, sdp_fkey F, int ci)
 {
@@ -864,7 +829,7 @@ SDP_DEV void sdp_col_filter_pass1(const sdp_real *ad_tab, const sdp_real *utab, 
                                   int c_lo, int c_hi, SdpColBounds &b)
 {
 #if SDP_COL_UTAB
-    if (SDP_COL_LEAN_ON || SDP_COL_WIDE_ON) {
+    {
         (void)box;
         auto one = [&](int ci) {
             sdp_fkey F;
@@ -894,7 +859,6 @@ SDP_DEV void sdp_col_filter_pass1(const sdp_real *ad_tab, const sdp_real *utab, 
 #endif
     (void)utab;
     auto eval = [&](int ci, const sdp_real *u) {
-        sdp_real F, S;
         if (SDP_COL_WIDE_ON) {
             double Fw;
             sdp_real bound;
@@ -904,15 +868,10 @@ SDP_DEV void sdp_col_filter_pass1(const sdp_real *ad_tab, const sdp_real *utab, 
             sdp_col_bounds_insert(b, (sdp_fkey)Fw, ci);
             return;
         }
-        if (SDP_COL_LEAN_ON) {
-            // (p_max holds the largest |lam0|, s_sum the sum of the |F|: see sdp_col_lean_eval)
-            sdp_col_lean_eval<AXIS>(ad_tab, f, l, x, u, t, F, b.p_max, b.s_max, b.b_max);
-            b.s_sum = b.s_sum + fabs(F);
-        } else {
-            sdp_col_filter_eval<AXIS>(ad_tab, f, l, x, u, t, F, S, b.p_max);
-            b.s_sum = b.s_sum + S;
-            if (!SDP_COL_RADIUS_FROM_SUM) b.s_max = sdp_vmax(b.s_max, S);
-        }
+        // (p_max holds the largest |lam0|, s_sum the sum of the |F|: see sdp_col_lean_eval)
+        sdp_real F;
+        sdp_col_lean_eval<AXIS>(ad_tab, f, l, x, u, t, F, b.p_max, b.s_max, b.b_max);
+        b.s_sum = b.s_sum + fabs(F);
         sdp_col_bounds_insert(b, F, ci);
     };
     auto one = [&](int ci) {
@@ -1248,7 +1207,7 @@ SDP_DEV void sdp_col_bounds_merge(SdpColBounds &b, int d)
 
 
 // Phase B with the filter for the nodes i_lo .. i_hi-1 of column `col`, by the `waves` waves
-// that call it (this one is number `wave`); `ad_tab` = the (A[r], D[r]) pairs, s.T the table.
+// that call it (this one is number `wave`); `ad_tab` = the reduced table, s.T the table.
 // A wave takes 64 / chunks consecutive nodes; the lanes l, l + npw, l + 2 npw, .. of a node
 // share its control lattice in `chunks` consecutive ranges and meet through lane shuffles.
 // Lanes past the end of the unit repeat its last node (they must stay active for the
@@ -1371,9 +1330,6 @@ SDP_DEV void sdp_col_filter_nodes(const SdpSweepArgs &a, const SdpGrid<sdp_real,
         bd.s_max = bd.s_sum = bd.p_max = bd.b_max = (sdp_real)0;
         bd.i1 = bd.i2 = INT_MAX;
         const bool plain = SDP_NU == 1 && box.n[0] > 1 && box.step[0] != (sdp_real)0;
-#ifdef SDP_DIAG_NO_PASS1
-        if (t == (sdp_real)123.456)
-#endif
         if (__all(plain)) {
             if (axis_mode == 2) sdp_col_filter_pass1<true, 2>(ad_tab, utab, filt, lead1, box, x, t, c_lo, c_hi, bd);
             else if (axis_mode == 1) sdp_col_filter_pass1<true, 1>(ad_tab, utab, filt, lead1, box, x, t, c_lo, c_hi, bd);
@@ -1399,7 +1355,7 @@ SDP_DEV void sdp_col_filter_nodes(const SdpSweepArgs &a, const SdpGrid<sdp_real,
                   !(bd.p_max < (sdp_real)2147483648.0) ||
                   !(((sdp_real)1 + (sdp_real)2 * bd.p_max) * dcol < SDP_COL_FILTER_LIMIT);
             radius = (sdp_fkey)(SDP_COL_FILTER_SCALE) * (sdp_fkey)(1.001 * 0x1p-24) * ((sdp_fkey)bd.s_max + (sdp_fkey)filt.floor);
-        } else if (SDP_COL_LEAN_ON) {
+        } else {
 #if SDP_COL_SHIFT
             // H D, H = (1 + 2 L + 2 Lc) (3 + Es): see sdp_col_shift_reduce
             const sdp_real h_cap = (((sdp_real)1 + (sdp_real)2 * (bd.p_max + shc.lc)) * ((sdp_real)3 + shc.es)) * dcol;
@@ -1419,9 +1375,6 @@ SDP_DEV void sdp_col_filter_nodes(const SdpSweepArgs &a, const SdpGrid<sdp_real,
             bad = !filt.ok || !(s_node < SDP_COL_FILTER_LIMIT) || !(bd.p_max < (sdp_real)1073741824.0);
             radius = filt.cu * s_node;
 #endif
-        } else {
-            bad = !filt.ok || !(bd.s_sum < SDP_COL_FILTER_LIMIT) || !(bd.p_max < (sdp_real)2147483648.0);
-            radius = filt.cu * (SDP_COL_RADIUS_FROM_SUM ? (sdp_real)bd.s_sum : bd.s_max);
         }
 #endif  // SDP_COL_WIDE2
         const sdp_fkey m_hi = bd.f1 + radius;                  // >= the minimum of E over the node
@@ -1437,9 +1390,6 @@ SDP_DEV void sdp_col_filter_nodes(const SdpSweepArgs &a, const SdpGrid<sdp_real,
         }
         sdp_real best = INFINITY;
         int ibest = INT_MAX;
-#ifdef SDP_DIAG_NO_PASS2
-        if (bd.f1 == (sdp_real)123.456)
-#endif
         for (int ci = first; ci < last; ci += stride) {
             sdp_real u[1][SDP_NU], jc[1];
             sdp_controls_at(box, ci, u[0]);
@@ -1458,14 +1408,9 @@ SDP_DEV void sdp_col_filter_nodes(const SdpSweepArgs &a, const SdpGrid<sdp_real,
                 else sdp_col_wide_eval<0>(ad_tab, filt, lead, x, u[0], t, Fw, bnd, pm);
                 cand = !((sdp_fkey)Fw - radius > m_hi);
             } else if (!cand) {
-                sdp_real F, S;
-                sdp_real pm = (sdp_real)0;
-                if (SDP_COL_LEAN_ON) {
-                    sdp_real gm = (sdp_real)0, bm = (sdp_real)0;
-                    if (lead.pow2) sdp_col_lean_eval<1>(ad_tab, filt, lead1, x, u[0], t, F, pm, gm, bm);
-                    else sdp_col_lean_eval<0>(ad_tab, filt, lead1, x, u[0], t, F, pm, gm, bm);
-                } else if (lead.pow2) sdp_col_filter_eval<1>(ad_tab, filt, lead, x, u[0], t, F, S, pm);
-                else sdp_col_filter_eval<0>(ad_tab, filt, lead, x, u[0], t, F, S, pm);
+                sdp_real F, pm = (sdp_real)0, gm = (sdp_real)0, bm = (sdp_real)0;
+                if (lead.pow2) sdp_col_lean_eval<1>(ad_tab, filt, lead1, x, u[0], t, F, pm, gm, bm);
+                else sdp_col_lean_eval<0>(ad_tab, filt, lead1, x, u[0], t, F, pm, gm, bm);
                 cand = !(F - radius > m_hi);
             }
 #endif

@@ -27,7 +27,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
     SdpColWalk walk;
     sdp_col_walk(a, walk);
     SdpColWeights wts;
-    sdp_col_load_weights(a, wts, sdp_lds.pw, sdp_lds.gw);
+    sdp_col_load_weights(a, wts);
 #if SDP_COL_FILTER
     SdpColFilter filt;
     sdp_col_filter_setup(a, filt);
@@ -69,21 +69,19 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
 #if SDP_COL_UTAB
     sdp_trap_unless(!a.box_per_node);                      // (and SDP_COL_UTAB_N controls: sdp_meta, checked by the host)
 #endif
-    // what stays the same from unit to unit (SDP_COL_HOIST)
+    // what stays the same from unit to unit (hoisted: see sdp_column_kernel.h)
     SdpBox box_hold;
     const SdpBox *box_c = nullptr;
     const sdp_real *w_mine = nullptr;
     sdp_real w_hold = (sdp_real)0, x0_pre = (sdp_real)0;
     int i_pre = -1;
-    if (SDP_COL_HOIST) {
-        if (!a.box_per_node) { sdp_load_box(a, 0, box_hold); box_c = &box_hold; }
+    if (!a.box_per_node) { sdp_load_box(a, 0, box_hold); box_c = &box_hold; }
 #if SDP_HAS_W
-        if (lane < Wn) { w_hold = ((const sdp_real *)a.wgrid)[lane]; w_mine = &w_hold; }
+    if (lane < Wn) { w_hold = ((const sdp_real *)a.wgrid)[lane]; w_mine = &w_hold; }
 #endif
-        if (a.col_splits == 1 && N0 <= (int)blockDim.x && (int)threadIdx.x < N0) {     // one lane per node, whole columns:
-            i_pre = (int)threadIdx.x;                                                   // this thread's node never changes
-            x0_pre = axis0[i_pre];
-        }
+    if (a.col_splits == 1 && N0 <= (int)blockDim.x && (int)threadIdx.x < N0) {     // one lane per node, whole columns:
+        i_pre = (int)threadIdx.x;                                                   // this thread's node never changes
+        x0_pre = axis0[i_pre];
     }
     if (unit < u_end) {                                    // trailing cells of the first unit
         sdp_real xn[SDP_D];
@@ -325,7 +323,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS) sdp_evalpol_col(Sd
     SdpColWalk walk;
     sdp_col_walk(a, walk);
     SdpColWeights wts;
-    sdp_col_load_weights(a, wts, sdp_lds.pw, sdp_lds.gw);
+    sdp_col_load_weights(a, wts);
     if (SDP_COL_WINDOW && threadIdx.x < 4) sdp_lds.win[threadIdx.x >> 1][threadIdx.x & 1] = INT_MAX;
     int parity = 0;
     for (int64_t unit = walk.unit; unit < walk.end; unit += walk.stride) {

@@ -36,31 +36,18 @@ static_assert(!SDP_COL_TOP2 || SDP_COL_SHIFT, "resident chunks: two carried surv
 static_assert(SDP_COL_WRES >= 1 && 2 * SDP_COL_WRES >= SDP_COL_W, "resident chunks: at least half of the points resident");
 constexpr int SDP_COLRES_K = SDP_COL_TOP2 ? 2 : 1;        // survivors a lane can carry through the rebuild of the tail
 
-// SDP_COL_TAIL_KEEP (round 6): the tail is built ONCE.  Its first build also stores the entries to a block of global memory
-// private to the workgroup (SdpSweepArgs.tail: (W - C) x N0 reals, rewritten every column, so it lives in L2 / the Infinity
-// Cache), and the second pass reads the survivor's T[w][q0], T[w][q0+1], w = C .. W-1, back from there: 2 (W - C) coalesced
-// 8-byte loads per node (neighbouring lanes: neighbouring rows) in place of (W - C) N0 / threads rebuilt entries per thread
-// (4 strip loads and 9 operations each) and the two barriers around them.  The entries are the reference's values either
-// way -- the same SdpColNest on the same operands -- so nothing changes in J, policy or index.  A workgroup's waves run on
-// one CU and share its vector L1 (write-through), and every build is followed by a workgroup barrier before anything reads:
-// the block needs no fence beyond __syncthreads().
-#ifndef SDP_COL_TAIL_KEEP
-#define SDP_COL_TAIL_KEEP 0
-#endif
-#if SDP_COL_TAIL_KEEP && (SDP_COL_SHIFT || !SDP_COL_A_WIDE_LOADS || SDP_COL_A_ORDER != 2 || SDP_COL_WPAIR)
-#error "SDP_COL_TAIL_KEEP: the plain resident-chunk kernel with 16-byte build loads"
-#endif
 // SDP_COL_TAIL_HOLD (round 6): the tail is built ONCE and its entries stay IN REGISTERS.  The thread that computes
 // T[w][r .. r+1], w >= C, in the first build of the tail keeps them -- (W - C) N0 / threads entries, 32 registers at
 // 16 x 256 / 256 -- through the first pass and the second pass over the head, and writes them back into the table where
 // the rebuild of the tail used to be: no strip loads (a third of the kernel's vector-memory instructions), no
 // interpolation (9 operations per entry), the same values by construction.  The registers are what it costs: the
 // kernel no longer fits the 128 of four waves per SIMD, so such a build asks for three (168 registers; the LDS image
-// still admits four workgroups per CU, the register file three).
+// still admits four workgroups per CU, the register file three).  (A copy of the tail in a block of global memory per
+// workgroup, read back by the second pass, was measured in the same round and gained nothing: 1.239 ms against 1.235.)
 #ifndef SDP_COL_TAIL_HOLD
 #define SDP_COL_TAIL_HOLD 0
 #endif
-#if SDP_COL_TAIL_HOLD && (!SDP_COL_A_WIDE_LOADS || SDP_COL_A_ORDER != 2 || SDP_COL_WPAIR || SDP_COL_TAIL_KEEP || \
+#if SDP_COL_TAIL_HOLD && (!SDP_COL_A_WIDE_LOADS || SDP_COL_A_ORDER != 2 || SDP_COL_WPAIR || \
                           (SDP_COL_W - SDP_COL_WRES) % (SDP_COL_THREADS / SDP_COL_A_LW) != 0 || SDP_COL_ROWS % (2 * SDP_COL_A_LW) != 0)
 #error "SDP_COL_TAIL_HOLD: the plain resident-chunk kernel with 16-byte build loads, whole rounds of points and rows"
 #endif
@@ -130,7 +117,6 @@ SDP_DEV void sdp_colres_tail(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
 #ifndef SDP_DIAG_SKIP
 #define SDP_DIAG_SKIP 0
 #endif
-#define SDP_COLRES_TAIL_BYTES (SDP_COL_TAIL_KEEP ? (SDP_COL_W - SDP_COL_WRES) * SDP_COL_ROWS * (int)sizeof(sdp_real) : 0)
 
 // cell of x0' along axis 0 of one control for the perturbation point value `wv`, as sdp_col_expected_cost computes it (pyx:75-81)
 SDP_DEV void sdp_colres_cell(const SdpLeadAxis &l, const sdp_real *x, const sdp_real *u, sdp_real wv, sdp_real t,
@@ -197,50 +183,6 @@ SDP_DEV void sdp_colres_partial(const sdp_real *T, const SdpColWeights &k, const
             }
     }
 }
-
-#if SDP_COL_TAIL_KEEP
-// sdp_colres_partial<1> for the points [w_lo, w_hi) with the table rows read from the workgroup's block of global
-// memory (row w - w_lo of `G`): the loads of SDP_COL_KEEP_BATCH points are in flight together.
-#ifndef SDP_COL_KEEP_BATCH
-#define SDP_COL_KEEP_BATCH 8
-#endif
-#ifndef SDP_COL_KEEP_LOADS
-#define SDP_COL_KEEP_LOADS 0
-#endif
-SDP_DEV void sdp_colres_partial_kept(const sdp_real *__restrict__ G, const SdpColWeights &k, const int w_lo, const int w_hi,
-                                     SdpColresCand &c)
-{
-    constexpr int N0 = SDP_COL_ROWS;
-    constexpr int B = SDP_COL_KEEP_BATCH;
-    const sdp_real *__restrict__ g0 = G + c.q0[0];
-#pragma unroll
-    for (int w0 = w_lo; w0 < w_hi; w0 += B) {
-        sdp_real lo[B], hi[B];
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-            if (w0 + b < w_hi) {
-#if SDP_COL_KEEP_LOADS == 1          // plain loads
-                lo[b] = g0[(w0 + b - w_lo) * N0];
-                hi[b] = g0[(w0 + b - w_lo) * N0 + 1];
-#elif SDP_COL_KEEP_LOADS == 2        // past the vector L1 (sc1)
-                lo[b] = __hip_atomic_load(g0 + (w0 + b - w_lo) * N0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                hi[b] = __hip_atomic_load(g0 + (w0 + b - w_lo) * N0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-                lo[b] = __builtin_nontemporal_load(g0 + (w0 + b - w_lo) * N0);
-                hi[b] = __builtin_nontemporal_load(g0 + (w0 + b - w_lo) * N0 + 1);
-#endif
-            }
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-            if (w0 + b < w_hi) {
-                const sdp_real pw = SDP_COL_PW(k, w0 + b);
-                const sdp_real val = c.oml0[0] * lo[b] + c.lam0[0] * hi[b];            // pyx:88-300
-                const sdp_real jc = c.g[0] + val;                                      // stodynprog.py:677
-                c.acc[0] = c.acc[0] + jc * pw;                                         // stodynprog.py:681, w order
-            }
-    }
-}
-#endif
 
 #if SDP_COL_LEAN2
 // ---------------------------------------------------------------------------
@@ -420,14 +362,9 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
     SdpColWalk walk;
     sdp_col_walk(a, walk);
     SdpColWeights wts;
-    sdp_col_load_weights(a, wts, sdp_lds.pw, sdp_lds.gw);
+    sdp_col_load_weights(a, wts);
     SdpColFilter filt;
     sdp_col_filter_setup(a, filt);
-#if SDP_COL_TAIL_KEEP
-    sdp_real *__restrict__ kept = (sdp_real *)((char *)a.tail + (size_t)blockIdx.x * (size_t)SDP_COLRES_TAIL_BYTES);
-#else
-    sdp_real *kept = nullptr;
-#endif
     const int axis_mode = __builtin_amdgcn_readfirstlane(sdp_col_axis_mode(lead));
     const sdp_cst_real *pw = (const sdp_cst_real *)a.proba;
     // (what is the same in every lane for the whole kernel lives in scalar registers: sdp_uniform)
@@ -461,26 +398,24 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
 #if SDP_COL_UTAB
     sdp_trap_unless(!a.box_per_node);
 #endif
-    // what stays the same from unit to unit (SDP_COL_HOIST)
+    // what stays the same from unit to unit (hoisted: see sdp_column_kernel.h)
     SdpBox box_hold;
     const SdpBox *box_c = nullptr;
     const sdp_real *w_mine = nullptr;
     sdp_real w_hold = (sdp_real)0;
-    if (SDP_COL_HOIST) {
-        if (!a.box_per_node) {
-            sdp_load_box(a, 0, box_hold);
+    if (!a.box_per_node) {
+        sdp_load_box(a, 0, box_hold);
 #pragma unroll
-            for (int c = 0; c < SDP_NU; ++c) {
-                box_hold.lo[c] = sdp_uniform(box_hold.lo[c]); box_hold.hi[c] = sdp_uniform(box_hold.hi[c]);
-                box_hold.step[c] = sdp_uniform(box_hold.step[c]); box_hold.delta[c] = sdp_uniform(box_hold.delta[c]);
-                box_hold.n[c] = sdp_uniform(box_hold.n[c]);
-            }
-            box_hold.total = sdp_uniform(box_hold.total);
-            box_c = &box_hold;
+        for (int c = 0; c < SDP_NU; ++c) {
+            box_hold.lo[c] = sdp_uniform(box_hold.lo[c]); box_hold.hi[c] = sdp_uniform(box_hold.hi[c]);
+            box_hold.step[c] = sdp_uniform(box_hold.step[c]); box_hold.delta[c] = sdp_uniform(box_hold.delta[c]);
+            box_hold.n[c] = sdp_uniform(box_hold.n[c]);
         }
-        // (the held tail has no registers to spare for it: phase W loads the point where it uses it)
-        if (lane < Wn && !SDP_COL_TAIL_HOLD) { w_hold = ((const sdp_real *)a.wgrid)[lane]; w_mine = &w_hold; }
+        box_hold.total = sdp_uniform(box_hold.total);
+        box_c = &box_hold;
     }
+    // (the held tail has no registers to spare for it: phase W loads the point where it uses it)
+    if (lane < Wn && !SDP_COL_TAIL_HOLD) { w_hold = ((const sdp_real *)a.wgrid)[lane]; w_mine = &w_hold; }
 #if SDP_COL_SHIFT
     if (threadIdx.x < 2) sdp_col_shift_reset(sdp_lds, threadIdx.x);
     __syncthreads();
@@ -522,7 +457,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
         sdp_held_rows held[SDP_HOLD_NW][SDP_HOLD_NJ];
         sdp_colres_tail<true>(a, tg, s, held);
 #else
-        if (!(SDP_DIAG_SKIP & 1)) sdp_col_phase_a<false>(a, tg, s, C, R, kept);
+        if (!(SDP_DIAG_SKIP & 1)) sdp_col_phase_a<false>(a, tg, s, C, R);
 #endif
         __syncthreads();
 #if SDP_COL_SHIFT
@@ -804,14 +739,6 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
         if (SDP_DIAG_SKIP & 8) {}
         else if (SDP_COLRES_K > 1 && two) sdp_colres_partial<SDP_COLRES_K>(sdp_lds.T, wts, lead, x, t, 0, C, 0, cd);
         else if (cd.n) sdp_colres_partial<1>(sdp_lds.T, wts, lead, x, t, 0, C, 0, cd);
-#if SDP_COL_TAIL_KEEP
-        // ---- second pass over the tail, from the copy its first build left in global memory (no barrier: the table
-        // is not touched again before the top of the next unit)
-        if (cd.n) sdp_colres_partial_kept(kept, wts, C, Wn, cd);
-#ifdef SDP_DIAG_KEEP_BARRIER
-        __syncthreads();
-#endif
-#else
         __syncthreads();                                   // the head has been read
         // ---- the tail again, second pass over it
         __builtin_amdgcn_s_setprio(0);
@@ -825,7 +752,6 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
         if (SDP_DIAG_SKIP & 32) {}
         else if (SDP_COLRES_K > 1 && two) sdp_colres_partial<SDP_COLRES_K>(sdp_lds.T, wts, lead, x, t, C, Wn, C, cd);
         else if (cd.n) sdp_colres_partial<1>(sdp_lds.T, wts, lead, x, t, C, Wn, C, cd);
-#endif
         if (live) {
             // the carried survivors in lattice order, compared like the reference compares
 #pragma unroll
@@ -903,7 +829,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS) sdp_evalpol_col(Sd
     SdpColWalk walk;
     sdp_col_walk(a, walk);
     SdpColWeights wts;
-    sdp_col_load_weights(a, wts, sdp_lds.pw, sdp_lds.gw);
+    sdp_col_load_weights(a, wts);
     for (int64_t unit = walk.unit; unit < walk.end; unit += walk.stride) {
         const int64_t col = sdp_col_of_unit(a, unit);
         const int part = (int)((unsigned)unit % (unsigned)a.col_splits);      // (32-bit: units < 2^31)

@@ -141,7 +141,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
     SdpColWalk walk;
     sdp_col_walk(a, walk);
     SdpColWeights k;
-    sdp_col_load_weights(a, k, sdp_lds.pw, sdp_lds.gw);
+    sdp_col_load_weights(a, k);
     const volatile sdp_lds_real *T = (const volatile sdp_lds_real *)s.T;
 
     // units of this XCD's share, claimed in order (see sdp_col_of_unit): neighbouring columns at

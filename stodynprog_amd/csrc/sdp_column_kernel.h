@@ -40,7 +40,7 @@
 //   SDP_COST_HAS_W                   0: g is hoisted out of the w loop
 //   SDP_COL_FILTER                   1: certified expectation-first filter in phase B (SdpColFilter below):
 //                                    a first pass over every control on a table reduced over w -- lean
-//                                    (SDP_COL_LEAN, 8-byte reals) or wide (SDP_COL_WIDE, 4-byte reals) --
+//                                    (8-byte reals) or wide (4-byte reals) --
 //                                    and the reference's operations on the survivors only; same bits
 //   SDP_COL_UTAB (+ _N)              K > 0: sdp_model_utab / sdp_model_lead_tab / sdp_model_cost_tab are
 //                                    provided too: the K sub-expressions of x0' and of the cost that depend
@@ -74,8 +74,8 @@
 #define SDP_COL_A_GROUP 4        // table entries per thread whose vertex loads are issued together
 #endif
 #ifndef SDP_COL_A_ORDER
-#define SDP_COL_A_ORDER 0        // table build: 0 entries dealt round-robin; 1 a thread keeps its row and takes
-#endif                           //   consecutive w; 2 a thread keeps its w (SDP_COL_A_LW lanes per w) and walks the rows
+#define SDP_COL_A_ORDER 0        // table build: 0 entries dealt round-robin; 2 a thread keeps its w (SDP_COL_A_LW lanes
+#endif                           //   per w) and walks the rows (generated: codegen.column_build_order)
 #ifndef SDP_COL_A_LW
 #define SDP_COL_A_LW 16
 #endif
@@ -139,28 +139,20 @@
 // pass and the control table: 2 -> 2.05 ms, 4 -> 1.94, 8 -> 1.89, 16 -> 1.90; 4-byte reals keep 4
 #define SDP_COL_FILTER_UNROLL (sizeof(SDP_REAL) == 8 ? 8 : 4)
 #endif
-#ifndef SDP_COL_B_PRIO
 #define SDP_COL_B_PRIO 3         // wave priority (s_setprio) while in phase B
-#endif
 #ifndef SDP_COL_FILTER_RUNROLL
 #define SDP_COL_FILTER_RUNROLL 16   // table entries in flight per thread in the reduction over w
 #endif
-#ifndef SDP_COL_LEAN
-// Lean first pass of the filter (8-byte reals by default): ONE error bound per node -- from the
+// Lean first pass of the filter (8-byte reals, SDP_COL_LEAN_ON of sdp_colfilter_kernel.h): ONE error bound per node -- from the
 // largest |lam0| and the sum of the |F| of its controls and a bound D of the whole column -- instead
 // of one per control, F as two fused multiply-adds on a table of A[r] alone.  See SdpColFilter.
-#define SDP_COL_LEAN -1          // -1: for 8-byte reals; 0 / 1 force it (A/B runs)
-#endif
-#ifndef SDP_COL_WIDE
-// Wide first pass for 4-byte reals: F in 8-byte arithmetic on a table of A[r] accumulated in 8-byte
+// Wide first pass for 4-byte reals (SDP_COL_WIDE_ON): F in 8-byte arithmetic on a table of A[r] accumulated in 8-byte
 // reals -- its own error is negligible, so the radius only has to cover the reference's W x 6
 // roundings -- and a bound per control that follows those roundings term by term (position-weighted:
 // a term added at step w passes through W - w + 4 roundings, not W + 4) with the actual |T[w][r]|
 // instead of their maximum.  In 4-byte reals the radius is what decides how many nodes keep a
 // second control (5 % at first, more and more as the cost-to-go grows over a chain of sweeps), i.e.
 // how often the long way runs twice: see SdpColWide.
-#define SDP_COL_WIDE -1          // -1: for 4-byte reals; 0 / 1 force it off / on (A/B runs; needs 4-byte reals)
-#endif
 #ifndef SDP_COL_UTAB
 // K > 0: the generated unit provides sdp_model_utab / sdp_model_lead_tab / sdp_model_cost_tab
 // (codegen.control_table_source): the K sub-expressions of x0' and of the cost that depend on the
@@ -224,9 +216,6 @@
 #endif
 constexpr bool SDP_LEAN2_A_FIXED_ON = SDP_LEAN2_A_FIXED && SDP_COL_BNB;
 constexpr int sdp_bnb_block(int n) { int b = 8; while ((n + b - 1) / b > 64) b *= 2; return b; }
-#ifndef SDP_COL_LDS_PAD
-#define SDP_COL_LDS_PAD 0        // diagnostic builds: unused bytes in the LDS image (fewer workgroups per CU: occupancy A/B)
-#endif
 // This thread's index, as the building blocks of a unit see it.  In the held-tail form (SDP_COL_TAIL_HOLD of
 // sdp_colres_kernel.h) 32 registers of table entries stay live through most of a unit, and the optimiser hoisted
 // what every building block derives from the index alone -- LDS and table addresses, row and lane numbers -- out of
@@ -244,14 +233,11 @@ SDP_DEV T sdp_col_opaque(T v)
     return v;
 }
 SDP_DEV int sdp_col_tid() { return sdp_col_opaque((int)threadIdx.x); }
-#ifndef SDP_COL_HOIST
-// 1: what does not change from unit to unit is fetched ONCE per workgroup instead of once per unit -- the control
+// What does not change from unit to unit is fetched ONCE per workgroup instead of once per unit -- the control
 // box of a constant-box problem (its loads and the division of numpy.linspace's step sat at the head of every
 // first pass and of every control table), the perturbation point of a helper thread, the axis-0 coordinate of a
 // thread's node: global-memory round trips behind the co-resident workgroup's table build, each followed by a
-// dependent chain, several times per unit.  0: as in round 3 (A/B runs)
-#define SDP_COL_HOIST 1
-#endif
+// dependent chain, several times per unit ("hoisted" in the kernels' comments).
 #if SDP_COL_FILTER && (!SDP_HAS_W || (SDP_LEAD_HAS_W && !SDP_COL_SHIFT) || SDP_TRAIL_HAS_U || SDP_COL_ROWS < SDP_COL_N0)
 #error "SDP_COL_FILTER needs a perturbation that reaches x0' through a final sum at most, and the plain full-column table"
 #endif
@@ -272,9 +258,6 @@ constexpr int SDP_DT = SDP_D - 1;
 // rows of the LDS table: perturbation points, rounded up to whole pairs for the pair layout
 constexpr int SDP_COL_TW = SDP_COL_WPAIR ? (SDP_COL_W + 1) / 2 * 2 : SDP_COL_W;
 
-#ifndef SDP_COL_WMODE
-#define SDP_COL_WMODE 1          // where the inner loop takes the perturbation weights from: see SdpColWeights
-#endif
 struct SdpColShared {
     sdp_real *T;        // [Wn][N0]
     int *w_off;         // [Wn][SDP_DT]   M[k]*q[k] of the trailing cell (x N0)
@@ -290,9 +273,8 @@ struct SdpColShared {
 #define SDP_COL_WCHUNK SDP_COL_W     // per-control table only: perturbation points tabulated at a time
 #endif
 // (members a build does not use shrink to one element: the image decides how many workgroups share a CU)
-constexpr int SDP_COL_LDS_WCOPY = SDP_COL_WMODE == 2 ? SDP_COL_W : 1;
 constexpr int SDP_COL_LDS_PART = (SDP_COL_FILTER || SDP_TRAIL_HAS_U) ? 1 : SDP_COL_THREADS;
-// reals per row of the reduced table: A[r] alone in the lean form, (A[r], D[r]) otherwise, 16 bytes for 4-byte reals
+// reals per row of the reduced table: A[r] alone in the lean form, (A'[k], B'[k]) on the shifted lattice, 16 bytes for 4-byte reals
 constexpr int SDP_BNB_BLOCK = sdp_bnb_block(SDP_COL_UTAB_N);
 constexpr int SDP_BNB_BLOCKS = (SDP_COL_UTAB_N + SDP_BNB_BLOCK - 1) / SDP_BNB_BLOCK;
 constexpr int SDP_BNB_WORDS = SDP_COL_UTAB ? 4 * (SDP_BNB_BLOCKS + 1) : 0;      // (a record of 16 bytes per block and one for the end of the lattice: 4 x 4-byte or 2 x 8-byte reals)
@@ -301,13 +283,12 @@ constexpr int SDP_BNB_WORDS = SDP_COL_UTAB ? 4 * (SDP_BNB_BLOCKS + 1) : 0;      
 // of config 5 were bank conflicts, profiles/r05_synth512f32_summary.txt)
 #define SDP_AD_A(ad, r) (SDP_COL_WIDE2 ? ((double *)(ad))[(r)] : *(double *)((ad) + 4 * (r)))
 #define SDP_AD_A_CONST(ad, r) (SDP_COL_WIDE2 ? ((const double *)(ad))[(r)] : *(const double *)((ad) + 4 * (r)))
-constexpr int SDP_COL_LDS_AD = sizeof(SDP_REAL) == 4 ? 4 : ((SDP_COL_LEAN != 0 && !SDP_COL_SHIFT) ? 1 : 2);
+constexpr int SDP_COL_LDS_AD = sizeof(SDP_REAL) == 4 ? 4 : (!SDP_COL_SHIFT ? 1 : 2);
 struct __attribute__((aligned(16))) SdpColLds {
     sdp_real T[(SDP_TRAIL_HAS_U ? SDP_COL_WCHUNK : (SDP_COL_WRES < SDP_COL_W ? SDP_COL_WRES : SDP_COL_TW)) * SDP_COL_ROWS];
     sdp_real w_lam[SDP_COL_W * SDP_DT];
     sdp_real w_oml[SDP_COL_W * SDP_DT];
-    sdp_real pw[SDP_COL_LDS_WCOPY];        // weight / point copies (SDP_COL_WMODE 2)
-    sdp_real gw[SDP_COL_LDS_WCOPY];
+    sdp_real reserve_[2];                  // unused: the members behind it keep their offsets
     sdp_real part_J[SDP_COL_LDS_PART];     // partial minima of the control chunks (unfiltered sweep)
     int part_i[SDP_COL_LDS_PART];
     int w_off[SDP_COL_W * SDP_DT];
@@ -318,11 +299,8 @@ struct __attribute__((aligned(16))) SdpColLds {
     // (+ 4: statistics of the column's table for the short first pass, SDP_COL_LEAN2 -- sdp_col_phase_u)
     // (+ 4 per block of controls: statistics of the blocks for the branch and bound of the short first pass)
     sdp_real utab[2][SDP_COL_UTAB ? SDP_COL_UTAB * SDP_COL_UTAB_N + 4 + SDP_BNB_WORDS : 2] __attribute__((aligned(16)));
-#if SDP_COL_LDS_PAD
-    char pad_[SDP_COL_LDS_PAD];
-#endif
 #if SDP_COL_FILTER
-    // filter: per row r of axis 0 the pair (A[r], D[r]) = (sum_w p_w T[w][r], Pcap max_w |T[w][r]|)
+    // filter: per row r of axis 0 A[r] = sum_w p_w T[w][r] (shifted lattice: the pair (A'[k], B'[k]) per position)
     // (wide first pass of 4-byte reals: 16 bytes per row -- A[r] as a double, then the bound B[r])
     sdp_real ad[SDP_COL_LDS_AD * (SDP_COL_SHIFT ? SDP_COL_SHIFT_ROWS : SDP_COL_ROWS)] __attribute__((aligned(16)));
 #endif
@@ -456,11 +434,7 @@ SDP_DEV void sdp_col_phase_w(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
 #pragma unroll
         for (int k = 0; k < SDP_DT; ++k) {
             sdp_locate_axis<sdp_real, SDP_DT, sdp_real>(tg, k, xn[k + 1], c);
-#ifdef SDP_DIAG_SAME_CELL      // timing diagnostic (WRONG results): every perturbation point reads the strips of one cell
-            s.w_off[w * SDP_DT + k] = 0;
-#else
             s.w_off[w * SDP_DT + k] = c.off[k];
-#endif
             s.w_lam[w * SDP_DT + k] = c.lam[k];
             s.w_oml[w * SDP_DT + k] = c.oml[k];
         }
@@ -505,12 +479,10 @@ SDP_DEV double sdp_wave_sum(double v) { return __ockl_wfred_add_f64(v); }
 SDP_DEV float sdp_wave_sum(float v) { return __ockl_wfred_add_f32(v); }
 
 // (w_begin, w_count: the perturbation points to tabulate, into table rows 0 .. w_count-1 -- all of them by
-// default; the resident-chunk kernel builds the table a part at a time; `keep`: a copy of the entries in global
-// memory, same layout -- SDP_COL_TAIL_KEEP of sdp_colres_kernel.h, 16-byte build loads only)
+// default; the resident-chunk kernel builds the table a part at a time)
 template <bool SHIFT = false>
 SDP_DEV void sdp_col_phase_a(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_DT> &tg,
-                             const SdpColShared &s, const int w_begin = 0, const int w_count = SDP_COL_W,
-                             sdp_real *__restrict__ keep = nullptr)
+                             const SdpColShared &s, const int w_begin = 0, const int w_count = SDP_COL_W)
 {
     constexpr int N0 = SDP_COL_ROWS;        // rows held by the table (the whole axis without a window)
     const int Wn = w_begin + w_count;       // one past the last point
@@ -582,7 +554,6 @@ SDP_DEV void sdp_col_phase_a(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
                         for (int c = 0; c < RPL; ++c) s.T[((tw >> 1) * N0 + r + c) * 2 + (tw & 1)] = e[c];
 #else
                         *(sdp_rows *)(s.T + tw * N0 + r) = e;
-                        if (keep) *(sdp_rows *)(keep + tw * N0 + r) = e;
 #endif
                     }
                 }
@@ -595,11 +566,7 @@ SDP_DEV void sdp_col_phase_a(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
 #pragma unroll
             for (int j = 0; j < G; ++j) {
                 const int r = min((j0 + j) * LW + rl, N0 - 1);           // clamp: result unused
-#ifdef SDP_DIAG_NO_A_LOADS
-                for (int q = 0; q < NV; ++q) vals[j][q] = (sdp_real)(r + q);
-#else
                 SdpColGather<0>::run(V + r, tg, off, 0, vals[j]);
-#endif
             }
 #pragma unroll
             for (int j = 0; j < G; ++j) {
@@ -607,49 +574,6 @@ SDP_DEV void sdp_col_phase_a(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
                 if (r < N0) {
                     const sdp_real val = SdpColNest<0, SHIFT>::run(vals[j], lam, oml, tg.shift);
                     const sdp_real entry = val;
-#if SDP_COL_WPAIR
-                    s.T[((tw >> 1) * N0 + r) * 2 + (tw & 1)] = entry;
-#else
-                    s.T[tw * N0 + r] = entry;
-#endif
-                }
-            }
-        }
-    }
-#elif SDP_COL_A_ORDER == 1
-    // a thread keeps its row r and takes G CONSECUTIVE perturbation points per round:
-    // neighbouring points share part of their 2^(d-1) vertex strips (the cell of an
-    // exogenous process moves by about one grid step per point), so the second read of
-    // a strip comes from the CU's L1 instead of L2
-    constexpr int LANES_R = SDP_COL_THREADS < N0 ? SDP_COL_THREADS : N0;   // threads along the rows
-    constexpr int GROUPS = SDP_COL_THREADS / LANES_R;                        // thread groups along w
-    const int W_PER = (w_count + GROUPS - 1) / GROUPS;
-    const int grp = threadIdx.x / LANES_R;
-    const int w_lo = w_begin + grp * W_PER, w_hi = min(Wn, w_lo + W_PER);
-    for (int r = threadIdx.x - grp * LANES_R; r < N0 && grp < GROUPS; r += LANES_R) {
-        for (int w0 = w_lo; w0 < w_hi; w0 += G) {
-            sdp_real vals[G][NV];
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const int w = min(w0 + j, w_hi - 1);                 // clamp: result unused
-                int off[SDP_DT];
-#pragma unroll
-                for (int k = 0; k < SDP_DT; ++k) off[k] = s.w_off[w * SDP_DT + k];
-                SdpColGather<0>::run(V + r, tg, off, 0, vals[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const int w = w0 + j;
-                if (w < w_hi) {
-                    sdp_real lam[SDP_DT], oml[SDP_DT];
-#pragma unroll
-                    for (int k = 0; k < SDP_DT; ++k) {
-                        lam[k] = s.w_lam[w * SDP_DT + k];
-                        oml[k] = s.w_oml[w * SDP_DT + k];
-                    }
-                    const sdp_real val = SdpColNest<0, SHIFT>::run(vals[j], lam, oml, tg.shift);
-                    const sdp_real entry = val;
-                    const int tw = w - w_begin;
 #if SDP_COL_WPAIR
                     s.T[((tw >> 1) * N0 + r) * 2 + (tw & 1)] = entry;
 #else
@@ -738,71 +662,20 @@ SDP_DEV void sdp_col_lead_axis(const SdpSweepArgs &a, SdpLeadAxis &l)
     l.koff = (sdp_real)0;
 }
 
-// Where the inner loop takes the perturbation weights p_w (and points w, when
-// the cost depends on w) from -- SDP_COL_WMODE:
-//   0  VGPRs: every lane holds the same W values for the whole kernel (the w
-//      loop is fully unrolled, so the arrays are never indexed dynamically);
-//      2*W registers, no memory instruction besides the two LDS reads per cell
-//   1  scalar loads (s_load_*) from the constant address space into SGPRs,
-//      used directly as VALU operands: no VGPR cost
-//   2  LDS broadcast reads of a copy made at kernel start
-// Default: scalar loads (A/B on MI355X: as fast as VGPRs, and no register cost).
-
+// The inner loop takes the perturbation weights p_w (and points w, when the cost depends on w) by scalar
+// loads (s_load_*) from the constant address space into SGPRs, used directly as VALU operands: no VGPR cost.
+// (A/B on MI355X against every lane holding the W values in VGPRs for the whole kernel, and against LDS
+// broadcast reads of a copy made at kernel start: as fast as VGPRs, and no register cost.)
 struct SdpColWeights {
-#if SDP_COL_WMODE == 0 && SDP_HAS_W
-    sdp_real p[SDP_COL_W];
-#if SDP_COST_HAS_W || SDP_LEAD_HAS_W
-    sdp_real w[SDP_COL_W];
-#endif
-#endif
-    const volatile sdp_cst_real *cp, *cw;  // mode 1 (volatile: stay inside the loop)
-    const volatile sdp_lds_real *lp, *lw;  // mode 2
+    const volatile sdp_cst_real *cp, *cw;  // (volatile: stay inside the loop)
 };
-
-#if SDP_COL_WMODE == 0
-#define SDP_COL_PW(k, w) ((k).p[w])
-#define SDP_COL_GW(k, w) ((k).w[w])
-#elif SDP_COL_WMODE == 1
 #define SDP_COL_PW(k, w) ((k).cp[w])
 #define SDP_COL_GW(k, w) ((k).cw[w])
-#else
-#define SDP_COL_PW(k, w) ((k).lp[w])
-#define SDP_COL_GW(k, w) ((k).lw[w])
-#endif
 
-SDP_DEV void sdp_col_load_weights(const SdpSweepArgs &a, SdpColWeights &k, sdp_real *lds_p,
-                                  sdp_real *lds_w)
+SDP_DEV void sdp_col_load_weights(const SdpSweepArgs &a, SdpColWeights &k)
 {
-    const sdp_real *gp = (const sdp_real *)a.proba;
-    const sdp_real *gw = (const sdp_real *)a.wgrid;
     k.cp = (const volatile sdp_cst_real *)a.proba;
     k.cw = (const volatile sdp_cst_real *)a.wgrid;
-    k.lp = (const volatile sdp_lds_real *)lds_p;
-    k.lw = (const volatile sdp_lds_real *)lds_w;
-    (void)gp; (void)gw;
-#if SDP_HAS_W
-#if SDP_COL_WMODE == 0
-#pragma unroll
-    for (int w = 0; w < SDP_COL_W; ++w) {
-        // the empty asm pins each (wave-uniform) value in a VGPR: left to
-        // itself the compiler keeps them in SGPRs, runs out and spills
-        sdp_real v = gp[w];
-        asm volatile("" : "+v"(v));
-        k.p[w] = v;
-#if SDP_COST_HAS_W || SDP_LEAD_HAS_W
-        v = gw[w];
-        asm volatile("" : "+v"(v));
-        k.w[w] = v;
-#endif
-    }
-#elif SDP_COL_WMODE == 2
-    for (int w = threadIdx.x; w < SDP_COL_W; w += blockDim.x) {
-        lds_p[w] = gp[w];
-        lds_w[w] = gw[w];
-    }
-    __syncthreads();
-#endif
-#endif
 }
 
 #if SDP_COL_WPAIR
@@ -1005,13 +878,8 @@ SDP_DEV void sdp_col_expected_cost(const SdpSweepArgs &a, const SdpGrid<sdp_real
     // w order.
     constexpr int B = SDP_COL_BATCH;
     // a partially unrolled loop bounds the region the instruction scheduler sees
-    // (fully unrolled it tends to hoist every read and spill); mode-0 weights
-    // live in registers and need static indices, hence the full unroll there
-#if SDP_COL_WMODE == 0
-#pragma unroll
-#else
+    // (fully unrolled it tends to hoist every read and spill)
 #pragma unroll SDP_COL_UNROLL_W
-#endif
     for (int w0 = 0; w0 < Wn; w0 += B) {
         sdp_real lo[B][K], hi[B][K];
 #if SDP_LEAD_HAS_W
@@ -1113,22 +981,16 @@ SDP_DEV void sdp_col_walk(const SdpSweepArgs &a, SdpColWalk &w)
 // aligned block of 8 rows of columns inside the launch's range (identity elsewhere); the
 // results do not depend on the order.  (With the static striding of the other kernels the
 // workgroups drift apart and the order made no difference: measured.)
-#ifndef SDP_COL_TILE
-#define SDP_COL_TILE 1
-#endif
-#ifndef SDP_COL_SHARE_X2
-// 1 (three state variables, a launch over the whole grid, x2 a multiple of 64 and x1 of 8 points): the eight
+// Where it can (three state variables, a launch over the whole grid, x2 a multiple of 64 and x1 of 8 points), the eight
 // XCDs' shares of the columns are cut along x2 -- every XCD walks ALL rows of x1, an eighth of x2 each -- instead of
 // along x1.  The strips a column's table is built from lie around its next trailing state; with the shares cut along x1
 // the chip works on eight bands of x1 at once and their strips together (~70 MB per band at 512^3 x 4 bytes) do not fit
 // the cache, so every strip comes from HBM once per band that touches it (measured: 4.0 GB fetched per sweep for a
 // 0.54 GB array).  Cut along x2, the eight shares move through the SAME band of x1 together and share its strips:
-// 512^3 x 4 bytes 7.90 -> 7.54 ms, 256^3 x 8 bytes (which fits the cache) 1.336 -> 1.320 ms, same box.  0: along x1 (A/B runs)
-#define SDP_COL_SHARE_X2 1
-#endif
+// 512^3 x 4 bytes 7.90 -> 7.54 ms, 256^3 x 8 bytes (which fits the cache) 1.336 -> 1.320 ms, same box.
 SDP_DEV int64_t sdp_col_of_unit(const SdpSweepArgs &a, int64_t unit)
 {
-#if SDP_D == 3 && SDP_COL_SHARE_X2 && (SDP_COL_FILTER || SDP_TRAIL_HAS_U)
+#if SDP_D == 3 && (SDP_COL_FILTER || SDP_TRAIL_HAS_U)
     {
         const int n1 = a.orders[1], n2 = a.orders[2];
         const int64_t cols = (int64_t)n1 * n2;
@@ -1143,7 +1005,7 @@ SDP_DEV int64_t sdp_col_of_unit(const SdpSweepArgs &a, int64_t unit)
     }
 #endif
     const int64_t col = a.col_begin + (int64_t)((unsigned)unit / (unsigned)a.col_splits);     // (units < 2^31: see sdp_col_coords)
-#if SDP_D == 3 && (SDP_COL_FILTER || SDP_TRAIL_HAS_U) && SDP_COL_TILE
+#if SDP_D == 3 && (SDP_COL_FILTER || SDP_TRAIL_HAS_U)
     const int64_t n2 = a.orders[2];
     if ((n2 & 7) == 0) {
         const int64_t blk = 8 * n2;
@@ -1268,13 +1130,7 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
 #endif
         ((SDP_COL_FILTER || SDP_TRAIL_HAS_U) ? SDP_META_F_CLAIMS : 0) | SDP_META_PEER_FLAG,
     SDP_COL_FILTER ? SDP_COL_UTAB : 0, SDP_COL_FILTER ? SDP_COL_UTAB_N : 0, SDP_COL_THREADS, SDP_COL_ROWS,
-    0, 0,
-#ifdef SDP_COLRES_TAIL_BYTES
-    SDP_COLRES_TAIL_BYTES
-#else
-    0
-#endif
-    };
+    0, 0, 0};
 }
 
 #else   // SDP_D < 2: no column kernels; the unit is a node-order one after all

@@ -628,6 +628,11 @@ def test_the_environment_does_not_reach_the_generated_source(monkeypatch):
     s.debug_defines = {'SDP_COL_FILTRE_SCALE': '2'}
     with pytest.raises(ValueError):
         s._kernel_plan()
+    # and so are the switches of A/B forks that the headers no longer have
+    for retired in ('SDP_COL_TAIL_KEEP', 'SDP_COL_WMODE', 'SDP_COL_A_ORDER'):
+        s.debug_defines = {retired: '1'}
+        with pytest.raises(ValueError):
+            s._kernel_plan()
     assert DPSolver.debug_defines is None
 
 
