@@ -67,8 +67,8 @@ _BIN_INFIX = {'add': '+', 'sub': '-', 'mul': '*', 'div': '/',
               'lt': '<', 'le': '<=', 'gt': '>', 'ge': '>=', 'eq': '==', 'ne': '!=',
               'and': '&&', 'or': '||', 'xor': '!='}
 _FUNC1 = {'abs': 'fabs', 'sqrt': 'sqrt', 'floor': 'floor', 'ceil': 'ceil', 'trunc': 'trunc',
-          'rint': 'rint', 'exp': 'exp', 'exp2': 'exp2', 'expm1': 'expm1', 'log': 'log',
-          'log2': 'log2', 'log10': 'log10', 'log1p': 'log1p', 'sin': 'sin', 'cos': 'cos',
+          'rint': 'rint', 'exp': 'exp', 'exp2': 'exp2', 'expm1': 'sdp_npexpm1', 'log': 'log',
+          'log2': 'log2', 'log10': 'log10', 'log1p': 'sdp_nplog1p', 'sin': 'sin', 'cos': 'cos',
           'tan': 'tan', 'asin': 'asin', 'acos': 'acos', 'atan': 'atan', 'sinh': 'sinh',
           'cosh': 'cosh', 'tanh': 'tanh', 'cbrt': 'cbrt'}
 _FUNC2 = {'pow': 'pow', 'atan2': 'atan2', 'hypot': 'hypot', 'fmod': 'fmod',

@@ -180,12 +180,16 @@ SDP_DEV void sdp_make_grid(SdpGrid<real, D> &g, const int32_t *orders, const rea
 // numpy-semantics helpers for generated model code
 // ---------------------------------------------------------------------------
 template <typename real> SDP_DEV bool sdp_isnan(real a) { return a != a; }
-// np.minimum / np.maximum propagate NaN (first NaN operand is returned)
-template <typename real> SDP_DEV real sdp_npmin(real a, real b) { return (sdp_isnan(a) || a <= b) ? a : b; }
-template <typename real> SDP_DEV real sdp_npmax(real a, real b) { return (sdp_isnan(a) || a >= b) ? a : b; }
-// np.fmin / np.fmax ignore a NaN operand
-template <typename real> SDP_DEV real sdp_npfmin(real a, real b) { return (sdp_isnan(b) || a <= b) ? a : b; }
-template <typename real> SDP_DEV real sdp_npfmax(real a, real b) { return (sdp_isnan(b) || a >= b) ? a : b; }
+// np.minimum / np.maximum propagate NaN (the first NaN operand is returned); np.fmin / np.fmax ignore a NaN operand.
+// Operands that compare EQUAL -- zeros of opposite sign -- give the SECOND one: numpy's loops on x86-64 are the
+// minpd / maxpd family, which return their second source then (minimum(0., -0.) is -0., minimum(-0., 0.) is 0.).
+template <typename real> SDP_DEV real sdp_npmin(real a, real b) { return (sdp_isnan(a) || a < b) ? a : b; }
+template <typename real> SDP_DEV real sdp_npmax(real a, real b) { return (sdp_isnan(a) || a > b) ? a : b; }
+template <typename real> SDP_DEV real sdp_npfmin(real a, real b) { return (sdp_isnan(b) || a < b) ? a : b; }
+template <typename real> SDP_DEV real sdp_npfmax(real a, real b) { return (sdp_isnan(b) || a > b) ? a : b; }
+// expm1 and log1p of a zero are that zero, sign included (C99 and numpy; the device library returns +0 for -0)
+template <typename real> SDP_DEV real sdp_npexpm1(real a) { return a == (real)0 ? a : expm1(a); }
+template <typename real> SDP_DEV real sdp_nplog1p(real a) { return a == (real)0 ? a : log1p(a); }
 template <typename real> SDP_DEV real sdp_npsign(real a)
 {
     return a > (real)0 ? (real)1 : (a < (real)0 ? (real)-1 : (a == (real)0 ? (real)0 : a));
@@ -206,7 +210,8 @@ SDP_DEV float sdp_nppymod(float a, float b)
 }
 template <typename real> SDP_DEV real sdp_npfloordiv(real a, real b)
 {
-    // numpy npy_divmod: floor of the quotient, consistent with the Python-style remainder
+    // numpy npy_divmod: floor of the quotient, consistent with the Python-style remainder; a zero divisor gives a / b
+    if (b == (real)0) return a / b;
     const real m0 = fmod(a, b);
     real div = (a - m0) / b;
     if (b != (real)0 && m0 != (real)0 && ((m0 < (real)0) != (b < (real)0))) div -= (real)1;

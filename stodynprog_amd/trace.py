@@ -54,8 +54,10 @@ _OPS = {
     'interp1': (1, 'r'),         # np.interp(x, xp, fp): node.value = index into Graph.tables
 }
 
-# ops whose device result is the correctly rounded IEEE result (bit-exact vs numpy)
-EXACT_OPS = {'add', 'sub', 'mul', 'div', 'neg', 'abs', 'sqrt', 'square', 'recip',
+# ops whose device result is the correctly rounded IEEE result (bit-exact vs numpy); fmod, pymod (`%`) and floordiv
+# (`//`) are fixed sequences of exact and correctly rounded steps, numpy's npy_divmod restated (csrc/sdp_device.h).
+# Each is pinned on the device, operand by operand, by tests/test_gpu_device_ops.py.
+EXACT_OPS = {'add', 'sub', 'mul', 'div', 'neg', 'abs', 'sqrt', 'square', 'recip', 'fmod', 'pymod', 'floordiv',
              'min', 'max', 'fmin', 'fmax', 'floor', 'ceil', 'trunc', 'rint', 'sign',
              'lt', 'le', 'gt', 'ge', 'eq', 'ne', 'and', 'or', 'xor', 'not', 'isnan',
              'isfinite', 'isinf', 'select', 'bselect', 'b2r', 'var', 'const', 'bconst',
@@ -454,8 +456,16 @@ def _interp(x, xp, fp, left=None, right=None, period=None):
 
 
 def _clip(a, lo, hi):
-    # np.clip(a, lo, hi) == minimum(maximum(a, lo), hi)
+    """np.clip(a, lo, hi) as numpy 2 evaluates it:
+      * both bounds plain numbers, neither NaN -- the usual spelling, `np.clip(x, 0., 1.)` -- run numpy's loop for
+        constant bounds (clip.cpp, _npy_clip_const_minmax_): `if (x < lo) x = lo; if (x > hi) x = hi;`.  A value that
+        EQUALS a bound stays as it is, sign of a zero included (clip(-0., 0., 1.) is -0.), and NaN passes;
+      * anything else -- a bound that is an expression, one bound only -- is minimum(maximum(a, lo), hi), where operands
+        that compare equal give the second one (clip(-0., x * 0., 1.) is +0.)."""
     sym = _any_sym(a, lo, hi)
+    if _is_plain_number(lo) and _is_plain_number(hi) and not (math.isnan(float(lo)) or math.isnan(float(hi))):
+        out = _where(sym._bin('lt', a, lo), lo, a)
+        return _where(sym._bin('gt', out, hi), hi, out)
     out = a
     if lo is not None:
         out = sym._bin('max', out, lo)
