@@ -39,12 +39,13 @@ DEBUG_INT_MACROS = ('SDP_COL_MIN_WAVES', 'SDP_COL_BATCH', 'SDP_COL_UNROLL_U', 'S
                     'SDP_COL_TAIL_HOLD', 'SDP_SHORT_GROUP', 'SDP_BNB_CHUNK')
 # (SDP_COL_LEAN2 = 0 keeps the resident-chunk kernel on the first pass of section 3.1c: an A/B switch of short_pass_source)
 # (SDP_COL_WRES is a planning switch: it sizes the LDS image -- column_config)
+# (SDP_BNB_UNIFORM = 0 keeps the branch and bound on the bound stage that locates every block end per node: an A/B switch)
 # every name a `debug` dict may carry (a typo must not pass silently)
 DEBUG_NAMES = frozenset(DEBUG_INT_MACROS + (
     'SDP_STAMP', 'SDP_NO_POW2', 'SDP_EXTRA_DEFINES', 'SDP_COL_FILTER_SCALE', 'SDP_LEAD_FILTER_SCALE',
     'SDP_LEAD_UNROLL', 'SDP_COL_A_LW', 'SDP_COL_FILTER', 'SDP_COL_SHIFT', 'SDP_COL_UTAB', 'SDP_LEAD_FILTER',
     'SDP_COL_THREADS', 'SDP_COL_WCHUNK', 'SDP_STG_CU', 'SDP_COL_WPAIR', 'SDP_COL_WRES', 'SDP_COL_LEAN2', 'SDP_COL_BNB',
-    'SDP_LINE_FILTER', 'SDP_LINE_FILTER_SCALE', 'SDP_LINE_TOP2'))
+    'SDP_LINE_FILTER', 'SDP_LINE_FILTER_SCALE', 'SDP_LINE_TOP2', 'SDP_BNB_UNIFORM'))
 
 
 def check_debug(debug):
@@ -466,7 +467,109 @@ def _prologue_lines(model, real, lanes, debug, peer_stores=False):
     return lines
 
 
-def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, utab, debug, wres=0):
+def uniform_rows_axis(axis, dtype, n0=None):
+    """Does node r of a column sit at row r of the stock axis, as the branch and bound's bound stage locates it?  The
+    kernel forms the position of X_r as fl(fl(X_r - smin) k), k = fl((n - 1) / fl(X_last - smin)); here the product of the
+    STORED values is taken exactly (rationals), the two roundings are bounded by 2^-52 of it each, and the sum has to stay
+    within 2^-23 rows of r for every r -- half of what the kernel itself accepts when it checks the same thing, node by
+    node, before it relies on it (SDP_BNB_UNIFORM of csrc/sdp_colres_kernel.h).  8-byte reals only."""
+    from fractions import Fraction
+    if np.dtype(dtype).itemsize != 8:
+        return False
+    x = np.asarray(axis, dtype=np.float64).ravel()
+    n = x.size
+    if n < 2 or (n0 is not None and n != int(n0)) or not np.all(np.isfinite(x)):
+        return False
+    span = x[-1] - x[0]
+    if not (span > 0):
+        return False
+    k = Fraction(float(np.float64(n - 1) / span))
+    smin, tol, u2 = Fraction(float(x[0])), Fraction(1, 2 ** 23), Fraction(1, 2 ** 51)
+    for r in range(n):
+        p = (Fraction(float(x[r])) - smin) * k
+        if abs(p - r) + u2 * (abs(p) + 1) > tol:
+            return False
+    return True
+
+
+def uniform_stage_model(model, frontier):
+    """x0' = X +- a with X the stock ITSELF (not a function of it, of the column or of the time index): a node of row r
+    then sits at row r wherever the stock axis is uniform -- what the uniform bound stage of the branch and bound needs
+    of the model (the kernel checks the rows node by node all the same)"""
+    sp = model.additive_control_split(frontier) if frontier is not None else None
+    if sp is None:
+        return False
+    x_node, _, a_form = sp['lead']
+    return bool(a_form in ('add', 'sub') and x_node is not None and x_node.op == 'var' and x_node.value == 'x0')
+
+
+uniform_define = ('\n#define SDP_BNB_UNIFORM 1      // node r of a column sits at row r of the stock axis: the block ends of the '
+                  'branch and bound at the same offsets in every lane')
+
+
+def uniform_stage_reach(model, frontier, lattice, k_rows):
+    """Rows of the stock axis that the control lattice reaches on either side of a node under x0' = x0 +- a(u): the
+    largest |a| over the lattice (`lattice`: one array of values per control; a is evaluated with numpy on their
+    product) times `k_rows`, or None where a is not a function of the controls alone."""
+    from . import trace
+    a_node = frontier[int(model.additive_control_split(frontier)['lead'][1])]
+    mesh = np.meshgrid(*[np.asarray(v, dtype=float) for v in lattice], indexing='ij')
+    env = {}
+    with np.errstate(all='ignore'):
+        for n in model.slice_nodes([a_node]):
+            if n.op == 'var':
+                if not (isinstance(n.value, str) and n.value[0] == 'u'):
+                    return None
+                env[n.id] = mesh[int(n.value[1:])]
+            elif n.op == 'const':
+                env[n.id] = np.float64(n.value)
+            elif n.op == 'bconst':
+                env[n.id] = np.bool_(n.value)
+            elif n.op == 'interp1':
+                xp, fp, left, right = model.graph.tables[n.value][:4]
+                env[n.id] = np.interp(env[n.args[0].id], xp, fp, left, right)
+            else:
+                env[n.id] = trace._NP_EVAL[n.op](*[env[a.id] for a in n.args])
+    a = np.abs(np.asarray(env[a_node.id], dtype=float))
+    if not np.all(np.isfinite(a)):
+        return None
+    return float(a.max()) * abs(float(k_rows))
+
+
+def uniform_stage_pad(model, dtype, frontier, axis, n0, lattice, wres, shift, threads, lds, debug=None):
+    """THE place that decides the uniform bound stage of the branch and bound (SDP_BNB_UNIFORM of
+    csrc/sdp_colfilter_kernel.h): the rows the reduced table is padded by on either side -- BNB_PAD where a unit plans
+    the stage, 0 where it keeps the bound stage that locates every block end per node.  Planned only when ALL hold:
+    the resident-chunk form (`wres`) of 8-byte reals with the short first pass and its branch and bound, not the
+    shifted lattice; x0' = x0 +- a(u) with a control table (`uniform_stage_model`); a stock axis on which every node
+    provably sits at its row (`uniform_rows_axis`); the two rows either end of the table is continued from reduced by
+    one wave ((n0 - 1) % 64 != 0); a lattice (`lattice`: the values of every control) whose reach, max |a| k rows plus
+    the cell partner, the end's margin and the row below, fits the padding; and 2 BNB_PAD rows more that cost the CU no
+    workgroup (`threads`, `lds`: the shape planned without them).  The kernel checks rows and reach again where it
+    runs (a failure there is the full first pass): with this plan neither fails.
+    (`debug`: SDP_COL_LEAN2 / SDP_COL_BNB = 0 take the short pass away; SDP_BNB_UNIFORM = 0 keeps the PADDING and
+    leaves the stage out -- the A/B switch, decided by `_column_lines`.)"""
+    rs = np.dtype(dtype).itemsize
+    n0 = int(n0)
+    if not wres or shift or rs != 8 or frontier is None or model.cost_depends_on_w:
+        return 0
+    if _dbg(debug, 'SDP_COL_LEAN2') == '0' or _dbg(debug, 'SDP_COL_BNB') == '0':
+        return 0
+    if n0 < 2 or (n0 - 1) % 64 == 0 or not uniform_stage_model(model, frontier):
+        return 0
+    if not uniform_rows_axis(axis, dtype, n0):
+        return 0
+    x = np.asarray(axis, dtype=np.float64).ravel()
+    reach = uniform_stage_reach(model, frontier, lattice, np.float64(n0 - 1) / (x[-1] - x[0]))
+    if reach is None or not reach * (1.0 + 2.0 ** -30) + 2.0 ** -19 <= BNB_PAD - 3:
+        return 0
+    per_cu = lambda size: min(COLUMN_LDS_MAX // size, max(1, 2048 // int(threads)))      # (LDS, and 32 waves per CU)
+    if per_cu(int(lds) + 2 * BNB_PAD * rs) != per_cu(int(lds)):
+        return 0
+    return BNB_PAD
+
+
+def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, utab, debug, wres=0, bnb_pad=0):
     """the macros and model slices of a unit that includes csrc/sdp_column_kernel.h"""
     rs = np.dtype(dtype).itemsize
     wpair = use_wpair(model, dtype, debug) and window is None
@@ -557,6 +660,14 @@ def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, 
                 if short and _dbg(debug, 'SDP_COL_BNB') != '0':
                     short += ('\n#define SDP_COL_BNB 1          // the short first pass as a certified branch and bound over '
                               'blocks of controls (sdp_lean2_bnb)')
+                    # (X of x0' = X +- a must be the stock itself: a node of row r then sits at row r in every column, at every
+                    # time index; the kernel checks the rows node by node all the same)
+                    if bnb_pad:                # (uniform_stage_pad: the plan; the LDS image counts these rows)
+                        short += '\n#define SDP_BNB_PAD_ROWS {}    // the reduced table continued linearly on either side'.format(
+                            int(bnb_pad))
+                        if _dbg(debug, 'SDP_BNB_UNIFORM') != '0':
+                            short += uniform_define
+                        bnb_pad = 0
 
             elif rs == 4 and not wres and _dbg(debug, 'SDP_COL_FILTER_TOP2') in (None, '1'):
                 short = short_pass_source(model, utab[0], 'SDP_COL_WIDE2')
@@ -567,6 +678,8 @@ def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, 
                         short += '\n#define SDP_BNB_CHUNK 4        // blocks whose bounds are evaluated together (see SDP_COL_A_GROUP above)'
         if short:
             lines += [short, '']
+    if bnb_pad:
+        raise ValueError('a padded reduced table was planned for a unit without the branch and bound of the short first pass')
     lines += ['#include "sdp_column_kernel.h"    // also brings in sdp_sweep_kernel.h', '']
     return lines
 
@@ -624,7 +737,7 @@ def line_functions_source(model):
 
 def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
                      per_control=None, filtered=False, utab=None, lead_axes=0, col_cfg=None, debug=None, wres=0,
-                     lead_perm=None, line=0, peer_stores=False):
+                     lead_perm=None, line=0, peer_stores=False, bnb_pad=0):
     """column: None for the generic node-order kernels, or (N0, W[, controls, columns]) to also
     build the column kernels of csrc/sdp_column_kernel.h for a storage-separable
     model on a grid with N0 points along axis 0 and W perturbation points.
@@ -641,6 +754,9 @@ def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
     utab: None, or (frontier nodes, capacity of the control table in controls) of `control_table_plan`
     (filtered kernel only): the first pass reads the column-uniform sub-expressions from a table.
     debug: None (the product), or a dict of diagnostic switches (see DEBUG_NAMES).
+    bnb_pad: what `uniform_stage_pad` planned for this unit (rows the reduced table is padded by: the resident-chunk
+    form's branch and bound then takes its block ends at the same offsets in every lane, SDP_BNB_UNIFORM); `col_cfg`
+    counts these rows in its LDS bytes.
     peer_stores: the unit's backup kernels also store J into the buffers of other ranks (the direct exchange,
     SdpSweepArgs.peer_J); without it they hold no code for that, and the library refuses the direct exchange."""
     debug = check_debug(debug)
@@ -663,7 +779,7 @@ def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
         if col_cfg is None:
             raise ValueError('the column kernel does not fit this grid (its table exceeds the LDS of a CU)')
         head += _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, utab, debug,
-                              wres if (window is None and per_control is None) else 0)
+                              wres if (window is None and per_control is None) else 0, bnb_pad=bnb_pad)
     elif staged is not None:
         tile = tuple(staged['tile']) + (1,) * (4 - len(staged['tile']))
         head += ['#define SDP_STG_THREADS {}'.format(int(staged['threads']))] + [
@@ -998,6 +1114,11 @@ def column_build_order(threads, w, rows, rows_per_lane=1):
     return (best[0], best[1]) if best[2] >= 0.85 else (0, 0)
 
 
+BNB_PAD = 16                 # SDP_BNB_PAD_ROWS of csrc/sdp_column_kernel.h where a unit pads its reduced table
+
+
+
+
 def bnb_words(n_controls):
     """reals of block statistics kept beside a control table of `n_controls` controls (SDP_BNB_WORDS of
     csrc/sdp_column_kernel.h: four per block of 8 controls, larger blocks beyond 64 of them)"""
@@ -1015,7 +1136,7 @@ def utab_reals(n_values, n_controls):
 
 
 def _column_lds(tw, w, rows, n_state, rs, threads, reduced=False, shift=False, shift_rows=0, utab_values=0,
-                partial_minima=False):
+                partial_minima=False, bnb_pad=False):
     """sizeof(SdpColLds) of csrc/sdp_column_kernel.h, member by member with the alignment rules of
     the C++ struct.  tw: perturbation points the table holds (SDP_COL_TW; SDP_COL_WRES of the resident-chunk
     form; SDP_COL_WCHUNK of the table per control); rows: rows of axis 0 the table holds;
@@ -1023,7 +1144,9 @@ def _column_lds(tw, w, rows, n_state, rs, threads, reduced=False, shift=False, s
     lean form of 8-byte reals, 16 bytes per row otherwise;
     shift: the shifted lattice -- `ad` then has `shift_rows` rows of two reals -- and the shifts of the
     perturbation points; utab_values: reals per parity buffer of the control table (0: the struct's two);
-    partial_minima: the unfiltered sweep's per-thread partial minima (SDP_COL_LDS_PART)."""
+    partial_minima: the unfiltered sweep's per-thread partial minima (SDP_COL_LDS_PART);
+    bnb_pad: the resident-chunk form of 8-byte reals without the shifted lattice -- `ad` is padded by BNB_PAD rows on
+    either side (SDP_BNB_PAD: the uniform bound stage of the branch and bound)."""
     dt = n_state - 1
     part = threads if partial_minima else 1
     members = [(rs, tw * rows, 16),                          # T
@@ -1035,7 +1158,7 @@ def _column_lds(tw, w, rows, n_state, rs, threads, reduced=False, shift=False, s
                (rs, 2 * (int(utab_values) + 4 if utab_values else 2), 16)]        # utab[2][.. + 4 column statistics]
     if reduced or shift:
         per_row = 4 if rs == 4 else (2 if shift else 1)      # SDP_COL_LDS_AD (8-byte reals: the lean form is the default)
-        members.append((rs, per_row * int(shift_rows if shift else rows), 16))    # ad
+        members.append((rs, per_row * int(shift_rows if shift else rows) + (2 * BNB_PAD if bnb_pad and not shift else 0), 16))    # ad
     if shift:
         members += [(4, 2 * w, 4), (rs, 2 * w, rs), (rs, 2 * w, rs), (4, 8, 4)]                   # sh_q, sh_f, sh_c, sh_k
     off = 0

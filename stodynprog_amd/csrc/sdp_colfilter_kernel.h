@@ -571,6 +571,18 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
     const int lane_u = tid - first;
     bool bnb_fine = count == 64 && SDP_BNB_BLOCK <= 64;
     sdp_real bnb_prev_hi = -INFINITY, bnb_prev_lo = (sdp_real)NAN, bnb_between = (sdp_real)0, bnb_amax = (sdp_real)0;
+#if SDP_BNB_UNIFORM_ON
+    asm volatile("" : "+v"(bnb_prev_hi));                  // (a constant made here, not kept in registers across the unit loop)
+    // The uniform bound stage (sdp_short_bnb) takes a block end as  row r + k_b + phi_b  of lane r: k_b = floor(start),
+    // phi_b = start - k_b of the SAME stored start (an exact difference) -- in the half of the block records that 8-byte
+    // reals leave unused: 8 k_b as integers (SDP_BNB_UNI_K), then the phi_b (SDP_BNB_UNI_PHI).  It needs every |k_b| + 2
+    // within the padding of the reduced table: uni_k is the largest |k_b| (a 4-byte real: a whole number, or too large
+    // anyway).  The rows it reads beyond the two that the ends' cells bring along are the `extra` of the records:
+    // k_{b+1} - k_b <= floor(start_{b+1} - start_b) + 1, and the record's count allows for the roundings of that
+    // difference -- argued here, not checked on the device; tests/test_uniform_bound_exact.py asserts it case by case.
+    // Made from the records once they are all there (a lane per end; the wave's own writes: in order).
+    // (The planner proves rows and reach on the host, codegen.uniform_stage_pad: uni_fine below only guards the reads.)
+#endif
     for (int c0 = 0; c0 < n_tab; c0 += 64) {               // (every lane of the wave takes part in every round: shuffles)
         int ci = c0 + lane_u;
         // (opaque to the optimiser: with a constant box the control of a lane and everything computed from it alone are
@@ -635,7 +647,14 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
             }
         }
         // the block that follows in this round, or nothing (the last one of the round meets its successor next round)
+#if SDP_BNB_UNIFORM_ON
+        // (the lane from lane_u -- the table's wave starts at a multiple of 64 -- and not from a lane id kept across the unit loop)
+        const int next_at = (lane_u + SEG) << 2;
+        const sdp_real next_lo = (sdp_real)__hiloint2double(__builtin_amdgcn_ds_bpermute(next_at, __double2hiint((double)lo)),
+                                                            __builtin_amdgcn_ds_bpermute(next_at, __double2loint((double)lo)));
+#else
         const sdp_real next_lo = __shfl_down(lo, SEG, 64);
+#endif
         const bool has_next = lane_u + SEG < 64 && ci + SEG < n_tab;
         if (head) {
             const int b = ci / SDP_BNB_BLOCK;
@@ -665,6 +684,18 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
         const bool sorted = __all(bnb_fine);
         bnb_between = sdp_wave_max(bnb_between);
         bnb_amax = sdp_wave_max(bnb_amax);
+        bool uni_fine = true;                              // (a unit with the uniform bound stage has no other: no branch and bound
+                                                           //  in a column whose lattice reaches past the padding)
+#if SDP_BNB_UNIFORM_ON
+        float uni_k = 0.0f;
+        for (int b = lane_u; b <= (n_tab + SDP_BNB_BLOCK - 1) / SDP_BNB_BLOCK; b += 64) {
+            const sdp_real st = rec[2 * b], kf = floor(st);
+            SDP_BNB_UNI_K(rec)[b] = (int)((unsigned)(int)kf << 3);     // (a k_b beyond the padding is never read)
+            SDP_BNB_UNI_PHI(rec)[b] = st - kf;
+            uni_k = fmaxf(uni_k, fabsf((float)kf));
+        }
+        uni_fine = sorted && sdp_wave_max(uni_k) + 2.0f <= (float)SDP_BNB_PAD;
+#endif
         if (lane_u == 0) {
             const int n_blocks = (n_tab + SDP_BNB_BLOCK - 1) / SDP_BNB_BLOCK;
             // rows strictly between the starts of two neighbouring blocks: at most floor(between) + 1, of which the ends'
@@ -677,7 +708,7 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
             // (8 u (|X| + |smin| + max |a|) k < DELTA / 2), or -1: no branch and bound in this column
             sdp_real *st = utab + SDP_COL_UTAB * SDP_COL_UTAB_N;
             const sdp_real cap = x_cap - bnb_amax;         // (x_cap = 2^30 / k - |smin| (2^13 / k for 4-byte reals): once per workgroup, by the caller)
-            st[3] = (sorted && cap == cap && extra < SDP_COL_N0) ? cap : (sdp_real)-1;
+            st[3] = (sorted && uni_fine && cap == cap && extra < SDP_COL_N0) ? cap : (sdp_real)-1;
         }
     }
 #else
@@ -1025,10 +1056,28 @@ SDP_DEV void sdp_wide2_pass1(const sdp_real *ad, const sdp_real *utab, const Sdp
 // ends are moved out by 2^-8 rows there, which covers the 4-byte roundings of the kernel's own positions).
 // c_lo: the controls [c_lo, n) of the lattice are this lane's (0: all of them; the branch and bound runs with one lane
 // per node).  `insert` receives the packed F' of every control that is evaluated.
+// UNIFORM bound stage (SDP_BNB_UNIFORM_ON: such a unit has no other; row_u is this lane's row.  The caller has checked, in
+// the kernel's own arithmetic, that this lane's pX is within 2^-22 of row_u, and the control table's wave that the padding
+// reaches as far as the lattice -- st[3] of sdp_col_phase_u says no otherwise, like for blocks out of order; the planner has
+// proved both on the host before it defines the macro, codegen.uniform_stage_pad, so neither fails in a planned unit).
+// The ends of the generic stage are pX + start(b); here they are row_u + start(b) = row_u + k_b + phi_b,
+// k_b = floor(start(b)) and phi_b = start(b) - k_b EXACTLY (at most 2^-53 rows off where the difference rounds to 1): the
+// cell of end b is row_u + k_b in every lane -- an offset added to the lane's own address --, its fraction phi_b, and no
+// conversion, clamp or position arithmetic is left.  The block's controls still lie between its ends: the kernel's own
+// position of a control is within DELTA / 2 = 2^-21 rows of pX + pa, hence within 2^-21 + 2^-22 + 2^-53 < DELTA of
+// row_u + pa, and the ends are DELTA outside the block's smallest and largest pa.  L at an end is the SAME function: inside
+// the axis the cell is the same; beyond it L continues the first (last) cell's line, and the padded rows A[-j], A[N0-1+j]
+// hold that line (fma(-+j, A[1] - A[0], A[0]) and its mirror: two roundings of numbers bounded by (1 + 2 j) D with
+// j <= L_cap + 1, i.e. < 8 u S_node, which the caller adds to the slack), so interpolating between two of them, or taking
+// one as a breakpoint, stays within that of L.  The rows strictly between two ends are row_u + k_b + 1 .. row_u + k_{b+1}:
+// the two the ends' cells bring along and k_{b+1} - k_b - 2 <= extra more (extra = floor(largest start difference + 4 DELTA)
+// - 1 absorbs the roundings of that difference: argued in sdp_col_phase_u, asserted by tests/test_uniform_bound_exact.py);
+// any further row that the clamped extra reads (row k_b - 1 where two ends share a cell) only lowers the bound.  A NaN or an infinity in a row the bound reads keeps
+// the block as before.
 template <int AXIS, bool WIDE, typename INSERT>
 SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpColFilter &f, const SdpLeadAxis &l,
                            sdp_real X, sdp_real k_rows, int c_lo, int n, int mask, double slack, int guess, INSERT &insert,
-                           sdp_real &sdp_diag_cnt, sdp_real *b_seen = nullptr)
+                           sdp_real &sdp_diag_cnt, sdp_real *b_seen = nullptr, int row_u = -1)
 {
     // SDP_COL_SHIFT (round 6): `A` holds the (A', B') pairs of the shifted lattice, `l` is the lattice.  A control's F' is off
     // from the real number it stands for by its OWN cell's chord bound B'[q0] on top of the rounding radius, so a block is
@@ -1036,7 +1085,7 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
     // (slack: twice the ROUNDING radius + the bound's own roundings): then E_c >= F'_c - rho_c > F'_g + rho_g >= E_g >= the
     // node's minimum for every control c of the block.  The rows are those the bound reads anyway (q_b, q_b + 1, the rows
     // between, q_b+1): B' rides along in the same 16-byte reads.  *b_seen: the largest B' among the controls evaluated.
-    (void)sdp_diag_cnt; (void)c_lo; (void)b_seen;
+    (void)sdp_diag_cnt; (void)c_lo; (void)b_seen; (void)row_u;
     constexpr bool SHIFT = SDP_COL_SHIFT != 0;
     static_assert(!(SHIFT && WIDE), "branch and bound on the shifted lattice: 8-byte reals");
     constexpr double BSCALE = (double)(SDP_COL_FILTER_SCALE);
@@ -1064,6 +1113,7 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
     // ---- stage 3: F' of the guess (an upper bound of the node's smallest F'), the bounds, the blocks to evaluate
     const sdp_real ga = utab[g * SDP_COL_UTAB + SDP_LEAN2_A_SLOT];
     const sdp_real gh = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : utab[g * SDP_COL_UTAB + HS];
+    (void)k_rows;
     const sdp_real pX = (SDP_LEAN2_FORM == 2 ? -((X + l.smin) * k_rows) : (X - l.smin) * k_rows) - (SHIFT ? l.koff : (sdp_real)0);
     const int extra = __builtin_amdgcn_readfirstlane(WIDE ? __float_as_int((float)rec[4 * n_blocks + 1]) : __double2loint((double)rec[2 * n_blocks + 1]));
     int gq;
@@ -1073,6 +1123,50 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
     unsigned long long need = 0ull;
     double thresh = 0.0;
     constexpr int CB = NB < SDP_BNB_CHUNK ? NB : SDP_BNB_CHUNK;
+#if SDP_BNB_UNIFORM_ON
+    {
+        const char *Ar = (const char *)(A + row_u);        // this lane's row of the (padded) reduced table
+        auto at = [&](int off) -> double { return (double)*(const sdp_real *)(Ar + off); };
+        for (int b0 = 0; b0 < n_blocks; b0 += CB) {        // (uniform)
+            int ko[CB + 1];
+            double P[CB + 1], hp[CB], Aq[CB + 1], Aq1[CB + 1], m[CB];
+#pragma unroll
+            for (int j = 0; j <= CB; ++j) {
+                const int b = min(b0 + j, n_blocks);
+                ko[j] = SDP_BNB_UNI_K(rec)[b];
+                P[j] = (double)SDP_BNB_UNI_PHI(rec)[b];    // (P: the fraction of end j)
+                if (j < CB) hp[j] = least(min(b, n_blocks - 1));
+            }
+#pragma unroll
+            for (int j = 0; j <= CB; ++j) {
+                Aq[j] = at(ko[j]);
+                Aq1[j] = at(ko[j] + 8);
+            }
+            if (b0 == 0) {
+                const double h = fma((double)glam, gA1 - gA0, gA0);
+                const double Fg = pack(SDP_LEAN2_H_SLOT < 0 ? h : fma((double)(SDP_LEAN2_HNEG ? -gh : gh), psum, h), g);
+                thresh = Fg + slack;
+            }
+#pragma unroll
+            for (int j = 0; j <= CB; ++j) P[j] = fma(P[j], Aq1[j] - Aq[j], Aq[j]);       // (P: now L at the end)
+#pragma unroll
+            for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(sdp_vmin(P[j], P[j + 1]), sdp_vmin(Aq1[j], Aq[j + 1]));
+            for (int k = 0; k < extra; ++k) {
+                double more[CB];
+#pragma unroll
+                for (int j = 0; j < CB; ++j) more[j] = at(min(ko[j] + 16 + 8 * k, ko[j + 1] - 8));
+#pragma unroll
+                for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(m[j], more[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < CB; ++j) {
+                const double lbv = hp[j] + m[j];
+                // pruned only on a comparison that HOLDS (a NaN anywhere keeps the block); the guess's own block always stays
+                if ((!(lbv > thresh) || b0 + j == g / BS) && b0 + j < n_blocks) need |= 1ull << (b0 + j);
+            }
+        }
+    }
+#else
     for (int b0 = 0; b0 < n_blocks; b0 += CB) {            // (uniform; one chunk on the benchmark lattice)
         int q[CB + 1];
         double P[CB + 1], hp[CB], Aq[CB + 1], Aq1[CB + 1], m[CB], Bq[SHIFT ? CB + 1 : 1], bm[SHIFT ? CB : 1];
@@ -1129,6 +1223,7 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
             if ((!(lbv > thresh) || b0 + j == g / BS) && b0 + j < n_blocks) need |= 1ull << (b0 + j);
         }
     }
+#endif  // SDP_BNB_UNIFORM_ON
 #ifdef SDP_DIAG_BNB_COUNT                                  // diagnostic: J := blocks asked for (+ 100 x the guess's block)
     sdp_diag_cnt = (sdp_real)(__popcll(need) + 100 * (g / BS));
 #endif

@@ -339,6 +339,7 @@ SDP_DEV void sdp_lean2s_pass1(const sdp_real *A, const sdp_real *utab, const Sdp
 
 #endif  // SDP_COL_LEAN2
 
+#define SDP_LDS_AD (sdp_lds.ad + SDP_BNB_PAD)            // row 0 of the reduced table (behind the padding of the uniform bound stage)
 extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES) sdp_sweep_col(SdpSweepArgs a)
 {
     __shared__ SdpColLds sdp_lds;
@@ -484,6 +485,9 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
 #else
         {
             sdp_real dmax = (sdp_real)0;
+#if SDP_BNB_UNIFORM_ON
+            sdp_real acc_row = (sdp_real)0;
+#endif
             if (r < N0) {
                 sdp_real acc = (sdp_real)0;
 #pragma unroll SDP_COL_FILTER_RUNROLL
@@ -495,8 +499,33 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
                 acc = acc + acc_t;
                 // (>= tiny / cu: the radius never drops below `tiny`; a NaN entry, which the max skips, shows in acc)
                 dmax = acc == acc ? filt.pcap * big + filt.floor : (sdp_real)INFINITY;
-                sdp_lds.ad[r] = acc;
+                SDP_LDS_AD[r] = acc;
+#if SDP_BNB_UNIFORM_ON
+                acc_row = acc;
+#endif
             }
+#if SDP_BNB_UNIFORM_ON
+            // the padding of the reduced table: the linear continuation of its first and of its last cell (sdp_short_bnb),
+            // by the waves that hold the two rows, before the barrier that publishes A
+            // (the thread opaque to the optimiser: what follows from it alone is the same in every unit, and hoisted out of
+            // the unit loop it lands in registers the kernel does not have -- see sdp_col_phase_u)
+            int pt = (int)threadIdx.x;
+            asm volatile("" : "+v"(pt));
+            const int pl = pt & 63, pw = __builtin_amdgcn_readfirstlane(pt >> 6);
+            // (the two rows from their lanes into scalar registers: the held tail leaves no vector registers here)
+            auto row_of = [&](int l) -> sdp_real {
+                return (sdp_real)__hiloint2double(__builtin_amdgcn_readlane(__double2hiint((double)acc_row), l),
+                                                  __builtin_amdgcn_readlane(__double2loint((double)acc_row), l));
+            };
+            if (pw == 0) {
+                const sdp_real a0 = row_of(0), a1 = row_of(1);
+                if (pl < SDP_BNB_PAD) SDP_LDS_AD[-(pl + 1)] = fma(-(sdp_real)(pl + 1), a1 - a0, a0);
+            }
+            if (pw == ((N0 - 1) >> 6)) {
+                const sdp_real a0 = row_of((N0 - 1) & 63), a1 = row_of((N0 - 2) & 63);
+                if (pl < SDP_BNB_PAD) SDP_LDS_AD[N0 + pl] = fma((sdp_real)(pl + 1), a0 - a1, a0);
+            }
+#endif
             dmax = sdp_wave_max(dmax);
             if (lane == 0) atomicMax(&sdp_lds.dcol[parity], (unsigned long long)__double_as_longlong((double)dmax));
         }
@@ -587,15 +616,15 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
                     bd.f2 = sdp_vmin(bd.f2, sdp_vmax(bd.f1, Fq));
                     bd.f1 = sdp_vmin(bd.f1, Fq);
                 };
-                if (axis_mode == 2) sdp_short_bnb<2, false>(sdp_lds.ad, utab, filt, lead1, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, &b_max);
-                else if (axis_mode == 1) sdp_short_bnb<1, false>(sdp_lds.ad, utab, filt, lead1, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, &b_max);
-                else sdp_short_bnb<0, false>(sdp_lds.ad, utab, filt, lead1, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, &b_max);
+                if (axis_mode == 2) sdp_short_bnb<2, false>(SDP_LDS_AD, utab, filt, lead1, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, &b_max);
+                else if (axis_mode == 1) sdp_short_bnb<1, false>(SDP_LDS_AD, utab, filt, lead1, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, &b_max);
+                else sdp_short_bnb<0, false>(SDP_LDS_AD, utab, filt, lead1, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, &b_max);
             } else
 #endif
             {
-                if (axis_mode == 2) sdp_lean2s_pass1<2>(sdp_lds.ad, utab, filt, lead1, X, box.total, mask, bd.f1, bd.f2, bd.f3, b_max);
-                else if (axis_mode == 1) sdp_lean2s_pass1<1>(sdp_lds.ad, utab, filt, lead1, X, box.total, mask, bd.f1, bd.f2, bd.f3, b_max);
-                else sdp_lean2s_pass1<0>(sdp_lds.ad, utab, filt, lead1, X, box.total, mask, bd.f1, bd.f2, bd.f3, b_max);
+                if (axis_mode == 2) sdp_lean2s_pass1<2>(SDP_LDS_AD, utab, filt, lead1, X, box.total, mask, bd.f1, bd.f2, bd.f3, b_max);
+                else if (axis_mode == 1) sdp_lean2s_pass1<1>(SDP_LDS_AD, utab, filt, lead1, X, box.total, mask, bd.f1, bd.f2, bd.f3, b_max);
+                else sdp_lean2s_pass1<0>(SDP_LDS_AD, utab, filt, lead1, X, box.total, mask, bd.f1, bd.f2, bd.f3, b_max);
             }
             // (b_max: the largest B' among the controls the pass evaluated -- the ones it skipped are ruled out with their own)
             const sdp_real radius = fma((sdp_real)(SDP_COL_FILTER_SCALE), b_max, radius0);
@@ -632,22 +661,29 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
             // a block is skipped when its lower bound exceeds f1 by more than 2 radius + 16 u S_node (8 x EPS = 16 u).
             // Only where the column's blocks are in order and |X| is small enough for the bounds' positions (ust[3]:
             // sdp_col_phase_u); a wave with a node that does not qualify takes the full pass.
-            const sdp_real slack = fma((sdp_real)2, radius, ((sdp_real)8 * SDP_COL_FILTER_EPS) * s_node);
+            // (the uniform bound stage: 8 u S_node more for the roundings of the padded rows it reads)
+            const sdp_real slack = fma((sdp_real)2, radius, ((sdp_real)(SDP_BNB_UNIFORM_ON ? 12 : 8) * SDP_COL_FILTER_EPS) * s_node);
+#if SDP_BNB_UNIFORM_ON
+            // .. and where this lane's node sits at its own row: the position as the bound stage forms it, against the row
+            const bool bnb = fabs(X) < ust[3] && fabs((X - lead.smin) * k_rows - (sdp_real)i) <= (sdp_real)0x1p-22;
+#else
             const bool bnb = fabs(X) < ust[3];
+#endif
+            const int row_u = i;
             if (__all(bnb)) {                                  // (over the lanes that have a node)
                 auto ins = [&](double Fq) {
                     bd.f2 = sdp_vmin(bd.f2, sdp_vmax(bd.f1, Fq));
                     bd.f1 = sdp_vmin(bd.f1, Fq);
                 };
-                if (axis_mode == 2) sdp_short_bnb<2, false>(sdp_lds.ad, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt);
-                else if (axis_mode == 1) sdp_short_bnb<1, false>(sdp_lds.ad, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt);
-                else sdp_short_bnb<0, false>(sdp_lds.ad, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt);
+                if (axis_mode == 2) sdp_short_bnb<2, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u);
+                else if (axis_mode == 1) sdp_short_bnb<1, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u);
+                else sdp_short_bnb<0, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u);
             } else
 #endif
             {
-                if (axis_mode == 2) sdp_lean2_pass1<2>(sdp_lds.ad, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
-                else if (axis_mode == 1) sdp_lean2_pass1<1>(sdp_lds.ad, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
-                else sdp_lean2_pass1<0>(sdp_lds.ad, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
+                if (axis_mode == 2) sdp_lean2_pass1<2>(SDP_LDS_AD, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
+                else if (axis_mode == 1) sdp_lean2_pass1<1>(SDP_LDS_AD, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
+                else sdp_lean2_pass1<0>(SDP_LDS_AD, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
             }
             bd.i1 = bd.f1 < (sdp_real)INFINITY ? (__double2loint(bd.f1) & mask) : INT_MAX;
 #else
@@ -658,13 +694,13 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
             const sdp_real *utab = sdp_lds.utab[upar];
             const bool plain = SDP_NU == 1 && box.n[0] > 1 && box.step[0] != (sdp_real)0;
             if (plain) {
-                if (axis_mode == 2) sdp_col_filter_pass1<true, 2>(sdp_lds.ad, utab, filt, lead1, box, x, t, 0, box.total, bd);
-                else if (axis_mode == 1) sdp_col_filter_pass1<true, 1>(sdp_lds.ad, utab, filt, lead1, box, x, t, 0, box.total, bd);
-                else sdp_col_filter_pass1<true, 0>(sdp_lds.ad, utab, filt, lead1, box, x, t, 0, box.total, bd);
+                if (axis_mode == 2) sdp_col_filter_pass1<true, 2>(SDP_LDS_AD, utab, filt, lead1, box, x, t, 0, box.total, bd);
+                else if (axis_mode == 1) sdp_col_filter_pass1<true, 1>(SDP_LDS_AD, utab, filt, lead1, box, x, t, 0, box.total, bd);
+                else sdp_col_filter_pass1<true, 0>(SDP_LDS_AD, utab, filt, lead1, box, x, t, 0, box.total, bd);
             } else {
-                if (axis_mode == 2) sdp_col_filter_pass1<false, 2>(sdp_lds.ad, utab, filt, lead1, box, x, t, 0, box.total, bd);
-                else if (axis_mode == 1) sdp_col_filter_pass1<false, 1>(sdp_lds.ad, utab, filt, lead1, box, x, t, 0, box.total, bd);
-                else sdp_col_filter_pass1<false, 0>(sdp_lds.ad, utab, filt, lead1, box, x, t, 0, box.total, bd);
+                if (axis_mode == 2) sdp_col_filter_pass1<false, 2>(SDP_LDS_AD, utab, filt, lead1, box, x, t, 0, box.total, bd);
+                else if (axis_mode == 1) sdp_col_filter_pass1<false, 1>(SDP_LDS_AD, utab, filt, lead1, box, x, t, 0, box.total, bd);
+                else sdp_col_filter_pass1<false, 0>(SDP_LDS_AD, utab, filt, lead1, box, x, t, 0, box.total, bd);
             }
             // the radius of the lean first pass (sdp_col_lean_core), on the shifted lattice with its H and B' (sdp_col_shift_reduce)
 #if SDP_COL_SHIFT
@@ -712,15 +748,15 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
                     if (!cand) {
 #if SDP_COL_LEAN2 && SDP_COL_SHIFT
                         sdp_real b_unused = (sdp_real)0;       // (the radius holds the largest B' of the node already)
-                        const sdp_real F = lead.pow2 ? sdp_lean2s_value<1>(sdp_lds.ad, utab, filt, lead1, X, ci, b_unused)
-                                                     : sdp_lean2s_value<0>(sdp_lds.ad, utab, filt, lead1, X, ci, b_unused);
+                        const sdp_real F = lead.pow2 ? sdp_lean2s_value<1>(SDP_LDS_AD, utab, filt, lead1, X, ci, b_unused)
+                                                     : sdp_lean2s_value<0>(SDP_LDS_AD, utab, filt, lead1, X, ci, b_unused);
 #elif SDP_COL_LEAN2
-                        const sdp_real F = lead.pow2 ? sdp_lean2_value<1>(sdp_lds.ad, utab, filt, lead, X, ci)
-                                                     : sdp_lean2_value<0>(sdp_lds.ad, utab, filt, lead, X, ci);
+                        const sdp_real F = lead.pow2 ? sdp_lean2_value<1>(SDP_LDS_AD, utab, filt, lead, X, ci)
+                                                     : sdp_lean2_value<0>(SDP_LDS_AD, utab, filt, lead, X, ci);
 #else
                         sdp_real F, pm = (sdp_real)0, gm = (sdp_real)0, bm = (sdp_real)0;
-                        if (lead.pow2) sdp_col_lean_eval<1>(sdp_lds.ad, filt, lead1, x, u, t, F, pm, gm, bm);
-                        else sdp_col_lean_eval<0>(sdp_lds.ad, filt, lead1, x, u, t, F, pm, gm, bm);
+                        if (lead.pow2) sdp_col_lean_eval<1>(SDP_LDS_AD, filt, lead1, x, u, t, F, pm, gm, bm);
+                        else sdp_col_lean_eval<0>(SDP_LDS_AD, filt, lead1, x, u, t, F, pm, gm, bm);
 #endif
                         cand = !(F - radius > m_hi);
                     }

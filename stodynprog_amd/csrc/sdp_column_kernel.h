@@ -209,6 +209,28 @@
 // twice the radius holds no survivor, and its controls are never evaluated.  0: every control (round 4; A/B runs)
 #define SDP_COL_BNB 0
 #endif
+#ifndef SDP_BNB_UNIFORM
+#define SDP_BNB_UNIFORM 0        // generated (codegen.uniform_rows_axis): the stock axis is a uniform grid, node r sits at row r
+#endif
+// The UNIFORM bound stage of the branch and bound (sdp_short_bnb): where node r of the column sits at row r of axis 0, the
+// block ends of lane r lie at r + s_b with s_b the same in every lane -- whole part and fraction are made once per control
+// table, and the reduced table is padded by SDP_BNB_PAD rows of its linear continuation on either side instead of clamped
+// cells.  8-byte reals (SDP_COL_LEAN2), not the shifted lattice, x0' = X +- a; the two rows either end is continued from
+// are reduced by threads of one wave.  Such a unit holds this bound stage ALONE: a wave whose nodes fail the kernel's own
+// check of the plan's claim, or a column whose lattice reaches past the padding, takes the full first pass.
+// (its records, in the half of the block records that 8-byte reals leave unused: the byte offsets 8 k_b of the ends as
+// integers, then their fractions phi_b -- `rec`: the block records, sdp_col_phase_u)
+#define SDP_BNB_UNI_K(rec) ((int *)((rec) + 2 * (SDP_BNB_BLOCKS + 1)))
+#define SDP_BNB_UNI_PHI(rec) ((rec) + 2 * (SDP_BNB_BLOCKS + 1) + (SDP_BNB_BLOCKS + 2) / 2)
+#ifndef SDP_BNB_PAD_ROWS
+#define SDP_BNB_PAD_ROWS 0       // generated (codegen.column_config): rows the reduced table is padded by on either side
+#endif
+#if SDP_BNB_UNIFORM && SDP_BNB_PAD_ROWS > 0 && SDP_COL_LEAN2 && SDP_COL_BNB && !SDP_COL_SHIFT && SDP_LEAN2_FORM != 2 && \
+    SDP_COL_WRES < SDP_COL_W && SDP_COL_N0 >= 2 && (SDP_COL_N0 - 1) % 64 != 0
+#define SDP_BNB_UNIFORM_ON 1
+#else
+#define SDP_BNB_UNIFORM_ON 0
+#endif
 // controls per block of the branch and bound, and the block statistics kept beside the control table (four reals per
 // block: smallest a, largest a, smallest +-h psum, unused): at most 64 blocks -- one lane of the table's wave each
 #ifndef SDP_LEAN2_A_FIXED
@@ -284,6 +306,9 @@ constexpr int SDP_BNB_WORDS = SDP_COL_UTAB ? 4 * (SDP_BNB_BLOCKS + 1) : 0;      
 #define SDP_AD_A(ad, r) (SDP_COL_WIDE2 ? ((double *)(ad))[(r)] : *(double *)((ad) + 4 * (r)))
 #define SDP_AD_A_CONST(ad, r) (SDP_COL_WIDE2 ? ((const double *)(ad))[(r)] : *(const double *)((ad) + 4 * (r)))
 constexpr int SDP_COL_LDS_AD = sizeof(SDP_REAL) == 4 ? 4 : (!SDP_COL_SHIFT ? 1 : 2);
+// rows the reduced table is padded by on either side (what codegen._column_lds counts; the uniform bound stage fills and
+// reads them, every other reader starts at row 0)
+constexpr int SDP_BNB_PAD = (SDP_COL_FILTER && !SDP_COL_SHIFT) ? SDP_BNB_PAD_ROWS : 0;
 struct __attribute__((aligned(16))) SdpColLds {
     sdp_real T[(SDP_TRAIL_HAS_U ? SDP_COL_WCHUNK : (SDP_COL_WRES < SDP_COL_W ? SDP_COL_WRES : SDP_COL_TW)) * SDP_COL_ROWS];
     sdp_real w_lam[SDP_COL_W * SDP_DT];
@@ -302,7 +327,7 @@ struct __attribute__((aligned(16))) SdpColLds {
 #if SDP_COL_FILTER
     // filter: per row r of axis 0 A[r] = sum_w p_w T[w][r] (shifted lattice: the pair (A'[k], B'[k]) per position)
     // (wide first pass of 4-byte reals: 16 bytes per row -- A[r] as a double, then the bound B[r])
-    sdp_real ad[SDP_COL_LDS_AD * (SDP_COL_SHIFT ? SDP_COL_SHIFT_ROWS : SDP_COL_ROWS)] __attribute__((aligned(16)));
+    sdp_real ad[SDP_COL_LDS_AD * (SDP_COL_SHIFT ? SDP_COL_SHIFT_ROWS : SDP_COL_ROWS) + 2 * SDP_BNB_PAD] __attribute__((aligned(16)));
 #endif
 #if SDP_COL_SHIFT
     // per parity of the unit: the shift of every perturbation point in rows of axis 0 -- whole part, fraction

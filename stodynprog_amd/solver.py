@@ -753,7 +753,7 @@ class DPSolver(object):
         # with the time index gets a control table with room to spare (a capacity, checked by the library as
         # controls <= capacity), so that the steps of a horizon keep sharing one code object.
         n_controls = bp['max_u'] if box_t is None else 1 << max(int(bp['max_u']) - 1, 0).bit_length()
-        col_cfg, utab, wres = None, None, 0
+        col_cfg, utab, wres, bnb_pad = None, None, 0, 0
         if self.kernel in ('auto', 'column') and model.storage_separable:
             wpair = codegen.use_wpair(model, dt, debug)
             shift = bool(may_filter and codegen.column_shift_applies(model, dt, debug=debug))
@@ -768,7 +768,17 @@ class DPSolver(object):
                     wres = codegen.column_resident_points(model, shape[0], W, len(shape), dt, may_filter, shift, wpair,
                                                           col_cfg[0], kw['utab_values'], debug)
                     if wres:
+                        # (a uniform stock axis under x0' = x0 +- a: the branch and bound's uniform bound stage, which pads
+                        # the reduced table where that costs the CU no workgroup)
                         col_cfg = codegen.column_config(shape[0], W, len(shape), dt, wpair, may_filter, wres=wres, **kw)
+                        if col_cfg is not None and not bp['per_node']:
+                            # (the lattice of every control as the kernels form it: n points from lo to hi, sdp_control_value)
+                            lattice = [np.linspace(float(bp['lo'][c, 0]), float(bp['hi'][c, 0]), int(bp['n'][c, 0]))
+                                       for c in range(bp['lo'].shape[0])]
+                            bnb_pad = codegen.uniform_stage_pad(model, dt, frontier, self.state_grid[0], shape[0], lattice,
+                                                                wres, shift, col_cfg[0], col_cfg[1], debug)
+                            if bnb_pad:            # (the padded reduced table is the last member of the image)
+                                col_cfg = (col_cfg[0], col_cfg[1] + 2 * bnb_pad * np.dtype(dt).itemsize) + tuple(col_cfg[2:])
                     break
         column = col_cfg is not None
         # several controlled state variables next to an exogenous process: the node-order sweep with the
@@ -880,7 +890,8 @@ class DPSolver(object):
                                           window=window, per_control=per_control_cfg if per_control else None,
                                           filtered=filtered, utab=utab, lead_axes=lead_axes,
                                           col_cfg=col_cfg, debug=debug, wres=wres if filtered else 0,
-                                          lead_perm=lead_perm, line=line, peer_stores=self._plans_direct_exchange())
+                                          lead_perm=lead_perm, line=line, peer_stores=self._plans_direct_exchange(),
+                                          bnb_pad=bnb_pad if (filtered and wres and utab is not None) else 0)
         filtered = filtered or bool(lead_axes) or bool(line)
         return dict(model=model, source=source, column=column, lanes=lanes, staged=staged, filtered=filtered,
                     lead_axes=lead_axes, lead_perm=lead_perm, line=bool(line),
