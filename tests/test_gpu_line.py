@@ -7,47 +7,12 @@ import pytest
 
 from stodynprog_amd import SysDescription, DPSolver, models
 from oracle import vi_numpy
+from line_forms import shop, chain, same, V_OF
 
 pytestmark = pytest.mark.gpu
 
 
-def shop(n_x=600, n_u=257, n_w=16, dyn=None, cost=None, box=None, grid=(-8., 24.), wgrid=(0., 4.), law=None, steps=None):
-    sysd = SysDescription((1, 1, 1), name='shop')
-    sysd.dyn = dyn or (lambda x, u, w: (x + u - w,))
-    sysd.cost = cost or (lambda x, u, w: np.where(x > 0, x * 0.5, -x * 3.) + u * 1.)
-    sysd.control_box = box or (lambda x: ((0., 8.),))
-    sysd.perturb_laws = [law or models.NormalLaw(2.0, 0.8)]
-    s = DPSolver(sysd)
-    s.discretize_state(grid[0], grid[1], n_x)
-    s.discretize_perturb(wgrid[0], wgrid[1], n_w)
-    s.control_steps = steps or (8. / (n_u - 1),)
-    return s
-
-
-def chain(make, kernel, V0, sweeps=3, debug=None):
-    s = make()
-    s.kernel = kernel
-    s.debug_defines = debug
-    out, V = [], V0
-    with np.errstate(all='ignore'):
-        for _ in range(sweeps):
-            J, pol = s.value_iteration(V, report_time=False)
-            out.append((J.copy(), pol.copy(), s.last_policy_index.copy()))
-            V = J
-    return out, s.backend_info
-
-
-def same(a, b):
-    return all(np.array_equal(x[0], y[0], equal_nan=True) and np.array_equal(x[1], y[1], equal_nan=True) and np.array_equal(x[2], y[2])
-               for x, y in zip(a, b))
-
-
-V_OF = {
-    'zeros': lambda x, rng: np.zeros_like(x),
-    'smooth': lambda x, rng: 0.3 * (x - 3) ** 2 + np.sin(x),
-    'random': lambda x, rng: rng.standard_normal(x.size),
-    'kinked': lambda x, rng: np.abs(x - 1.3) * 2 + np.maximum(x - 7, 0) ** 2,
-}
+# (the shop model, chain(), same() and V_OF live with the table of line-kernel cases, which tests/test_gpu_line_forms.py runs)
 
 
 @pytest.mark.parametrize('vname', sorted(V_OF))
