@@ -8,6 +8,7 @@ csrc/sdp_sweep_kernel.h.  The unit is compiled to a gfx950 code object with
 so that every operator is one IEEE operation, as in numpy on the host
 (reference stodynprog.py:674-677 evaluates the same expressions with numpy).
 """
+import collections
 import hashlib
 import re
 import math
@@ -536,150 +537,116 @@ def uniform_stage_reach(model, frontier, lattice, k_rows):
     return float(a.max()) * abs(float(k_rows))
 
 
-def uniform_stage_pad(model, dtype, frontier, axis, n0, lattice, wres, shift, threads, lds, debug=None):
+def uniform_stage_pad(model, dtype, unit, axis, box):
     """THE place that decides the uniform bound stage of the branch and bound (SDP_BNB_UNIFORM of
     csrc/sdp_colfilter_kernel.h): the rows the reduced table is padded by on either side -- BNB_PAD where a unit plans
-    the stage, 0 where it keeps the bound stage that locates every block end per node.  Planned only when ALL hold:
-    the resident-chunk form (`wres`) of 8-byte reals with the short first pass and its branch and bound, not the
-    shifted lattice; x0' = x0 +- a(u) with a control table (`uniform_stage_model`); a stock axis on which every node
-    provably sits at its row (`uniform_rows_axis`); the two rows either end of the table is continued from reduced by
-    one wave ((n0 - 1) % 64 != 0); a lattice (`lattice`: the values of every control) whose reach, max |a| k rows plus
-    the cell partner, the end's margin and the row below, fits the padding; and 2 BNB_PAD rows more that cost the CU no
-    workgroup (`threads`, `lds`: the shape planned without them).  The kernel checks rows and reach again where it
-    runs (a failure there is the full first pass): with this plan neither fails.
-    (`debug`: SDP_COL_LEAN2 / SDP_COL_BNB = 0 take the short pass away; SDP_BNB_UNIFORM = 0 keeps the PADDING and
-    leaves the stage out -- the A/B switch, decided by `_column_lines`.)"""
+    the stage, 0 where it keeps the bound stage that locates every block end per node.  `unit`: the ColumnUnit as
+    `column_table_unit` has planned it so far, without the padding.  Planned only when ALL hold: the short first pass
+    of the resident-chunk form with its branch and bound (`unit.short`, `unit.bnb`), not the shifted lattice;
+    x0' = x0 +- a(u) (`uniform_stage_model`); a stock axis on which every node provably sits at its row
+    (`uniform_rows_axis`); the two rows either end of the table is continued from reduced by one wave
+    ((n0 - 1) % 64 != 0); a control lattice (`box`: the table of admissible boxes, the same at every node where a unit
+    has a control table) whose reach, max |a| k rows plus the cell partner, the end's margin and the row below, fits
+    the padding; and 2 BNB_PAD rows more that cost the CU no workgroup.  The kernel checks rows and reach again where
+    it runs (a failure there is the full first pass): with this plan neither fails."""
     rs = np.dtype(dtype).itemsize
-    n0 = int(n0)
-    if not wres or shift or rs != 8 or frontier is None or model.cost_depends_on_w:
+    n0 = unit.n0
+    if unit.short != 'lean2' or not unit.bnb or unit.shift:
         return 0
-    if _dbg(debug, 'SDP_COL_LEAN2') == '0' or _dbg(debug, 'SDP_COL_BNB') == '0':
-        return 0
-    if n0 < 2 or (n0 - 1) % 64 == 0 or not uniform_stage_model(model, frontier):
+    if n0 < 2 or (n0 - 1) % 64 == 0 or not uniform_stage_model(model, unit.frontier):
         return 0
     if not uniform_rows_axis(axis, dtype, n0):
         return 0
     x = np.asarray(axis, dtype=np.float64).ravel()
-    reach = uniform_stage_reach(model, frontier, lattice, np.float64(n0 - 1) / (x[-1] - x[0]))
+    # (the lattice of every control as the kernels form it: n points from lo to hi, sdp_control_value)
+    lattice = [np.linspace(float(box['lo'][c, 0]), float(box['hi'][c, 0]), int(box['n'][c, 0]))
+               for c in range(box['lo'].shape[0])]
+    reach = uniform_stage_reach(model, unit.frontier, lattice, np.float64(n0 - 1) / (x[-1] - x[0]))
     if reach is None or not reach * (1.0 + 2.0 ** -30) + 2.0 ** -19 <= BNB_PAD - 3:
         return 0
-    per_cu = lambda size: min(COLUMN_LDS_MAX // size, max(1, 2048 // int(threads)))      # (LDS, and 32 waves per CU)
-    if per_cu(int(lds) + 2 * BNB_PAD * rs) != per_cu(int(lds)):
+    per_cu = lambda size: min(COLUMN_LDS_MAX // size, max(1, 2048 // unit.threads))      # (LDS, and 32 waves per CU)
+    if per_cu(unit.lds_bytes + 2 * BNB_PAD * rs) != per_cu(unit.lds_bytes):
         return 0
     return BNB_PAD
 
 
-def _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, utab, debug, wres=0, bnb_pad=0):
-    """the macros and model slices of a unit that includes csrc/sdp_column_kernel.h"""
-    rs = np.dtype(dtype).itemsize
-    wpair = use_wpair(model, dtype, debug) and window is None
-    shifted = bool(filtered and column_shift_applies(model, dtype, debug=debug))
+def shift_chain(model):
+    """additions of a chain of sums that the shifted lattice regrouped (SDP_COL_SHIFT_CHAIN / SDP_LINE_CHAIN; 0: the
+    final-sum form)"""
+    chain = model.lead_split_chain()
+    return chain[1] if chain is not None else 0
+
+
+def _column_lines(model, dtype, unit, debug):
+    """the macros and model slices of a unit that includes csrc/sdp_column_kernel.h: `unit` (a ColumnUnit) printed as
+    it was planned -- nothing is decided here"""
     lines = ['#define SDP_COST_HAS_W {}'.format(1 if model.cost_depends_on_w else 0),
              '#define SDP_LEAD_HAS_W {}'.format(1 if model.lead_depends_on_w else 0),
              '#define SDP_TRAIL_HAS_U {}'.format(1 if model.trail_depends_on_u else 0),
-             '#define SDP_COL_N0 {}'.format(int(column[0])),
-             '#define SDP_COL_W {}'.format(max(int(column[1]), 1)),
-             '#define SDP_COL_THREADS {}'.format(col_cfg[0]),
-             '#define SDP_COL_WPAIR {}'.format(1 if wpair else 0)]
-    if wres:
-        lines.append('#define SDP_COL_WRES {}         // resident-chunk form: perturbation points the table holds at a time'.format(int(wres)))
-        if rs == 8 and shifted and not _dbg(debug, 'SDP_COL_UNROLL_W'):
-            # the second pass of the shifted lattice's resident-chunk kernel one batch of perturbation points at a time: unrolled
-            # four times it kept 8 points' cells, table entries and weights per survivor in flight (two survivors in half of the
-            # waves), in registers the kernel does not have at three waves per SIMD -- round 6, same box: 2.45 -> 2.23 ms, and
-            # with the tail held on top 2.12 ms (boxes 9-11 of profiles/r06_column_ab.txt: 48 -> 22 spilled registers).  The
-            # benchmark's kernel (no cell per point, one survivor) does not care: 948.8 against 954.3 sweeps/s over 50 steps
-            # (box 20; the 5 % of box 12 were the A/B tool's first-position penalty); 4-byte reals: 7.51 against 7.72 ms.
-            lines.append('#define SDP_COL_UNROLL_W 1')
-    if filtered and int(col_cfg[0]) <= 256 and not _dbg(debug, 'SDP_COL_MIN_WAVES'):
-        if wres:
-            # (at most 4: 128 registers per lane.  Round 4 asked for up to 8 for small tables -- 64 registers, which these
-            # kernels do not fit in: 90 - 200 spilled registers in the suite's small models, and spill code the compiler
-            # got wrong, see spill_hazards)
-            lines.append('#define SDP_COL_MIN_WAVES {}    // as many waves per SIMD as the LDS image admits workgroups per CU, at most 4'.format(
-                max(1, min(4, (COLUMN_LDS_MAX // int(col_cfg[1])) * int(col_cfg[0]) // 256))))
-        else:
-            lines.append('#define SDP_COL_MIN_WAVES 1    // small workgroups of the filtered kernel: no register cap')
-    if filtered:
+             '#define SDP_COL_N0 {}'.format(unit.n0),
+             '#define SDP_COL_W {}'.format(max(unit.w, 1)),
+             '#define SDP_COL_THREADS {}'.format(unit.threads),
+             '#define SDP_COL_WPAIR {}'.format(1 if unit.wpair else 0)]
+    if unit.wres:
+        lines.append('#define SDP_COL_WRES {}         // resident-chunk form: perturbation points the table holds at a time'.format(unit.wres))
+    if unit.unroll_w:
+        lines.append('#define SDP_COL_UNROLL_W {}'.format(unit.unroll_w))
+    if unit.min_waves and unit.wres:
+        lines.append('#define SDP_COL_MIN_WAVES {}    // as many waves per SIMD as the LDS image admits workgroups per CU, at most 4'.format(
+            unit.min_waves))
+    elif unit.min_waves:
+        lines.append('#define SDP_COL_MIN_WAVES {}    // small workgroups of the filtered kernel: no register cap'.format(unit.min_waves))
+    if unit.filtered:
         lines.append('#define SDP_COL_FILTER 1')
-        if shifted:
+        if unit.shift:
             lines += ['#define SDP_COL_SHIFT 1        // x0\' = a(x, u) +- b_1(x_1.., w) +- ..: first pass on the shifted lattice',
                       '#define SDP_COL_SHIFT_TERMS {}'.format(len(model.lead_split()[1])),
                       '#define SDP_COL_SHIFT_CHAIN {}        // additions of a chain of sums that was regrouped (0: the final-sum form)'.format(
-                          model.lead_split_chain()[1] if model.lead_split_chain() is not None else 0),
-                      '#define SDP_COL_SHIFT_ROWS {}'.format(int(col_cfg[2]))]
+                          shift_chain(model)),
+                      '#define SDP_COL_SHIFT_ROWS {}'.format(unit.shift_rows)]
         if _dbg(debug, 'SDP_COL_FILTER_SCALE'):
             lines.append('#define SDP_COL_FILTER_SCALE {}'.format(float(_dbg(debug, 'SDP_COL_FILTER_SCALE'))))
-    # how the table build deals its entries to the threads
-    if per_control is None:
-        wide = column_wide_loads(column[0], dtype, window, debug)
-        order = column_build_order(int(col_cfg[0]), column[1], int(window[2]) if window is not None else column[0],
-                                   (16 // rs) if wide else 1)
-        if order[0] == 2:
-            lw = int(_dbg(debug, 'SDP_COL_A_LW') or order[1])
-            lines += ['#define SDP_COL_A_ORDER 2',
-                      '#define SDP_COL_A_LW {}'.format(lw)]
-            if rs == 4 and int(column[0]) >= 512 and not wres and window is None and not _dbg(debug, 'SDP_COL_A_GROUP'):
-                # (config 5, 512^3 in 4-byte reals, same box: 7.50 -> 7.36 ms, with four blocks' bounds per stage of
-                # the branch and bound 7.24 ms -- boxes 25-26 of profiles/r06_column_ab.txt; 8-byte reals: worse)
-                lines.append('#define SDP_COL_A_GROUP 8      // table entries per thread whose vertex loads are issued together')
-            if wide and not _dbg(debug, 'SDP_COL_A_WIDE_LOADS'):
-                lines.append('#define SDP_COL_A_WIDE_LOADS 1')
-
-                # resident chunks: the tail is built once, its entries wait in the registers of the threads that made
-                # them (SDP_COL_TAIL_HOLD of csrc/sdp_colres_kernel.h; round 6: 1.235 -> 1.048 ms on the benchmark, same
-                # bits) -- where they are whole rounds of points and rows and at most 32 registers per thread
-                # (on the shifted lattice too since the second pass is no longer unrolled there: 2.23 -> 2.12 ms, box 11 of
-                # profiles/r06_column_ab.txt; with the unrolled pass it had lost, 2.96 against 2.71 ms)
-                if wres and rs == 8 and not wpair and window is None and _dbg(debug, 'SDP_COL_TAIL_HOLD') is None:
-                    tail, groups = int(column[1]) - int(wres), int(col_cfg[0]) // lw
-                    if (tail > 0 and tail % groups == 0 and int(column[0]) % (2 * lw) == 0
-                            and (tail // groups) * (int(column[0]) // (2 * lw)) * 4 <= 32):
-                        lines.append('#define SDP_COL_TAIL_HOLD 1    // the tail of the table is built once and held in registers')
-    if window is not None:
-        lines.append('#define SDP_COL_ROWS {}'.format(int(window[2])))
-    if per_control is not None:
-        lines.append('#define SDP_COL_WCHUNK {}'.format(int(per_control[2])))
-        if int(column[0]) % (16 // rs) == 0 and not _dbg(debug, 'SDP_COLU_WIDE_LOADS'):
+    if unit.a_lw:                 # how the table build deals its entries to the threads (else round-robin)
+        lines += ['#define SDP_COL_A_ORDER 2',
+                  '#define SDP_COL_A_LW {}'.format(unit.a_lw)]
+        if unit.a_group:
+            lines.append('#define SDP_COL_A_GROUP {}      // table entries per thread whose vertex loads are issued together'.format(unit.a_group))
+        if unit.wide_loads:
+            lines.append('#define SDP_COL_A_WIDE_LOADS 1')
+        if unit.tail_hold:
+            lines.append('#define SDP_COL_TAIL_HOLD 1    // the tail of the table is built once and held in registers')
+    if unit.form == 'row window':
+        lines.append('#define SDP_COL_ROWS {}'.format(unit.window_rows))
+    if unit.form == 'table per control':
+        lines.append('#define SDP_COL_WCHUNK {}'.format(unit.wchunk))
+        if unit.colu_wide_loads:
             lines.append('#define SDP_COLU_WIDE_LOADS 1')
     for k in DEBUG_INT_MACROS:                                   # tuning knobs of A/B runs (explicit dict only)
         if _dbg(debug, k):
             lines.append('#define {} {}'.format(k, int(_dbg(debug, k))))
     lines += [separable_functions_source(model), '']
-    if utab is not None and filtered:
-        lines += ['#define SDP_COL_UTAB {}'.format(len(utab[0])),
-                  '#define SDP_COL_UTAB_N {}'.format(int(utab[1])),
-                  control_table_source(model, utab[0]), '']
-        # the short first passes: 8-byte reals in the resident-chunk kernel, 4-byte reals (wide form) in the full-table one
-        short = None
-        if not model.cost_depends_on_w and window is None and per_control is None \
-                and _dbg(debug, 'SDP_COL_LEAN2') != '0' and (not shifted or rs == 8):
-            # (round 6: on the shifted lattice too -- final sums only, additive_control_split)
-            if rs == 8 and wres:
-                short = short_pass_source(model, utab[0], 'SDP_COL_LEAN2')
-                if short and _dbg(debug, 'SDP_COL_BNB') != '0':
-                    short += ('\n#define SDP_COL_BNB 1          // the short first pass as a certified branch and bound over '
-                              'blocks of controls (sdp_lean2_bnb)')
-                    # (X of x0' = X +- a must be the stock itself: a node of row r then sits at row r in every column, at every
-                    # time index; the kernel checks the rows node by node all the same)
-                    if bnb_pad:                # (uniform_stage_pad: the plan; the LDS image counts these rows)
-                        short += '\n#define SDP_BNB_PAD_ROWS {}    // the reduced table continued linearly on either side'.format(
-                            int(bnb_pad))
-                        if _dbg(debug, 'SDP_BNB_UNIFORM') != '0':
-                            short += uniform_define
-                        bnb_pad = 0
-
-            elif rs == 4 and not wres and _dbg(debug, 'SDP_COL_FILTER_TOP2') in (None, '1'):
-                short = short_pass_source(model, utab[0], 'SDP_COL_WIDE2')
-                if short and _dbg(debug, 'SDP_COL_BNB') != '0':
-                    short += ('\n#define SDP_COL_BNB 1          // the short wide first pass as a certified branch and bound over '
-                              'blocks of controls (sdp_short_bnb)')
-                    if int(column[0]) >= 512 and not _dbg(debug, 'SDP_BNB_CHUNK'):
-                        short += '\n#define SDP_BNB_CHUNK 4        // blocks whose bounds are evaluated together (see SDP_COL_A_GROUP above)'
-        if short:
-            lines += [short, '']
-    if bnb_pad:
-        raise ValueError('a padded reduced table was planned for a unit without the branch and bound of the short first pass')
+    if unit.frontier is not None:
+        lines += ['#define SDP_COL_UTAB {}'.format(len(unit.frontier)),
+                  '#define SDP_COL_UTAB_N {}'.format(unit.utab_n),
+                  control_table_source(model, unit.frontier), '']
+    if unit.short == 'lean2':
+        short = short_pass_source(model, unit.frontier, 'SDP_COL_LEAN2')
+        if unit.bnb:
+            short += ('\n#define SDP_COL_BNB 1          // the short first pass as a certified branch and bound over '
+                      'blocks of controls (sdp_lean2_bnb)')
+        if unit.bnb_pad:               # (uniform_stage_pad: the LDS image counts these rows)
+            short += '\n#define SDP_BNB_PAD_ROWS {}    // the reduced table continued linearly on either side'.format(unit.bnb_pad)
+        if unit.uniform:
+            short += uniform_define
+        lines += [short, '']
+    elif unit.short == 'wide2':
+        short = short_pass_source(model, unit.frontier, 'SDP_COL_WIDE2')
+        if unit.bnb:
+            short += ('\n#define SDP_COL_BNB 1          // the short wide first pass as a certified branch and bound over '
+                      'blocks of controls (sdp_short_bnb)')
+        if unit.bnb_chunk:
+            short += '\n#define SDP_BNB_CHUNK {}        // blocks whose bounds are evaluated together (see SDP_COL_A_GROUP above)'.format(unit.bnb_chunk)
+        lines += [short, '']
     lines += ['#include "sdp_column_kernel.h"    // also brings in sdp_sweep_kernel.h', '']
     return lines
 
@@ -735,51 +702,29 @@ def line_functions_source(model):
     return '\n\n'.join(out)
 
 
-def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
-                     per_control=None, filtered=False, utab=None, lead_axes=0, col_cfg=None, debug=None, wres=0,
-                     lead_perm=None, line=0, peer_stores=False, bnb_pad=0):
-    """column: None for the generic node-order kernels, or (N0, W[, controls, columns]) to also
-    build the column kernels of csrc/sdp_column_kernel.h for a storage-separable
-    model on a grid with N0 points along axis 0 and W perturbation points.
-    col_cfg: the tuple `column_config` returned for exactly this unit (the caller plans once and
-    hands the plan over; None: planned here, same arguments).
-    staged: None, or the dict of `staged_config` to also build the LDS-staged
-    generic kernel of csrc/sdp_staged_kernel.h (node order, any traceable model).
-    window: None, or the tuple of `column_window_config` (column kernel whose
-    table holds a window of rows of axis 0).
-    per_control: None, or the tuple of `column_percontrol_config` (column kernel
-    that rebuilds its table for every control).
-    filtered: column kernel with the certified expectation-first filter (SDP_COL_FILTER of
-    csrc/sdp_colfilter_kernel.h; see `column_filter_applies`).
-    utab: None, or (frontier nodes, capacity of the control table in controls) of `control_table_plan`
-    (filtered kernel only): the first pass reads the column-uniform sub-expressions from a table.
+def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False):
+    """The generated source of one model code object.  `family`: what the unit is to hold beside the direct node-order
+    kernels of csrc/sdp_sweep_kernel.h --
+    None: nothing else;
+    a ColumnUnit (`column_table_unit`, `column_percontrol_unit`, `column_window_unit`): the column kernels of
+    csrc/sdp_column_kernel.h, printed as the record says;
+    a dict of `staged_config`: the LDS-staged generic kernel of csrc/sdp_staged_kernel.h (node order, any traceable model);
+    a pair (lead_axes, lead_perm) of `lead_filter_applies` / `lead_order`: the reduced-array sweep of
+    csrc/sdp_lead_kernel.h (lead_perm None: the stocks are listed first);
+    an int W: the line kernel of csrc/sdp_line_kernel.h on W perturbation points.
     debug: None (the product), or a dict of diagnostic switches (see DEBUG_NAMES).
-    bnb_pad: what `uniform_stage_pad` planned for this unit (rows the reduced table is padded by: the resident-chunk
-    form's branch and bound then takes its block ends at the same offsets in every lane, SDP_BNB_UNIFORM); `col_cfg`
-    counts these rows in its LDS bytes.
     peer_stores: the unit's backup kernels also store J into the buffers of other ranks (the direct exchange,
     SdpSweepArgs.peer_J); without it they hold no code for that, and the library refuses the direct exchange."""
     debug = check_debug(debug)
     real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
     head = _prologue_lines(model, real, lanes, debug, peer_stores)
+    column = family if isinstance(family, ColumnUnit) else None
+    staged = family if isinstance(family, dict) else None
+    line = family if isinstance(family, (int, np.integer)) else 0
+    lead_axes, lead_perm = family if (column is None and isinstance(family, tuple)) else (0, None)
     if column is not None:
         assert model.column_shareable
-        if per_control is not None:
-            col_cfg = per_control
-        elif window is not None:
-            col_cfg = window
-        elif col_cfg is None:
-            col_cfg = column_config(column[0], column[1], model.n_state, dtype,
-                                    use_wpair(model, dtype, debug), filtered,
-                                    max_controls=column[2] if len(column) > 2 else None,
-                                    n_columns=column[3] if len(column) > 3 else None,
-                                    shift=filtered and column_shift_applies(model, dtype, debug=debug),
-                                    utab_values=(utab_reals(len(utab[0]), utab[1]) if utab is not None and filtered else 0),
-                                    debug=debug)
-        if col_cfg is None:
-            raise ValueError('the column kernel does not fit this grid (its table exceeds the LDS of a CU)')
-        head += _column_lines(model, dtype, column, col_cfg, window, per_control, filtered, utab, debug,
-                              wres if (window is None and per_control is None) else 0, bnb_pad=bnb_pad)
+        head += _column_lines(model, dtype, column, debug)
     elif staged is not None:
         tile = tuple(staged['tile']) + (1,) * (4 - len(staged['tile']))
         head += ['#define SDP_STG_THREADS {}'.format(int(staged['threads']))] + [
@@ -791,11 +736,10 @@ def translation_unit(model, dtype, lanes, column=None, staged=None, window=None,
             '']
     elif line:
         # one state variable with noise in its sums: the filter on the shifted lattice, the value array as its table
-        chain = model.lead_split_chain()
         head += ['#define SDP_LINE 1',
                  '#define SDP_LINE_W {}'.format(int(line)),
                  '#define SDP_LINE_CHAIN {}        // additions of a chain of sums that was regrouped (0: the final-sum form)'.format(
-                     chain[1] if chain is not None else 0)]
+                     shift_chain(model))]
         if _dbg(debug, 'SDP_LINE_FILTER_SCALE'):
             head.append('#define SDP_LINE_FILTER_SCALE {}'.format(float(_dbg(debug, 'SDP_LINE_FILTER_SCALE'))))
         if _dbg(debug, 'SDP_LINE_TOP2') is not None:
@@ -1215,6 +1159,170 @@ def column_lds_bytes(n0, w, n_state, dtype):
     """LDS bytes of the column kernel's image (struct SdpColLds), plain table."""
     cfg = column_config(n0, w, n_state, dtype)
     return cfg[1] if cfg else COLUMN_LDS_MAX + 1
+
+
+# ---------------------------------------------------------------------------
+# One column unit, planned once: everything `_column_lines` prints and `solver.plan_info` reports.
+#   form            'full table' / 'resident chunks' / 'row window' / 'table per control'
+#   n0, w           rows of axis 0, perturbation points (0: none)
+#   max_controls    capacity of a node's control lattice (a horizon's steps share a unit), n_columns: columns of the grid
+#   threads, lds_bytes          workgroup size, sizeof(SdpColLds)
+#   filtered        the certified filter (SDP_COL_FILTER); wpair: SDP_COL_WPAIR
+#   shift, shift_rows           first pass on the shifted lattice (SDP_COL_SHIFT) and the rows of that lattice
+#   wres            perturbation points resident at a time (SDP_COL_WRES; 0: the whole table)
+#   frontier, utab_n            the control table's sub-expressions (None: no table) and its capacity in controls
+#   short           the short first pass: 'none' / 'lean2' (resident chunks, 8-byte reals) / 'wide2' (full table, 4-byte)
+#   bnb             .. as a branch and bound over blocks of controls (SDP_COL_BNB)
+#   bnb_pad, uniform            rows the reduced table is padded by (SDP_BNB_PAD_ROWS) and the uniform bound stage on them
+#   window_rows, seg_nodes      rows of the row window's table; nodes of a column per unit (0: the whole column)
+#   wchunk          perturbation points per table of the table per control (SDP_COL_WCHUNK)
+#   unroll_w, min_waves, a_lw, a_group, wide_loads, tail_hold, bnb_chunk, colu_wide_loads
+#                   the tuning macros the planner defines (SDP_COL_UNROLL_W .. SDP_COLU_WIDE_LOADS); None: not defined -- the
+#                   header's default, or the value an explicit `debug` dict carries (copied as it is); a_lw None: the build
+#                   deals its entries round-robin (no SDP_COL_A_ORDER)
+# ---------------------------------------------------------------------------
+ColumnUnit = collections.namedtuple('ColumnUnit', (
+    'form', 'n0', 'w', 'max_controls', 'n_columns', 'threads', 'lds_bytes',
+    'filtered', 'wpair', 'shift', 'shift_rows', 'wres', 'frontier', 'utab_n', 'short', 'bnb', 'bnb_pad', 'uniform',
+    'window_rows', 'seg_nodes', 'wchunk',
+    'unroll_w', 'min_waves', 'a_lw', 'a_group', 'wide_loads', 'tail_hold', 'bnb_chunk', 'colu_wide_loads'),
+    defaults=(False, False, False, 0, 0, None, 0, 'none', False, 0, False, 0, 0, 0) + (None,) * 8)
+
+
+def _with_build_order(unit, dtype, debug):
+    """`unit` with how phase A deals the table's entries to the threads (every form but the table per control)"""
+    rs = np.dtype(dtype).itemsize
+    window = unit.window_rows or None
+    wide = column_wide_loads(unit.n0, dtype, window, debug)
+    order, lw = column_build_order(unit.threads, unit.w, unit.window_rows or unit.n0, (16 // rs) if wide else 1)
+    if order != 2:
+        return unit
+    lw = int(_dbg(debug, 'SDP_COL_A_LW') or lw)
+    more = dict(a_lw=lw)
+    if rs == 4 and unit.n0 >= 512 and not unit.wres and window is None and not _dbg(debug, 'SDP_COL_A_GROUP'):
+        # (config 5, 512^3 in 4-byte reals, same box: 7.50 -> 7.36 ms, with four blocks' bounds per stage of
+        # the branch and bound 7.24 ms -- boxes 25-26 of profiles/r06_column_ab.txt; 8-byte reals: worse)
+        more['a_group'] = 8
+    if wide and not _dbg(debug, 'SDP_COL_A_WIDE_LOADS'):
+        more['wide_loads'] = 1
+        # resident chunks: the tail is built once, its entries wait in the registers of the threads that made
+        # them (SDP_COL_TAIL_HOLD of csrc/sdp_colres_kernel.h; round 6: 1.235 -> 1.048 ms on the benchmark, same
+        # bits) -- where they are whole rounds of points and rows and at most 32 registers per thread
+        # (on the shifted lattice too since the second pass is no longer unrolled there: 2.23 -> 2.12 ms, box 11 of
+        # profiles/r06_column_ab.txt; with the unrolled pass it had lost, 2.96 against 2.71 ms)
+        if unit.wres and rs == 8 and not unit.wpair and window is None and _dbg(debug, 'SDP_COL_TAIL_HOLD') is None:
+            tail, groups = unit.w - unit.wres, unit.threads // lw
+            if (tail > 0 and tail % groups == 0 and unit.n0 % (2 * lw) == 0
+                    and (tail // groups) * (unit.n0 // (2 * lw)) * 4 <= 32):
+                more['tail_hold'] = 1
+    return unit._replace(**more)
+
+
+def _short_pass(model, dtype, unit, debug):
+    """(short, bnb, bnb_chunk) of a full-table or resident-chunk unit: the short first passes -- 8-byte reals in the
+    resident-chunk kernel, 4-byte reals (wide form) in the full-table one -- of a model x0' = X(x) +- a(u),
+    cost = K(x) +- h(u) with a control table (round 6: on the shifted lattice too -- final sums only,
+    additive_control_split).  (`debug`: SDP_COL_LEAN2 = 0 takes them away, SDP_COL_BNB = 0 their branch and bound.)"""
+    rs = np.dtype(dtype).itemsize
+    short = 'none'
+    if (unit.frontier is not None and not model.cost_depends_on_w and _dbg(debug, 'SDP_COL_LEAN2') != '0'
+            and (not unit.shift or rs == 8)):
+        if rs == 8 and unit.wres:
+            short = 'lean2'
+        elif rs == 4 and not unit.wres and _dbg(debug, 'SDP_COL_FILTER_TOP2') in (None, '1'):
+            short = 'wide2'
+    if short != 'none' and model.additive_control_split(unit.frontier) is None:
+        short = 'none'
+    bnb = short != 'none' and _dbg(debug, 'SDP_COL_BNB') != '0'
+    chunk = 4 if (short == 'wide2' and bnb and unit.n0 >= 512 and not _dbg(debug, 'SDP_BNB_CHUNK')) else None
+    return short, bnb, chunk
+
+
+def column_table_unit(model, dtype, shape, W, max_controls, box, axis, certified_filter=True, debug=None):
+    """The column kernel whose table holds every row of axis 0 (all W points of it, or a resident chunk), for a
+    storage-separable model on a grid of `shape`: a ColumnUnit, or None where the table does not fit the LDS of a CU.
+    The shape is planned ONCE, with everything that sizes its LDS image (the control table, the padding of the
+    uniform bound stage), and printed as it is.  `box`: the table of admissible boxes (lo, hi, n, per_node), `axis`:
+    the grid of the stock, `certified_filter`: whether the solver wants the filter where it applies."""
+    rs = np.dtype(dtype).itemsize
+    n0, n_state, n_columns = int(shape[0]), len(shape), int(np.prod(shape[1:]))
+    filtered = bool(certified_filter and column_filter_applies(model, dtype=dtype, table=(n0, W, n_state), debug=debug))
+    wpair = bool(use_wpair(model, dtype, debug))
+    shift = bool(filtered and column_shift_applies(model, dtype, debug=debug))
+    fr = control_table_plan(model, dtype, box['per_node'], max_controls, debug) if filtered else None
+    for frontier in ((fr, None) if fr is not None else (None,)):
+        kw = dict(max_controls=max_controls, n_columns=n_columns, shift=shift,
+                  utab_values=utab_reals(len(frontier), max_controls) if frontier else 0, debug=debug)
+        cfg = column_config(n0, W, n_state, dtype, wpair, filtered, **kw)
+        if cfg is not None:                   # (else once more without the control table)
+            break
+    else:
+        return None
+    # the table a chunk of perturbation points at a time, where that lets more workgroups share a CU
+    wres = column_resident_points(model, n0, W, n_state, dtype, filtered, shift, wpair, cfg[0], kw['utab_values'], debug)
+    if wres:
+        cfg = column_config(n0, W, n_state, dtype, wpair, filtered, wres=wres, **kw)
+        if cfg is None:
+            return None
+    unit = ColumnUnit('resident chunks' if wres else 'full table', n0, int(W), int(max_controls), n_columns,
+                      int(cfg[0]), int(cfg[1]), filtered=filtered, wpair=wpair, shift=shift,
+                      shift_rows=int(cfg[2]) if shift else 0, wres=int(wres), frontier=frontier,
+                      utab_n=int(max_controls) if frontier is not None else 0)
+    short, bnb, chunk = _short_pass(model, dtype, unit, debug)
+    unit = unit._replace(short=short, bnb=bnb, bnb_chunk=chunk)
+    # (a uniform stock axis under x0' = x0 +- a: the branch and bound's uniform bound stage, which pads the reduced
+    # table -- the last member of the image -- where that costs the CU no workgroup.  SDP_BNB_UNIFORM = 0 keeps the
+    # PADDING and leaves the stage out: the A/B switch)
+    pad = uniform_stage_pad(model, dtype, unit, axis, box)
+    if pad:
+        unit = unit._replace(bnb_pad=pad, uniform=_dbg(debug, 'SDP_BNB_UNIFORM') != '0',
+                             lds_bytes=_column_lds(unit.wres, max(unit.w, 1), n0, n_state, rs, unit.threads, reduced=True,
+                                                   utab_values=kw['utab_values'], bnb_pad=True))
+    if wres and rs == 8 and shift and not _dbg(debug, 'SDP_COL_UNROLL_W'):
+        # the second pass of the shifted lattice's resident-chunk kernel one batch of perturbation points at a time: unrolled
+        # four times it kept 8 points' cells, table entries and weights per survivor in flight (two survivors in half of the
+        # waves), in registers the kernel does not have at three waves per SIMD -- round 6, same box: 2.45 -> 2.23 ms, and
+        # with the tail held on top 2.12 ms (boxes 9-11 of profiles/r06_column_ab.txt: 48 -> 22 spilled registers).  The
+        # benchmark's kernel (no cell per point, one survivor) does not care: 948.8 against 954.3 sweeps/s over 50 steps
+        # (box 20; the 5 % of box 12 were the A/B tool's first-position penalty); 4-byte reals: 7.51 against 7.72 ms.
+        unit = unit._replace(unroll_w=1)
+    if filtered and unit.threads <= 256 and not _dbg(debug, 'SDP_COL_MIN_WAVES'):
+        # resident chunks: as many waves per SIMD as the LDS image admits workgroups per CU, at most 4 (128 registers
+        # per lane.  Round 4 asked for up to 8 for small tables -- 64 registers, which these kernels do not fit in:
+        # 90 - 200 spilled registers in the suite's small models, and spill code the compiler got wrong, see
+        # spill_hazards); else the small workgroups of the filtered kernel, without a register cap
+        unit = unit._replace(min_waves=(max(1, min(4, (COLUMN_LDS_MAX // unit.lds_bytes) * unit.threads // 256))
+                                        if wres else 1))
+    return _with_build_order(unit, dtype, debug)
+
+
+def column_percontrol_unit(model, dtype, shape, W, max_controls, debug=None):
+    """The column kernel with a table per control, for trailing next states that depend on the control but not on x0
+    (the nodes of a column still share a table, control by control: SDP_TRAIL_HAS_U of csrc/sdp_column_kernel.h): a
+    ColumnUnit, or None.  The caller sees to it that the nodes of a column share their control values."""
+    if not (model.column_shareable and model.trail_depends_on_u):
+        return None
+    n0 = int(shape[0])
+    cfg = column_percontrol_config(n0, W, len(shape), dtype, debug)
+    if cfg is None:
+        return None
+    wide = n0 % (16 // np.dtype(dtype).itemsize) == 0 and not _dbg(debug, 'SDP_COLU_WIDE_LOADS')
+    return ColumnUnit('table per control', n0, int(W), int(max_controls), int(np.prod(shape[1:])), int(cfg[0]), int(cfg[1]),
+                      wpair=bool(use_wpair(model, dtype, debug)), seg_nodes=int(cfg[0]), wchunk=int(cfg[2]),
+                      colu_wide_loads=1 if wide else None)
+
+
+def column_window_unit(model, dtype, shape, W, max_controls, reach_rows, debug=None):
+    """The column kernel of a storage-separable model whose W x N0 table exceeds the LDS of a CU: a window of rows
+    per segment of the column (SDP_COL_ROWS of csrc/sdp_column_kernel.h; `reach_rows`: the rows the controls of one
+    node span).  A ColumnUnit, or None."""
+    n0 = int(shape[0])
+    cfg = column_window_config(n0, W, len(shape), dtype, reach_rows)
+    if cfg is None:
+        return None
+    unit = ColumnUnit('row window', n0, int(W), int(max_controls), int(np.prod(shape[1:])), int(cfg[0]), int(cfg[1]),
+                      window_rows=int(cfg[2]), seg_nodes=int(cfg[3]))
+    return _with_build_order(unit, dtype, debug)
 
 
 HIPCC_FLAGS = ['--genco', '--offload-arch=gfx950', '-O3', '-ffp-contract=off',

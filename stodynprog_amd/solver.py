@@ -746,88 +746,50 @@ class DPSolver(object):
         # a CU run the column kernels, with per-node arrays stored axis-0-fastest
         if self.kernel not in ('auto', 'generic', 'column', 'staged', 'lead', 'line'):
             raise ValueError("kernel must be 'auto', 'column', 'lead', 'line', 'staged' or 'generic'")
-        may_filter = (getattr(self, 'certified_filter', True)
-                      and codegen.column_filter_applies(model, dtype=dt, table=(shape[0], W, len(shape)), debug=debug))
-        # The shape of the full-table column kernel is planned ONCE, with everything that sizes its LDS image
-        # (the control table included), and handed to the code generator as it is.  A lattice that changes
-        # with the time index gets a control table with room to spare (a capacity, checked by the library as
-        # controls <= capacity), so that the steps of a horizon keep sharing one code object.
+        certified = getattr(self, 'certified_filter', True)
+        col_family = self.kernel in ('auto', 'column')
+        S_nodes = int(np.prod(shape))
+        # A lattice that changes with the time index gets a control table with room to spare (a capacity, checked by
+        # the library as controls <= capacity), so that the steps of a horizon keep sharing one code object.
         n_controls = bp['max_u'] if box_t is None else 1 << max(int(bp['max_u']) - 1, 0).bit_length()
-        col_cfg, utab, wres, bnb_pad = None, None, 0, 0
-        if self.kernel in ('auto', 'column') and model.storage_separable:
-            wpair = codegen.use_wpair(model, dt, debug)
-            shift = bool(may_filter and codegen.column_shift_applies(model, dt, debug=debug))
-            fr = codegen.control_table_plan(model, dt, bp['per_node'], n_controls, debug) if may_filter else None
-            for frontier in ((fr, None) if fr is not None else (None,)):
-                kw = dict(max_controls=n_controls, n_columns=int(np.prod(shape[1:])), shift=shift,
-                          utab_values=codegen.utab_reals(len(frontier), n_controls) if frontier else 0, debug=debug)
-                col_cfg = codegen.column_config(shape[0], W, len(shape), dt, wpair, may_filter, **kw)
-                if col_cfg is not None:                   # (else once more without the control table)
-                    utab = (frontier, n_controls) if frontier is not None else None
-                    # the table a chunk of perturbation points at a time, where that lets more workgroups share a CU
-                    wres = codegen.column_resident_points(model, shape[0], W, len(shape), dt, may_filter, shift, wpair,
-                                                          col_cfg[0], kw['utab_values'], debug)
-                    if wres:
-                        # (a uniform stock axis under x0' = x0 +- a: the branch and bound's uniform bound stage, which pads
-                        # the reduced table where that costs the CU no workgroup)
-                        col_cfg = codegen.column_config(shape[0], W, len(shape), dt, wpair, may_filter, wres=wres, **kw)
-                        if col_cfg is not None and not bp['per_node']:
-                            # (the lattice of every control as the kernels form it: n points from lo to hi, sdp_control_value)
-                            lattice = [np.linspace(float(bp['lo'][c, 0]), float(bp['hi'][c, 0]), int(bp['n'][c, 0]))
-                                       for c in range(bp['lo'].shape[0])]
-                            bnb_pad = codegen.uniform_stage_pad(model, dt, frontier, self.state_grid[0], shape[0], lattice,
-                                                                wres, shift, col_cfg[0], col_cfg[1], debug)
-                            if bnb_pad:            # (the padded reduced table is the last member of the image)
-                                col_cfg = (col_cfg[0], col_cfg[1] + 2 * bnb_pad * np.dtype(dt).itemsize) + tuple(col_cfg[2:])
-                    break
-        column = col_cfg is not None
+        col_args = (model, dt, shape, W, n_controls)
+        # the column family, first form: the table of a column fits the LDS of a CU (codegen.column_table_unit)
+        unit = None
+        if col_family and model.storage_separable:
+            unit = codegen.column_table_unit(*col_args, box=bp, axis=self.state_grid[0], certified_filter=certified, debug=debug)
         # several controlled state variables next to an exogenous process: the node-order sweep with the
         # certified filter on an array reduced over w (csrc/sdp_lead_kernel.h); one GPU for now
-        lead_axes = 0
-        if (not column and self.kernel in ('auto', 'lead') and W > 0 and not self._cache.get('no_lead')
-                and (self.comm is None or self.comm.is_device)
-                and getattr(self, 'certified_filter', True)):
-            # (one stock whose table does not fit LDS too: measured 5.9 ms against 12.7 ms of the row-window
-            # column kernel at 1024 x 128 x 128 x 64 x 32, tools/window_vs_lead.py)
+        # (one stock whose table does not fit LDS too: measured 5.9 ms against 12.7 ms of the row-window
+        # column kernel at 1024 x 128 x 128 x 64 x 32, tools/window_vs_lead.py)
+        lead_axes, lead_perm = 0, None
+        if (unit is None and self.kernel in ('auto', 'lead') and W > 0 and not self._cache.get('no_lead')
+                and (self.comm is None or self.comm.is_device) and certified):
             lead_axes = codegen.lead_filter_applies(
                 model, dt, 1 if (self.kernel == 'lead' or model.storage_separable) else 2, debug)
-        # the stocks need not be listed first (the order of the state variables is the user's, reference
-        # stodynprog.py:119-131): the filter then works on a permuted view of the axes, the second pass keeps the
-        # reference's own axis order
-        lead_perm = None
-        if (not column and not lead_axes and self.kernel in ('auto', 'lead') and W > 0 and not self._cache.get('no_lead')
-                and (self.comm is None or self.comm.is_device)
-                and getattr(self, 'certified_filter', True)):
-            co = codegen.lead_order(model, dt, debug)
-            if co is not None:
-                lead_axes, lead_perm = co
+            # the stocks need not be listed first (the order of the state variables is the user's, reference
+            # stodynprog.py:119-131): the filter then works on a permuted view of the axes, the second pass keeps the
+            # reference's own axis order
+            if not lead_axes:
+                lead_axes, lead_perm = codegen.lead_order(model, dt, debug) or (0, None)
         if self.kernel == 'lead' and not lead_axes:
             raise ValueError("kernel = 'lead' needs controlled state variables next to an exogenous process, "
                              'a perturbation that reaches only that process, 8-byte reals and the certified '
                              'filter (several GPUs: a device communicator)')
         if lead_axes:
             lanes = 1                                     # one lane per node, the control loop in-lane
-        # trailing next states that depend on the control but not on x0: the nodes of a
-        # column still share a table, control by control, provided they share their control
-        # values (box independent of x0) -- csrc/sdp_column_kernel.h, SDP_TRAIL_HAS_U
+        # second form: a table per control, provided the nodes of a column share their control values (box independent
+        # of x0) -- codegen.column_percontrol_unit
         # (on a grid of fewer than PERCONTROL_MIN_NODES nodes the direct kernel is faster than a table per control: 16^3
         # 0.160 / 0.036 ms, 24^3 0.224 / 0.101 ms, 32^3 0.242 / 0.251 ms, 48^3 0.46 / 0.95 ms -- round 5)
-        per_control = (not column and not lead_axes and self.kernel in ('auto', 'column') and model.column_shareable
-                       and model.trail_depends_on_u
-                       and (self.kernel == 'column' or int(np.prod(shape)) >= self.PERCONTROL_MIN_NODES)
-                       and self._box_constant_along_axis0(bp, shape))
-        per_control_cfg = None
-        if per_control:
-            per_control_cfg = codegen.column_percontrol_config(shape[0], W, len(shape), dt, debug)
-            column = per_control = per_control_cfg is not None
-        window = None
-        if (not column and not per_control and not lead_axes and self.kernel in ('auto', 'column')
-                and model.storage_separable):
-            # the W x N0 table exceeds the LDS of a CU: tabulate a window of rows per
-            # segment of the column (csrc/sdp_column_kernel.h, SDP_COL_ROWS)
-            window = codegen.column_window_config(shape[0], W, len(shape), dt,
-                                                  self._lead_reach_rows(model, bp, box_t))
-            column = window is not None
+        if (unit is None and not lead_axes and col_family
+                and (self.kernel == 'column' or S_nodes >= self.PERCONTROL_MIN_NODES)
+                and self._box_constant_along_axis0(bp, shape)):
+            unit = codegen.column_percontrol_unit(*col_args, debug=debug)
+        # third form: the W x N0 table exceeds the LDS of a CU -- a window of rows per segment of the column
+        if unit is None and not lead_axes and col_family and model.storage_separable:
+            unit = codegen.column_window_unit(*col_args, reach_rows=self._lead_reach_rows(model, bp, box_t), debug=debug)
+        column = unit is not None
+        per_control = column and unit.form == 'table per control'
         if (not column or per_control) and not lead_perm and self.kernel in ('auto', 'column'):
             k = model.separable_axis_hint()
             if k is not None and not self._cache.get('hinted'):
@@ -848,7 +810,6 @@ class DPSolver(object):
         # 256^2 0.218 / 0.288 ms, 512^2 0.34 / 1.26 ms; the same with 1025 controls: 256^2 3.04 / 1.46 ms, 512^2 4.5 / 5.9 ms.
         # So the direct kernel for one state variable, for grids of at most STAGED_MIN_NODES nodes, and up to four times
         # that where a node has STAGED_MIN_WORK control x perturbation points or more (few threads with long loops).
-        S_nodes = int(np.prod(shape))
         small = (len(shape) == 1 or S_nodes <= self.STAGED_MIN_NODES
                  or (S_nodes <= 4 * self.STAGED_MIN_NODES and bp['max_u'] * max(W, 1) >= self.STAGED_MIN_WORK))
         if not column and not lead_axes and (self.kernel == 'staged' or (self.kernel == 'auto' and not small)):
@@ -863,7 +824,7 @@ class DPSolver(object):
         # there is work to save: LINE_MIN_CELLS lattice cells per sweep (below that the direct kernel takes microseconds).
         line = 0
         if (len(shape) == 1 and self.kernel in ('auto', 'line') and self.comm is None and W > 0 and staged is None
-                and getattr(self, 'certified_filter', True) and box_t is None
+                and certified and box_t is None
                 and model.t_value is None and model.param_index is None
                 and (self.kernel == 'line' or S_nodes * int(bp['max_u']) * W >= self.LINE_MIN_CELLS)
                 and codegen.line_filter_applies(model, dt, W, debug)):
@@ -879,24 +840,14 @@ class DPSolver(object):
             raise ValueError("kernel = 'line' needs one state variable whose perturbation enters x' through final sums "
                              "(x + u - w), a cost that does not see it, 8-byte reals, a stationary system, the certified "
                              'filter, one GPU')
-        filtered = bool(column and getattr(self, 'certified_filter', True) and codegen.column_filter_applies(
-            model, window, per_control_cfg if per_control else None, dtype=dt,
-            table=(shape[0], W, len(shape)), debug=debug))
-        if not filtered or window is not None or per_control:
-            utab = None
-        source = codegen.translation_unit(model, dt, lanes,
-                                          column=(shape[0], W, n_controls, int(np.prod(shape[1:]))) if column else None,
-                                          staged=staged,
-                                          window=window, per_control=per_control_cfg if per_control else None,
-                                          filtered=filtered, utab=utab, lead_axes=lead_axes,
-                                          col_cfg=col_cfg, debug=debug, wres=wres if filtered else 0,
-                                          lead_perm=lead_perm, line=line, peer_stores=self._plans_direct_exchange(),
-                                          bnb_pad=bnb_pad if (filtered and wres and utab is not None) else 0)
-        filtered = filtered or bool(lead_axes) or bool(line)
-        return dict(model=model, source=source, column=column, lanes=lanes, staged=staged, filtered=filtered,
+        # (what the unit holds beside the direct kernels: codegen.translation_unit)
+        family = unit or staged or line or ((lead_axes, lead_perm) if lead_axes else None)
+        source = codegen.translation_unit(model, dt, lanes, family, debug=debug, peer_stores=self._plans_direct_exchange())
+        window = (unit.threads, unit.lds_bytes, unit.window_rows, unit.seg_nodes) if column and unit.form == 'row window' else None
+        return dict(model=model, source=source, column=column, unit=unit, lanes=lanes, staged=staged,
+                    filtered=bool((column and unit.filtered) or lead_axes or line),
                     lead_axes=lead_axes, lead_perm=lead_perm, line=bool(line),
-                    window=window, per_control=per_control,
-                    col_seg_nodes=(window[3] if window else (per_control_cfg[0] if per_control else 0)),
+                    window=window, per_control=per_control, col_seg_nodes=unit.seg_nodes if column else 0,
                     per_node=bp['per_node'], lo=bp['lo'], hi=bp['hi'], n=bp['n'],
                     max_u=bp['max_u'], W=W, box_digest=bp['digest'], box_mode=bp.get('mode'))
 
@@ -1103,26 +1054,7 @@ class DPSolver(object):
         prob.lead_halo = bool(plan.get('lead_axes') and self.comm is not None and self.comm.is_device
                               and self.comm.nranks > 1)
         self._set_exchange_lists(prob, model, plan)
-        prob.info = dict(mode='traced', exchange=exchange,
-                         kernel='column' if column else ('staged' if plan['staged'] else
-                                                         ('lead' if plan.get('lead_axes') else ('line' if plan.get('line') else 'generic'))),
-                         controlled_axes=int(plan.get('lead_axes') or (1 if column else 0)),
-                         # state variables in the order the filter sees them (stocks first) when they are not listed first
-                         controlled_order=(list(plan['lead_perm']) if plan.get('lead_perm') else None),
-                         staged=plan['staged'],
-                         row_window=(dict(rows=plan['window'][2], segment_nodes=plan['window'][3])
-                                     if plan['window'] else None),
-                         table_per_control=bool(plan['per_control']),
-                         certified_filter=bool(plan.get('filtered')),
-                         # 'shifted lattice': the perturbation reaches x0' through a final sum (SDP_COL_SHIFT)
-                         filter_form=(None if not plan.get('filtered') else
-                                      ('shifted lattice' if ('#define SDP_COL_SHIFT 1' in plan['source'] or plan.get('line')) else
-                                       ('reduced array' if plan.get('lead_axes') else 'reduced table'))),
-                         # x0' = a chain of sums in another nesting than ((a +- b) +- ..), x + (w - u): regrouped for the first pass
-                         regrouped_sums=bool(plan.get('filtered') and '#define SDP_COL_SHIFT 1' in plan['source']
-                                             and '#define SDP_COL_SHIFT_CHAIN 0' not in plan['source']),
-                         module=module, lanes_per_node=lanes,
-                         max_controls=max_u, box_per_node=bool(per_node),
+        prob.info = dict(plan_info(plan), mode='traced', exchange=exchange, module=module,
                          bit_exact_model=model.bit_exact,
                          inexact_ops=model.inexact_ops(),
                          # diagnostic switches this code object was built with (None in the product)
@@ -1979,6 +1911,29 @@ class DPSolver(object):
             print('  control combinations:'
                   ' [{:,d} to {:,d}] possible values ({:,.1f} on average)'.format(
                       tot.min(), tot.max(), tot.mean()))
+
+
+def plan_info(plan):
+    """The entries of `backend_info` that the plan of `DPSolver._kernel_plan` decides alone (no GPU needed)."""
+    model, unit, filtered = plan['model'], plan['unit'], bool(plan['filtered'])
+    shifted = bool(unit is not None and unit.shift)
+    return dict(
+        kernel='column' if plan['column'] else ('staged' if plan['staged'] else
+                                                ('lead' if plan['lead_axes'] else ('line' if plan['line'] else 'generic'))),
+        controlled_axes=int(plan['lead_axes'] or (1 if plan['column'] else 0)),
+        # state variables in the order the filter sees them (stocks first) when they are not listed first
+        controlled_order=list(plan['lead_perm']) if plan['lead_perm'] else None,
+        staged=plan['staged'],
+        row_window=dict(rows=unit.window_rows, segment_nodes=unit.seg_nodes) if plan['window'] else None,
+        table_per_control=bool(plan['per_control']),
+        certified_filter=filtered,
+        # 'shifted lattice': the perturbation reaches x0' through a final sum (SDP_COL_SHIFT; the line kernel)
+        filter_form=(None if not filtered else
+                     ('shifted lattice' if (shifted or plan['line']) else
+                      ('reduced array' if plan['lead_axes'] else 'reduced table'))),
+        # x0' = a chain of sums in another nesting than ((a +- b) +- ..), x + (w - u): regrouped for the first pass
+        regrouped_sums=bool(filtered and shifted and codegen.shift_chain(model)),
+        lanes_per_node=plan['lanes'], max_controls=plan['max_u'], box_per_node=bool(plan['per_node']))
 
 
 def _params_key(params):

@@ -1,8 +1,9 @@
 """The compile-time forms of the column family (csrc/sdp_column_kernel.h, sdp_colres_kernel.h,
 sdp_colfilter_kernel.h) as a table of cases (test infrastructure, like tests/full_parity.py; not a test file).
 
-codegen._column_lines, column_config and column_resident_points turn four numbers -- the rows of axis 0,
-the perturbation points W, the number of controls and the dtype -- into one of many units: workgroup size,
+codegen.column_table_unit (with column_config and column_resident_points, the arithmetic underneath) turns four
+numbers -- the rows of axis 0, the perturbation points W, the number of controls and the dtype -- into one of many
+units (a codegen.ColumnUnit, which codegen._column_lines prints as it is): workgroup size,
 resident chunks (SDP_COL_WRES), the tail held in registers (SDP_COL_TAIL_HOLD) and its geometry, lanes per
 point of the table build (SDP_COL_A_LW), the short first pass and its branch and bound, the control table,
 the register cap, the knobs of 4-byte reals.  Each case below is the benchmark model (models.synthetic3d)

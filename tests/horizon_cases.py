@@ -4,7 +4,8 @@ column forms (test infrastructure, like tests/column_forms.py; not a test file).
 A time-dependent system reaches the kernels through paths no stationary model runs: the time index is a kernel
 argument, the control box is tabulated again at every step, every step is planned on its own, and a lattice that
 changes with the time index gets a control table with room to spare -- a CAPACITY, the power of two at or above the
-step's largest lattice (DPSolver._kernel_plan_now), so that the steps of a horizon share code objects.  The kernel
+step's largest lattice (DPSolver._kernel_plan_now; ColumnUnit.max_controls and utab_n of the unit's record), so that
+the steps of a horizon share code objects.  The kernel
 then runs with fewer controls than its table holds, and the branch and bound's block size and block count come from
 the capacity, not from the lattice.
 

@@ -1,7 +1,8 @@
 """The shapes and decision paths of the filtered line kernel (csrc/sdp_line_kernel.h) as a table of cases (test
 infrastructure, like tests/column_forms.py; not a test file, and no GPU code).
 
-DPSolver._kernel_plan turns three numbers -- nodes S, the largest control lattice and the perturbation points W -- into
+DPSolver._kernel_plan_now (the line kernel's own part of it; codegen.translation_unit then gets W as the family it
+prints) turns three numbers -- nodes S, the largest control lattice and the perturbation points W -- into
 SDP_LANES = min(64, max(need, want)): `need` keeps a tile's (node, perturbation point) terms within the kernel's LDS
 table (64 / lanes x W <= 2048), `want` fills the chip and keeps at least 8 controls in a slice.  The lane count sets the
 shape of everything the kernel merges: NPW = 64 / lanes nodes per tile, P = 4 lanes slices of the control lattice, the

@@ -199,7 +199,11 @@ def test_np_interp_is_traced_with_numpy_semantics():
         xn, g = evaluate(m, [0.3, 0.4], [u], [w])
         assert np.array_equal(xn[0], dyn(0.3, 0.4, u, w)[0], equal_nan=True)
         assert np.array_equal(g, cost(0.3, 0.4, u, w), equal_nan=True)
-    src = codegen.translation_unit(m, np.float64, 64, column=(21, 5))
+    # (a 21-row, 5-point column unit as the planner makes it for this model, without the filter)
+    unit = codegen.column_table_unit(m, np.float64, (21, 9), 5, 64, box=dict(per_node=False), axis=np.linspace(0., 1., 21),
+                                     certified_filter=False)
+    assert unit.form == 'full table' and (unit.n0, unit.w) == (21, 5)
+    src = codegen.translation_unit(m, np.float64, 64, unit)
     assert 'sdp_np_interp' in src and 'sdp_tabx_2[1]' in src and 'sdp_interp1_0(' in src
     # same table twice -> one table; a different table -> a different structure
     m2 = trace_model(lambda e, p, u, w: (e + np.interp(u, xp, fp) + np.interp(w, xp, fp), p),
