@@ -113,11 +113,12 @@ typedef struct sdp_problem_desc {
     int32_t dtype;              /* SDP_F64 | SDP_F32: type of every real array below */
     int32_t d;                  /* state variables, 1..4 */
     int32_t nu;                 /* control variables, 1..4 */
-    int32_t W;                  /* perturbation points; 0 = deterministic system */
+    int32_t W;                  /* perturbation points (of the FLAT law when n_perturb >= 2); 0 = deterministic system */
     int64_t orders[4];          /* points per state axis (state_grid lengths) */
     const void *axes[4];        /* state_grid[k]: orders[k] reals (np.linspace values) */
-    const void *wgrid;          /* perturb_grid[0]: W reals, NULL if W == 0 */
-    const void *proba;          /* perturb_proba[0]: W reals */
+    const void *wgrid;          /* [n_perturb][W] reals, row i = variable i at every point of the law (one variable:
+                                 * perturb_grid[0]); NULL if W == 0 */
+    const void *proba;          /* [W] reals: the law's probabilities (one variable: perturb_proba[0]) */
     int32_t box_per_node;       /* 0: one box for all nodes, 1: arrays over nodes */
     int32_t lanes_per_node;     /* SDP_LANES the code object was built with */
     int32_t layout;             /* SDP_LAYOUT_NODES | SDP_LAYOUT_COLUMNS (see below) */
@@ -131,7 +132,10 @@ typedef struct sdp_problem_desc {
     int32_t tile[4];            /* SDP_VARIANT_STAGED: node-tile shape the code object was built with */
     int32_t col_seg_nodes;      /* SDP_LAYOUT_COLUMNS with a row window (code object built with SDP_COL_ROWS
                                  * < orders[0]): nodes of a column one workgroup takes at most; 0 = no window */
-    int32_t reserved;           /* must be 0 */
+    int32_t n_perturb;          /* perturbation variables, 0..4; 0 means "1 when W > 0" (the field was `reserved`, must be 0).
+                                 * 2..4: the code object is a unit of several variables (csrc/sdp_multiw_kernel.h), the law
+                                 * is their product flattened in C order, last variable fastest; node layout, direct
+                                 * variant, one GPU */
 } sdp_problem_desc;
 
 /* The code object must have been generated for THIS problem: it declares
@@ -238,7 +242,8 @@ int sdp_host_free(void *ptr);
  *                                    ([nu][S] control values on the state grid, C order;
  *                                    same arithmetic as sdp_mlinterp_*)
  *     x[k+1] = dyn(x[k], u[k], w[k]), g[k] = cost(x[k], u[k], w[k])    (the traced model)
- * host_x0 [d][B]; host_w [T][B] (NULL for a deterministic system); outputs host_x
+ * host_x0 [d][B]; host_w [T][B] (NULL for a deterministic system; [T][n_perturb][B] for a problem of
+ * several perturbation variables); outputs host_x
  * [T+1][d][B] (x[0] = x0), host_u [T][nu][B], host_g [T][B] (may be NULL).  t0: time
  * index of step 0 for a non-stationary system.
  */
@@ -255,7 +260,8 @@ int sdp_problem_simulate(sdp_problem *p, const void *host_pol, int64_t B, int64_
  *     u = ((r0 >> 5) * 2^26 + (r1 >> 6)) * 2^-53       output words 0 and 1; a double in [0, 1)
  *     j = number of i in [0, n_law - 2] with u >= host_cum[i];   w = host_law_grid[j]
  * host_cum [n_law] doubles: running sum of the law's probabilities (its last entry is not read);
- * host_law_grid [n_law] reals, n_law in 1..4096.  A draw depends on (seed, id, k) alone: B, the
+ * host_law_grid [n_law] reals, n_law in 1..4096 (several perturbation variables: [n_perturb][n_law], w = column j,
+ * and 8 (n_law - 1) + n_perturb n_law sizeof(real) <= 65536 bytes).  A draw depends on (seed, id, k) alone: B, the
  * launch grid and steps_per_launch (the run is cut into kernel launches of at most that many
  * steps, the state kept on the device between them) do not change a bit of the results.
  * Over the steps k >= n_burn: host_cost_sum [B] reals, acc = acc + g[k] in k order;

@@ -48,7 +48,7 @@ class sdp_problem_desc(C.Structure):
         ('node_begin', C.c_int64), ('node_end', C.c_int64),
         ('module_path', C.c_char_p),
         ('tile', C.c_int32 * 4),
-        ('col_seg_nodes', C.c_int32), ('reserved', C.c_int32),
+        ('col_seg_nodes', C.c_int32), ('n_perturb', C.c_int32),
     ]
 
 

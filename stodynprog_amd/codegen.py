@@ -19,6 +19,7 @@ import numpy as np
 from .trace import TracedModel, DEP_X
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
+MAX_PERTURB = 4          # perturbation variables of a generated unit (perturb.MAX_PERTURB)
 
 
 # ---------------------------------------------------------------------------
@@ -87,7 +88,7 @@ def real_literal(value):
     return '(sdp_real)({})'.format(float(value).hex())
 
 
-def _emit_node(n, name, param_index=None):
+def _emit_node(n, name, param_index=None, vector_w=False):
     a = [name(x) for x in n.args]
     op = n.op
     if op == 'const':
@@ -100,6 +101,8 @@ def _emit_node(n, name, param_index=None):
         v = n.value
         if v == 't':
             return 't'
+        if v[0] == 'w' and vector_w:         # several perturbation variables: the model entry takes them as w[SDP_NW]
+            return 'w[{}]'.format(v[1:])
         return '{}[{}]'.format(v[0], v[1:]) if v[0] in 'xu' else 'w'
     if op in _BIN_INFIX:
         return '({} {} {})'.format(a[0], _BIN_INFIX[op], a[1])
@@ -189,7 +192,7 @@ def _emit_body(model, nodes, lines, names=None):
         return names[n.id]
 
     for n in nodes:
-        expr = _emit_node(n, name, getattr(model, 'param_index', None))
+        expr = _emit_node(n, name, getattr(model, 'param_index', None), getattr(model, 'n_perturb', 0) >= 2)
         if n.op in ('const', 'bconst', 'var'):
             names[n.id] = expr              # inline leaves
             continue
@@ -203,10 +206,11 @@ def _emit_body(model, nodes, lines, names=None):
 def model_function_source(model):
     """C++ text of sdp_model_cell for a TracedModel: the whole dyn + cost."""
     assert isinstance(model, TracedModel)
-    if model.n_perturb > 1:
-        raise NotImplementedError('only 0 or 1 perturbation variable is supported '
-                                  '(as reference stodynprog.py:679-683)')
-    lines = ['SDP_DEV void sdp_model_cell(const sdp_real *x, const sdp_real *u, sdp_real w,',
+    if model.n_perturb > MAX_PERTURB:
+        raise NotImplementedError('{} perturbation variables: at most {} are supported'.format(model.n_perturb, MAX_PERTURB))
+    # (several perturbation variables, csrc/sdp_multiw_kernel.h: variable w<i> is w[i])
+    w_arg = 'const sdp_real *w' if model.n_perturb >= 2 else 'sdp_real w'
+    lines = ['SDP_DEV void sdp_model_cell(const sdp_real *x, const sdp_real *u, {},'.format(w_arg),
              '                            sdp_real t, sdp_real *xn, sdp_real &g)',
              '{',
              '    (void)x; (void)u; (void)w; (void)t;']
@@ -447,6 +451,9 @@ def _prologue_lines(model, real, lanes, debug, peer_stores=False):
              '#define SDP_LANES {}'.format(int(lanes)),
              '#define SDP_PEER_STORES {}     // the backup kernels also store J into other ranks (direct exchange)'.format(
                  1 if peer_stores else 0)]
+    if model.n_perturb >= 2:
+        lines.append('#define SDP_NW {}         // perturbation variables: the kernels of sdp_multiw_kernel.h on their flat law'.format(
+            int(model.n_perturb)))
     if _dbg(debug, 'SDP_STAMP') in ('1', '2', '3'):
         lines.append('#define SDP_STAMP {}     // diagnostic build: in-kernel clock stamps (tools/clock_probe.py, '
                      'tools/phase_probe.py)'.format(int(_dbg(debug, 'SDP_STAMP'))))
@@ -717,6 +724,8 @@ def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=F
     SdpSweepArgs.peer_J); without it they hold no code for that, and the library refuses the direct exchange."""
     debug = check_debug(debug)
     real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    if model.n_perturb >= 2 and (family is not None or peer_stores):
+        raise ValueError('the column, lead, line and staged families and the direct exchange take one perturbation variable')
     head = _prologue_lines(model, real, lanes, debug, peer_stores)
     column = family if isinstance(family, ColumnUnit) else None
     staged = family if isinstance(family, dict) else None
@@ -1381,6 +1390,9 @@ def source_key(source):
     # (headers only some units include enter the key of those units alone: an edit there leaves the other code objects valid)
     if '#define SDP_LINE ' in source:
         with open(os.path.join(CSRC, 'sdp_line_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_NW ' in source:
+        with open(os.path.join(CSRC, 'sdp_multiw_kernel.h'), 'rb') as f:
             h.update(f.read())
     h.update(source.encode())
     h.update(' '.join(HIPCC_FLAGS[:-1]).encode())

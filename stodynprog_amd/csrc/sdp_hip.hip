@@ -908,6 +908,7 @@ extern "C" int sdp_comm_barrier(sdp_comm *c)
 struct sdp_problem {
     int dtype = SDP_F64, d = 0, nu = 0, W = 0, lanes = 64, box_per_node = 0, layout = 0, variant = 0;
     int stg_threads = 0, col_seg = 0;
+    int n_perturb = 0;                 // perturbation variables (sdp_problem_desc.n_perturb; >= 2: the flat law of several)
     int64_t stg_tiles = 0;
     int64_t S = 0, node_begin = 0, node_end = 0;
     int32_t orders[SDP_MAXD] = {0, 0, 0, 0};
@@ -1031,11 +1032,14 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
         return fail(SDP_EDIM, "state dimension %d: multilinear interpolation supports 1..4", desc->d);
     if (desc->nu < 1 || desc->nu > SDP_MAXU) return fail(SDP_EINVAL, "number of controls %d outside 1..%d", desc->nu, SDP_MAXU);
     if (desc->W < 0) return fail(SDP_EINVAL, "negative perturbation count");
+    if (desc->n_perturb < 0 || desc->n_perturb > 4) return fail(SDP_EINVAL, "%d perturbation variables: at most 4", (int)desc->n_perturb);
+    if (desc->n_perturb > 0 && desc->W < 1) return fail(SDP_EINVAL, "%d perturbation variables but no point of their law", (int)desc->n_perturb);
     if (!desc->module_path) return fail(SDP_EMODULE, "no model code object given");
     if (!desc->box_lo || !desc->box_hi || !desc->box_n) return fail(SDP_EINVAL, "control box arrays missing");
     sdp_problem *p = new sdp_problem();
     std::unique_ptr<sdp_problem> guard(p);
     p->dtype = desc->dtype; p->d = desc->d; p->nu = desc->nu; p->W = desc->W;
+    p->n_perturb = desc->n_perturb > 0 ? desc->n_perturb : (desc->W > 0 ? 1 : 0);       // (0: "1 when W > 0")
     p->lanes = desc->lanes_per_node; p->box_per_node = desc->box_per_node;
     if (p->lanes < 1 || p->lanes > 64 || (p->lanes & (p->lanes - 1))) return fail(SDP_EINVAL, "lanes_per_node must be a power of two in 1..64");
     const size_t rs = real_size(p->dtype);
@@ -1063,7 +1067,7 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if ((rc = upload(p->axes, ax.data(), ax.size()))) return rc;
     if (p->W > 0) {
         if (!desc->wgrid || !desc->proba) return fail(SDP_EINVAL, "perturbation grid/weights missing");
-        if ((rc = upload(p->wgrid, desc->wgrid, p->W * rs))) return rc;
+        if ((rc = upload(p->wgrid, desc->wgrid, (size_t)p->n_perturb * p->W * rs))) return rc;        // [n_perturb][W]
         if ((rc = upload(p->proba, desc->proba, p->W * rs))) return rc;
     }
     const size_t nbox = (size_t)p->nu * (p->box_per_node ? (size_t)S : 1);
@@ -1144,6 +1148,8 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
         META_CHECK((m[SDP_META_HAS_W] != 0) == (p->W > 0), "built %s a perturbation, the problem has W = %d", m[SDP_META_HAS_W] ? "with" : "without", p->W);
         // (every unit also carries the node-order kernels sdp_sweep / sdp_evalpol: a column or staged unit
         // may serve a node-layout, direct-variant problem; the reverse is what must be refused)
+        META_CHECK((m[SDP_META_NW] ? m[SDP_META_NW] : (m[SDP_META_HAS_W] ? 1 : 0)) == p->n_perturb, "built for %d perturbation variable(s), the problem has %d", m[SDP_META_NW] ? m[SDP_META_NW] : (m[SDP_META_HAS_W] ? 1 : 0), p->n_perturb);
+        META_CHECK(p->n_perturb < 2 || (p->layout == SDP_LAYOUT_NODES && p->variant == SDP_VARIANT_DIRECT), "several perturbation variables run the node layout's direct kernels only");
         META_CHECK(p->layout != SDP_LAYOUT_COLUMNS || m[SDP_META_LAYOUT] == SDP_LAYOUT_COLUMNS, "the column layout was asked of a code object without column kernels");
         META_CHECK(p->variant != SDP_VARIANT_STAGED || (m[SDP_META_FLAGS] & SDP_META_F_STAGED), "the staged-tile variant was asked of a code object without sdp_sweep_lds");
         if (p->layout == SDP_LAYOUT_COLUMNS) {
@@ -2263,7 +2269,7 @@ extern "C" int sdp_problem_simulate(sdp_problem *p, const void *host_pol, int64_
     int rc;
     if ((rc = upload(dpol, host_pol, (size_t)p->nu * p->S * rs))) return rc;
     if ((rc = upload(dx0, host_x0, (size_t)p->d * B * rs))) return rc;
-    if (host_w && T > 0 && (rc = upload(dw, host_w, (size_t)T * B * rs))) return rc;
+    if (host_w && T > 0 && (rc = upload(dw, host_w, (size_t)T * (p->n_perturb > 1 ? p->n_perturb : 1) * B * rs))) return rc;     // [T][n_perturb][B]
     if ((rc = dx.alloc((size_t)(T + 1) * p->d * B * rs))) return rc;
     if ((rc = du.alloc((size_t)T * p->nu * B * rs))) return rc;
     if (host_g && (rc = dg.alloc((size_t)T * B * rs))) return rc;
@@ -2308,12 +2314,16 @@ extern "C" int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int6
     if (B == 0) return SDP_OK;
     if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
     const size_t rs = real_size(p->dtype);
+    const size_t nw = p->n_perturb > 1 ? (size_t)p->n_perturb : 1;
+    // (the draw table in LDS: the cumulative sums, then the values of every variable)
+    if ((size_t)(n_law - 1) * 8 + nw * n_law * rs > 65536)
+        return fail(SDP_EINVAL, "a law of %d points of %d variables needs %zu bytes of LDS: at most 65536", (int)n_law, (int)nw, (size_t)(n_law - 1) * 8 + nw * n_law * rs);
     DevBuf dpol, dx, dacc, dout, dcum, dlaw, docc;
     int rc;
     if ((rc = upload(dpol, host_pol, (size_t)p->nu * p->S * rs))) return rc;
     if ((rc = upload(dx, host_x0, (size_t)p->d * B * rs))) return rc;
     if ((rc = upload(dcum, host_cum, (size_t)n_law * 8))) return rc;
-    if ((rc = upload(dlaw, host_law_grid, (size_t)n_law * rs))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, (size_t)nw * n_law * rs))) return rc;      // [n_perturb][n_law]
     if ((rc = dacc.alloc((size_t)B * rs))) return rc;
     if ((rc = dout.alloc((size_t)B * 8))) return rc;
     HIP_TRY(hipMemsetAsync(dacc.p, 0, (size_t)B * rs, p->stream));
@@ -2336,7 +2346,7 @@ extern "C" int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int6
     // draw table decide how many a CU holds: 8 for the small models, 5 or 6 for the large ones), the rest in a
     // grid-stride loop
     const int threads = 256;
-    const unsigned lds = (unsigned)((size_t)(n_law - 1) * 8 + (size_t)n_law * rs);      // cumulative table, then the values
+    const unsigned lds = (unsigned)((size_t)(n_law - 1) * 8 + nw * n_law * rs);      // cumulative table, then the values
     int per_cu = 0;
     if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p->f_montecarlo, threads, lds) != hipSuccess) {
         (void)hipGetLastError();
@@ -2687,6 +2697,7 @@ extern "C" int sdp_problem_attach_comm(sdp_problem *p, sdp_comm *c, int32_t n_ph
     if (!p) return fail(SDP_EINVAL, "NULL problem");
     if (!c) { p->release_peers(); p->comm = nullptr; p->parts.clear(); p->n_phases = 0; return SDP_OK; }
     if (!part_bounds || n_phases < 1) return fail(SDP_EINVAL, "phase partition missing");
+    if (p->n_perturb > 1 && c->nranks > 1) return fail(SDP_EINVAL, "several perturbation variables run on one GPU");
     const int n = c->nranks;
     std::vector<int64_t> parts(part_bounds, part_bounds + (size_t)n_phases * (n + 1));
     int64_t at = 0;

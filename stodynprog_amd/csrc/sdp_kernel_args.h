@@ -23,8 +23,10 @@ enum {
     SDP_META_THREADS,       // workgroup size of the sweep kernel (column / staged units)
     SDP_META_COL_ROWS,      // rows of axis 0 the table holds (< COL_N0: row window)
     SDP_META_LEAD_AXES,     // SDP_META_F_LEAD units: controlled state variables (the plane-major arrays' "lead" axes)
-    SDP_META_LEAD_PERM      // ... and which state variable logical axis j is (nibble j; stocks first)
-};                          // (word 15: not used, zero)
+    SDP_META_LEAD_PERM,     // ... and which state variable logical axis j is (nibble j; stocks first)
+    SDP_META_NW             // perturbation variables the model entry takes as a vector (sdp_multiw_kernel.h: 2..4); 0: at most
+                            // one, told by SDP_META_HAS_W (every unit of one variable)
+};
 enum {
     SDP_META_F_FILTER = 1, SDP_META_F_WINDOW = 2, SDP_META_F_TRAIL_HAS_U = 4, SDP_META_F_STAGED = 8,
     SDP_META_F_WPAIR = 16, SDP_META_F_LEAN = 32,
@@ -45,7 +47,7 @@ struct SdpSweepArgs {
     void *pol;             // [S*nu] output optimal control VALUES (may be null)
     int32_t *idx;          // [S] output flat C-order index into the control lattice (may be null)
     const void *axes;      // concatenated state-grid axes (reals); axis k at axis_off[k]
-    const void *wgrid;     // [W] perturbation grid (null when W == 0)
+    const void *wgrid;     // [W] perturbation grid (null when W == 0); several variables: [m][W], row i = variable i on the flat law
     const void *proba;     // [W] perturbation weights
     const void *box_lo;    // control box lower ends: [nu] or [nu][S] (per node)
     const void *box_hi;    // control box upper ends
@@ -101,7 +103,7 @@ struct SdpSimArgs {
     const void *pol;       // [nu][S] policy (control VALUES on the state grid), C order
     const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
     const void *x0;        // [d][B] start states
-    const void *w;         // [T][B] perturbation sequences (null: deterministic system)
+    const void *w;         // [T][B] perturbation sequences (null: deterministic system); several variables: [T][m][B]
     void *x;               // [T+1][d][B] states (x[0] = x0)
     void *u;               // [T][nu][B] controls applied
     void *g;               // [T][B] instantaneous costs (may be null)
@@ -120,7 +122,7 @@ struct SdpMcArgs {
     const void *pol;       // [nu][S] policy, like SdpSimArgs
     const void *axes;      // concatenated state-grid axes
     const double *cum;     // [n_law] float64 running sum of the law's probabilities (the last entry is not read)
-    const void *law_grid;  // [n_law] perturbation values (reals)
+    const void *law_grid;  // [n_law] perturbation values (reals); several variables: [m][n_law]
     void *x;               // [d][B] states: x at step_begin in, x at step_end out
     void *acc;             // [B] running cost sums (reals)
     long long *n_outside;  // [B] steps k >= n_burn whose x_k lies outside the state grid or is NaN

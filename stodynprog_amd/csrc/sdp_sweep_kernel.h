@@ -128,6 +128,9 @@ SDP_DEV void sdp_grid_from_args(const SdpSweepArgs &a, SdpGrid<sdp_real, SDP_D> 
     sdp_make_grid<sdp_real, SDP_D>(g, a.orders, smin, smax);
 }
 
+#if defined(SDP_NW) && SDP_NW >= 2
+#include "sdp_multiw_kernel.h"  // the kernels below and sdp_meta for several perturbation variables (w a vector)
+#else
 // expected cost of one (node, control): sum_w p_w * (g + J_next(f))
 template <bool SHIFT = false>
 SDP_DEV sdp_real sdp_expected_cost(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_D> &grid,
@@ -317,3 +320,4 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
     0};
 }
 #endif
+#endif  // SDP_NW

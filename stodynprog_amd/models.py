@@ -511,3 +511,37 @@ def two_reservoirs(api=None, n_a=48, n_b=48, n_y=24, n_w=9, steps=(0.125, 0.125)
     solver.discretize_perturb(-0.3, 0.3, n_w)
     solver.control_steps = steps
     return sysd, solver
+
+
+# ----------------------------------------------------------------------------
+# Two reservoirs, an inflow innovation each: SEVERAL perturbation variables (csrc/sdp_multiw_kernel.h)
+# ----------------------------------------------------------------------------
+def two_inflows(api=None, n_a=24, n_b=24, n_y=12, n_w=(5, 5), steps=(0.125, 0.125)):
+    """The cascade of `two_reservoirs` with a second source of randomness: the upper reservoir is fed by an
+    AR(1) inflow y whose innovation is the first perturbation variable, the lower one also by a lateral inflow,
+    the second variable, independent of the first.  `SysDescription((3, 2, 2))`, two laws and
+    `discretize_perturb(lo1, hi1, n1, lo2, hi2, n2)` are the reference's own interface (stodynprog.py:57-81,
+    :335-362); its sweep stops at `# TODO : implement nD perturbation` (:666).  Here the backup sums over the
+    flat product law of `stodynprog_amd.perturb`."""
+    SysDescription, DPSolver = _classes(api)
+    sysd = SysDescription((3, 2, 2), name='Two inflows')
+
+    def dyn(a, b, y, u, v, w_y, w_b):
+        return (a + (0.7 + 0.5 * y) - u, (b + u - v) + w_b, 0.3 + 0.7 * (y - 0.3) + w_y)
+    sysd.dyn = dyn
+
+    def box(a, b, y):
+        return ((0., 1.), (0., 1.))
+    sysd.control_box = box
+
+    def cost(a, b, y, u, v, w_y, w_b):
+        spill = np.where(a > 1.7, a - 1.7, 0.0 * a) + np.where(b > 1.7, b - 1.7, 0.0 * b)
+        dry = np.where(a < 0.3, 0.3 - a, 0.0 * a) + np.where(b < 0.3, 0.3 - b, 0.0 * b)
+        return (v - 0.8) * (v - 0.8) + 0.05 * (u - v) * (u - v) + 4.0 * spill + 8.0 * dry
+    sysd.cost = cost
+    sysd.perturb_laws = [NormalLaw(0, 0.1), NormalLaw(0, 0.05)]
+    solver = DPSolver(sysd)
+    solver.discretize_state(0., 2., n_a, 0., 2., n_b, -0.2, 0.8, n_y)
+    solver.discretize_perturb(-0.3, 0.3, n_w[0], -0.15, 0.15, n_w[1])
+    solver.control_steps = steps
+    return sysd, solver

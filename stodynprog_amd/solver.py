@@ -30,6 +30,7 @@ from . import _native as nat
 from . import codegen
 from . import convergence as conv
 from . import montecarlo as mc
+from . import perturb
 from .interp import MlinInterpolator
 from .trace import TraceError, trace_model, trace_box, callable_fingerprint, _fp_value, _NoFingerprint
 
@@ -40,7 +41,7 @@ class _DeviceProblem(object):
     """Owner of one sdp_problem handle (include/sdp_hip.h)."""
 
     def __init__(self, desc_arrays, module_path, dtype, shape, nu, W, lanes, box_per_node,
-                 node_range, comm=None, slab_bounds=None, layout=0, staged=None, col_seg_nodes=0):
+                 node_range, comm=None, slab_bounds=None, layout=0, staged=None, col_seg_nodes=0, n_perturb=0):
         self._keep = desc_arrays            # host arrays referenced by the descriptor
         self.layout = int(layout)
         self.dtype = np.dtype(dtype)
@@ -63,6 +64,7 @@ class _DeviceProblem(object):
         d.lanes_per_node = int(lanes)
         d.layout = int(layout)
         d.col_seg_nodes = int(col_seg_nodes)
+        d.n_perturb = int(n_perturb)            # 0: "1 when W > 0"; 2..4: wgrid is [n_perturb][W], the flat law
         d.variant = nat.VARIANT_STAGED if staged else nat.VARIANT_DIRECT
         if staged:
             for k, n in enumerate(staged['tile']):
@@ -607,9 +609,12 @@ class DPSolver(object):
             return model
 
     def _check_supported(self):
-        if len(self.perturb_grid) > 1:
-            raise NotImplementedError('only one perturbation variable is supported '
-                                      '(as in the reference, sdp.py:664-666)')
+        m = len(self.perturb_grid)
+        if m > perturb.MAX_PERTURB:
+            raise NotImplementedError('{} perturbation variables: at most {} are supported (the reference stops at '
+                                      'one, sdp.py:664-666)'.format(m, perturb.MAX_PERTURB))
+        if m > 1 and self.comm is not None:
+            raise NotImplementedError('several perturbation variables run on one GPU (no communicator)')
         d = len(self.state_grid)
         if d > 5:
             raise NotImplementedError('interpolation for state dimension >5'
@@ -709,7 +714,7 @@ class DPSolver(object):
         bp = self._box_plan(box_t)
         lanes = bp['lanes']
         debug = codegen.check_debug(self.debug_defines)
-        W = len(self.perturb_grid[0]) if self.perturb_grid else 0
+        W = self._law_points()
         # The callables are traced afresh on every call (_trace_now), but a trace with the structure and the constants
         # of the last one plans -- and generates -- the same unit: the plan is kept (the source text of a call was a
         # fifth of a millisecond, as much as the kernels of the reference's own problem sizes).
@@ -746,6 +751,8 @@ class DPSolver(object):
         # a CU run the column kernels, with per-node arrays stored axis-0-fastest
         if self.kernel not in ('auto', 'generic', 'column', 'staged', 'lead', 'line'):
             raise ValueError("kernel must be 'auto', 'column', 'lead', 'line', 'staged' or 'generic'")
+        if model.n_perturb >= 2:
+            return self._multiw_plan(model, bp, lanes, debug, W)
         certified = getattr(self, 'certified_filter', True)
         col_family = self.kernel in ('auto', 'column')
         S_nodes = int(np.prod(shape))
@@ -850,6 +857,36 @@ class DPSolver(object):
                     window=window, per_control=per_control, col_seg_nodes=unit.seg_nodes if column else 0,
                     per_node=bp['per_node'], lo=bp['lo'], hi=bp['hi'], n=bp['n'],
                     max_u=bp['max_u'], W=W, box_digest=bp['digest'], box_mode=bp.get('mode'))
+
+    def _multiw_plan(self, model, bp, lanes, debug, W):
+        """the plan of a system with SEVERAL perturbation variables: the node-order kernels of
+        csrc/sdp_multiw_kernel.h on the flat law of `perturb.product_law`, planned before any other family (the fast
+        families -- column, lead, line, staged -- take one variable)"""
+        self._check_supported()
+        if self.kernel not in ('auto', 'generic'):
+            raise ValueError("kernel = '{}' takes one perturbation variable: a system of {} runs the direct node-order "
+                             "kernel (kernel = 'auto' or 'generic')".format(self.kernel, model.n_perturb))
+        source = codegen.translation_unit(model, self.dtype, lanes, None, debug=debug)
+        return dict(model=model, source=source, column=False, unit=None, lanes=lanes, staged=None, filtered=False,
+                    lead_axes=0, lead_perm=None, line=False, window=None, per_control=False, col_seg_nodes=0,
+                    per_node=bp['per_node'], lo=bp['lo'], hi=bp['hi'], n=bp['n'],
+                    max_u=bp['max_u'], W=W, box_digest=bp['digest'], box_mode=bp.get('mode'))
+
+    def _law_points(self):
+        """points of the (flat) perturbation law: W_1 .. W_m; 0 for a deterministic system"""
+        return int(np.prod([len(g) for g in self.perturb_grid], dtype=np.int64)) if self.perturb_grid else 0
+
+    def _flat_law(self):
+        """The law the backups sum over, as the callables see it: (one array of W values per perturbation variable,
+        float64 probabilities [W] or None, W).  One variable: its grid and weights as they are; several: the flat
+        product law of `perturb.product_law` (C order, last variable fastest)."""
+        if not self.perturb_grid:
+            return (), None, 0
+        if len(self.perturb_grid) == 1:
+            return (tuple(self.perturb_grid), np.ascontiguousarray(self.perturb_proba[0], dtype=float),
+                    len(self.perturb_grid[0]))
+        wtab, P = perturb.product_law(self.perturb_grid, self.perturb_proba)
+        return tuple(wtab), P, int(P.size)
 
     @staticmethod
     def _box_constant_along_axis0(bp, shape):
@@ -957,7 +994,10 @@ class DPSolver(object):
             box_lo=np.ascontiguousarray(lo, dtype=dt),
             box_hi=np.ascontiguousarray(hi, dtype=dt),
             box_n=np.ascontiguousarray(n, dtype=np.int32))
-        if W:
+        if W and model.n_perturb >= 2:
+            # (the flat law, rounded ONCE to the problem's reals: perturb.product_law)
+            arrays['wgrid'], arrays['proba'] = perturb.product_law(self.perturb_grid, self.perturb_proba, dt)
+        elif W:
             arrays['wgrid'] = np.ascontiguousarray(self.perturb_grid[0], dtype=dt)
             arrays['proba'] = np.ascontiguousarray(self.perturb_proba[0], dtype=dt)
         module = nat.compile_model(source)
@@ -1008,7 +1048,8 @@ class DPSolver(object):
         prob = _DeviceProblem(arrays, module, dt, shape, len(self.sys.control), W, lanes,
                               per_node, node_range,
                               self.comm if (self.comm is not None and self.comm.is_device) else None,
-                              bounds, layout, plan['staged'], plan['col_seg_nodes'])
+                              bounds, layout, plan['staged'], plan['col_seg_nodes'],
+                              n_perturb=model.n_perturb if model.n_perturb >= 2 else 0)
         self._cache[fp] = prob
         if self._debug_after_create is not None:        # (tools/host_phase_stress.py: poison the fresh buffers)
             self._debug_after_create(prob)
@@ -1312,7 +1353,7 @@ class DPSolver(object):
         shape = self._shape()
         S = int(np.prod(shape))
         nu = len(self.sys.control)
-        W = len(self.perturb_grid[0]) if self.perturb_grid else 0
+        w_args, proba, W = self._flat_law()
         d = len(shape)
         smin = np.array([g[0] for g in self.state_grid], dtype=float)
         smax = np.array([g[-1] for g in self.state_grid], dtype=float)
@@ -1325,7 +1366,6 @@ class DPSolver(object):
         J_k = np.zeros(S)
         idx_k = np.zeros(S, dtype=np.int64)
         pol_k = np.zeros((S, nu))
-        proba = np.ascontiguousarray(self.perturb_proba[0], dtype=float) if W else None
         try:
             batch = []          # (flat, u_grids, dims, x_next[d, cells], g[cells])
             cells = 0
@@ -1361,7 +1401,7 @@ class DPSolver(object):
                 lattice = dims + ((W,) if W else ())
                 for i in range(nu):
                     u_grids[i] = u_grids[i].reshape((1,) * i + (-1,) + (1,) * (nu - i))
-                args = tuple(x_k) + tuple(u_grids) + tuple(self.perturb_grid)
+                args = tuple(x_k) + tuple(u_grids) + w_args
                 if t_k is not None:
                     args = (t_k,) + args
                 x_next = self.sys.dyn(*args, **self.sys.params)
@@ -1417,7 +1457,7 @@ class DPSolver(object):
         nu = len(u_grids)
         for i in range(nu):
             u_grids[i] = u_grids[i].reshape((1,) * i + (-1,) + (1,) * (nu - i))
-        args = tuple(x_k) + tuple(u_grids) + tuple(self.perturb_grid)
+        args = tuple(x_k) + tuple(u_grids) + self._flat_law()[0]
         if t_k is not None:
             args = (t_k,) + args
         return u_grids, dims, args
@@ -1428,7 +1468,7 @@ class DPSolver(object):
         on the device.  Returns (J_xk_opt, u_xk_opt)."""
         u_grids, dims, args = self._node_lattice(x_k, t_k)
         nu = len(u_grids)
-        W = len(self.perturb_grid[0]) if self.perturb_grid else 0
+        _, proba, W = self._flat_law()
         lattice = dims + ((W,) if W else ())
         x_next = self.sys.dyn(*args, **self.sys.params)
         g_grid = self.sys.cost(*args, **self.sys.params)
@@ -1442,7 +1482,6 @@ class DPSolver(object):
         off = np.array([0, gg.size], dtype=np.int64)
         Jb = np.zeros(1)
         ib = np.zeros(1, dtype=np.int64)
-        proba = np.ascontiguousarray(self.perturb_proba[0], dtype=float) if W else None
         nat.check(nat.lib().sdp_tab_backup(tab.h, 1, nat.ptr(off), W, nat.ptr(proba),
                                            nat.ptr(xn), nat.ptr(gg), nat.ptr(Jb),
                                            nat.ptr(ib)))
@@ -1545,12 +1584,13 @@ class DPSolver(object):
         d = len(dims)
         S = int(np.prod(dims))
         nu = len(self.sys.control)
-        w_k = self.perturb_grid[0]
-        W = len(w_k)
+        w_args, proba, W = self._flat_law()
+        if not W:           # (this path has always read perturb_grid[0])
+            raise NotImplementedError('eval_policy of a deterministic system whose callables cannot be traced')
         state_grid = tuple(np.reshape(self.state_grid[i], (1,) * i + (-1,) + (1,) * (d - i))
                            for i in range(d))
         u_k = [pol[..., i].reshape(dims + (1,)) for i in range(nu)]
-        args = state_grid + tuple(u_k) + (w_k,)
+        args = state_grid + tuple(u_k) + w_args
         if not self.sys.stationnary:
             args = (0,) + args                  # like the traced path: time index 0
         x_next = self.sys.dyn(*args, **self.sys.params)
@@ -1560,7 +1600,6 @@ class DPSolver(object):
             [np.broadcast_to(np.asarray(x, dtype=float), lattice).ravel() for x in x_next]))
         gg = np.ascontiguousarray(np.broadcast_to(np.asarray(g, dtype=float), lattice).ravel())
         off = np.arange(S + 1, dtype=np.int64) * W
-        proba = np.ascontiguousarray(self.perturb_proba[0], dtype=float)
         smin = np.array([gr[0] for gr in self.state_grid], dtype=float)
         smax = np.array([gr[-1] for gr in self.state_grid], dtype=float)
         orders = np.array(dims, dtype=np.int64)
@@ -1658,7 +1697,7 @@ class DPSolver(object):
               (as returned by value_iteration / policy_iteration)
         x0  : start state(s), shape (nb_state,) or (B, nb_state)
         w   : perturbation sequence(s), shape (T,) or (T, B); None for a deterministic
-              system (then give n_steps)
+              system (then give n_steps); m >= 2 perturbation variables: (T, m) or (T, m, B)
         t0  : time index of the first step (non-stationary systems)
 
         Returns (x, u, g): states (T+1, [B,] nb_state), controls (T, [B,] nb_control) and
@@ -1677,8 +1716,12 @@ class DPSolver(object):
         if n_w:
             assert w is not None, 'a stochastic system needs the perturbation sequence(s) w'
             w = np.asarray(w, dtype=float)
-            w = w.reshape(-1, 1) if w.ndim == 1 else w
-            assert w.shape[1] == B
+            if n_w >= 2:
+                w = w[:, :, None] if w.ndim == 2 else w
+                assert w.ndim == 3 and w.shape[1] == n_w, 'w must have shape (T, {0}) or (T, {0}, B)'.format(n_w)
+            else:
+                w = w.reshape(-1, 1) if w.ndim == 1 else w
+            assert w.shape[-1] == B
             T = w.shape[0] if n_steps is None else int(n_steps)
             assert w.shape[0] >= T
         else:
@@ -1693,7 +1736,7 @@ class DPSolver(object):
             dt = self.dtype
             pol_d = np.ascontiguousarray(np.moveaxis(pol, -1, 0), dtype=dt)        # [nu][S]
             x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
-            w_d = np.ascontiguousarray(w[:T], dtype=dt) if n_w else None            # [T][B]
+            w_d = np.ascontiguousarray(w[:T], dtype=dt) if n_w else None            # [T][B]; several variables: [T][m][B]
             x = np.empty((T + 1, d, B), dtype=dt)
             u = np.empty((T, nu, B), dtype=dt)
             g = np.empty((T, B), dtype=dt)
@@ -1719,7 +1762,8 @@ class DPSolver(object):
             xs = tuple(x[k, :, i] for i in range(d))
             for c in range(nu):
                 u[k, :, c] = laws[c](*xs)
-            args = xs + tuple(u[k, :, c] for c in range(nu)) + ((w[k],) if w is not None else ())
+            args = xs + tuple(u[k, :, c] for c in range(nu)) + (
+                () if w is None else ((w[k],) if w.ndim == 2 else tuple(w[k])))       # (several variables: w is (T, m, B))
             if not self.sys.stationnary:
                 args = (t0 + k,) + args
             xn = self.sys.dyn(*args, **self.sys.params)
@@ -1732,13 +1776,26 @@ class DPSolver(object):
     def _mc_law(self, law):
         if not self.sys.stochastic:
             raise ValueError('a deterministic system has nothing to draw: use simulate(pol, x0, n_steps=...)')
-        if len(self.sys.perturb) != 1:
-            raise NotImplementedError('monte_carlo draws one perturbation variable')
+        m = len(self.sys.perturb)
+        if m == 1:
+            if law is None:
+                law = (self.perturb_grid[0], self.perturb_proba[0])
+            if len(law) != 2:
+                raise ValueError('law must be (grid, proba)')
+            return mc.check_law(*law)
+        # several variables: ONE draw per step indexes a joint law, values (m, n) and proba (n,) -- by default the
+        # flat product law the DP optimised against (stodynprog_amd.perturb)
+        self._check_supported()
         if law is None:
-            law = (self.perturb_grid[0], self.perturb_proba[0])
+            law = perturb.product_law(self.perturb_grid, self.perturb_proba)
         if len(law) != 2:
-            raise ValueError('law must be (grid, proba)')
-        return mc.check_law(*law)
+            raise ValueError('law must be (values of shape ({}, n), proba of shape (n,))'.format(m))
+        n = np.size(law[1])
+        need = perturb.mc_table_bytes(n, m, self.dtype.itemsize)
+        if n <= mc.MAX_LAW_POINTS and need > perturb.MC_TABLE_BYTES:
+            raise ValueError('a law of {} points of {} variables needs a draw table of {} bytes: at most {} (the LDS the '
+                             'Monte Carlo kernel may ask for)'.format(n, m, need, perturb.MC_TABLE_BYTES))
+        return perturb.check_joint_law(law[0], law[1], m)
 
     @staticmethod
     def _mc_ids(n_traj, traj_offset):
@@ -1754,7 +1811,8 @@ class DPSolver(object):
         (`stodynprog_amd.montecarlo`): trajectories traj_offset .. traj_offset + n_traj - 1, steps
         0 .. n_steps - 1.  Returns (indices, w): (n_steps, n_traj) int32 indices
         into the law and the values law_grid[indices] in the problem's reals, so that
-        `simulate(pol, x0, w)` replays the run.  NOT in the reference API."""
+        `simulate(pol, x0, w)` replays the run (m >= 2 perturbation variables: w is
+        (n_steps, m, n_traj), the columns of the joint law).  NOT in the reference API."""
         grid, proba = self._mc_law(law)
         n_steps = int(n_steps)
         if n_steps < 0:
@@ -1762,6 +1820,8 @@ class DPSolver(object):
         ids = self._mc_ids(n_traj, traj_offset)
         steps = np.arange(n_steps, dtype=np.uint64)
         idx = mc.draws(seed, ids, steps, proba)
+        if grid.ndim == 2:
+            return idx, np.ascontiguousarray(np.moveaxis(grid.astype(self.dtype)[:, idx], 0, 1))
         return idx, grid.astype(self.dtype)[idx]
 
     def monte_carlo(self, pol, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False,
@@ -1780,7 +1840,9 @@ class DPSolver(object):
                    split over calls (traj_offset = id of row 0) do not change a bit
         n_burn   : the first n_burn steps advance the state but enter no reduction
         law      : (grid, proba) of the perturbation, at most 4096 points; default: the solver's
-                   own perturb_grid / perturb_proba, the chain the DP optimised against
+                   own perturb_grid / perturb_proba, the chain the DP optimised against.
+                   m >= 2 perturbation variables: (values (m, n), proba (n,)), a JOINT law (it need
+                   not be a product; default: the flat product law of stodynprog_amd.perturb)
         occupancy: also count, per grid node, the visits of the node nearest to x_k (k >= n_burn)
         t0       : time index of the first step (non-stationary systems)
 
@@ -1827,7 +1889,7 @@ class DPSolver(object):
             pol_d = np.ascontiguousarray(np.moveaxis(pol, -1, 0), dtype=dt)        # [nu][S]
             x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
             cum = np.ascontiguousarray(mc.cumulative(proba))
-            law_d = np.ascontiguousarray(grid, dtype=dt)
+            law_d = np.ascontiguousarray(grid, dtype=dt)                            # [n]; several variables: [m][n]
             cost_sum = np.empty(B, dtype=dt)
             n_out = np.empty(B, dtype=np.int64)
             x_final = np.empty((d, B), dtype=dt)
@@ -1857,7 +1919,8 @@ class DPSolver(object):
         for k0 in range(0, n_steps, self.MC_HOST_BLOCK):
             n = min(self.MC_HOST_BLOCK, n_steps - k0)
             steps = np.arange(k0, k0 + n, dtype=np.uint64)
-            w = wgrid[mc.draws(seed, ids, steps, proba)].astype(float)
+            idx = mc.draws(seed, ids, steps, proba)
+            w = (wgrid[idx] if wgrid.ndim == 1 else np.moveaxis(wgrid[:, idx], 0, 1)).astype(float)
             xs, _, g = self._simulate_host(pol, x, w, n, t0 + k0)
             for i in range(n):
                 if k0 + i < n_burn:
@@ -1933,7 +1996,9 @@ def plan_info(plan):
                       ('reduced array' if plan['lead_axes'] else 'reduced table'))),
         # x0' = a chain of sums in another nesting than ((a +- b) +- ..), x + (w - u): regrouped for the first pass
         regrouped_sums=bool(filtered and shifted and codegen.shift_chain(model)),
-        lanes_per_node=plan['lanes'], max_controls=plan['max_u'], box_per_node=bool(plan['per_node']))
+        lanes_per_node=plan['lanes'], max_controls=plan['max_u'], box_per_node=bool(plan['per_node']),
+        # perturbation variables; 2 or more: kernel 'generic' is the family of csrc/sdp_multiw_kernel.h on their flat law
+        n_perturb=int(model.n_perturb), perturb_vars=int(model.n_perturb))
 
 
 def _params_key(params):
