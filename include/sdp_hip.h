@@ -277,6 +277,53 @@ int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int64_t B, int6
                            int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
                            void *host_x_final, uint64_t *host_occupancy);
 
+/* ---- transition operator of a policy: the forward half of the model -------------
+ * Under a fixed policy the backup of sdp_problem_eval_policy is (P J)(s) + gbar(s), with
+ * (P J)(s) = sum_j P[j] interp(J)(dyn(x_s, pol[s], w_j)).  A sdp_transop holds P^T as a CSR matrix on
+ * the device -- W 2^d entries per node, sorted STABLY by target node so that a row keeps the emission
+ * order (source s, law point j, vertex v ascending) -- and moves a state distribution: mu' = P^T mu,
+ *     out[t]: acc = 0; acc = acc + data[k] * mu[indices[k]]   for k ascending through row t
+ * (one rounded multiply and one rounded add per entry; an empty row gives +0).  The definition, entry
+ * by entry, is stodynprog_amd/forward.py; the interpolation extrapolates, so weights are negative or
+ * above 1 where the model leaves the grid (nothing is clamped: P^T stays the exact adjoint of the
+ * backup).  An operator takes nnz (sizeof(real) + 4) + 8 (S + 1) bytes plus two vectors, and about
+ * three times that while it is built; nnz < 2^32.  One GPU. */
+typedef struct sdp_transop sdp_transop;
+/* Entries from the model's code object (kernel sdp_transitions) at the policy host_pol [S][nu]
+ * (reals, C order: the layout of sdp_problem_set_policy) and time index t_k, with the problem's law
+ * (a deterministic system: one point of weight 1).  The operator does not refer to the problem
+ * afterwards.  SDP_EINVAL with a communicator of several ranks. */
+int sdp_transop_create(sdp_problem *p, const void *host_pol, double t_k, sdp_transop **out);
+/* The same sort and row build on host-given entries in emission order: tgt, src [nnz] node ids in
+ * [0, S) -- anything else is refused with SDP_EINVAL before a byte is allocated -- and val [nnz]
+ * reals of `dtype`.  For models evaluated on the host, and for any sparse chain on S nodes. */
+int sdp_transop_from_coo(int dtype, int64_t S, int64_t nnz, const int32_t *tgt, const int32_t *src,
+                         const void *val, sdp_transop **out);
+int sdp_transop_destroy(sdp_transop *op);
+/* n_steps >= 0 pushes, ping-pong in device memory, no host round trip between them.  host_mu [S]
+ * reals replaces the resident vector first; NULL continues from it (SDP_EINVAL if there is none). */
+int sdp_transop_push(sdp_transop *op, const void *host_mu_or_null, int32_t n_steps);
+/* Pushes from the resident vector until delta = max |mu_{k+1} - mu_k| <= tol, checked after push
+ * check_every, 2 check_every, .. and after push n_max (the reduction of the convergence check above:
+ * a difference is 0 where the two are equal, NaN never converges; 24 bytes come back per check, the
+ * only synchronisations).  *n_done: pushes made; *delta: the last checked value. */
+int sdp_transop_push_until(sdp_transop *op, int32_t n_max, int32_t check_every, double tol,
+                           int32_t *n_done, double *delta);
+int sdp_transop_get(sdp_transop *op, void *host_mu);                 /* S reals: the resident vector */
+/* indptr [S+1], indices [nnz] (the sources), data [nnz] reals; any of them may be NULL */
+int sdp_transop_get_csr(sdp_transop *op, int64_t *indptr, int32_t *indices, void *data);
+/* gbar [S] reals: acc = 0; acc = acc + g_j P[j], j ascending (sdp_transop_create only) */
+int sdp_transop_get_mean_cost(sdp_transop *op, void *host_gbar);
+/* HIP-event duration of the last call's device work (the build, a push, a push_until), ms */
+int sdp_transop_last_kernel_ms(sdp_transop *op, double *ms);
+/* Which rows a push gives to a whole wave (its lanes form the products from coalesced loads, one chain adds them in
+ * entry order: the same bits as the lane-per-row path): those of min_entries entries or more.  The build sets 8;
+ * 0 gives every row to one lane.  A tuning and measuring knob: results do not depend on it. */
+int sdp_transop_set_long_rows(sdp_transop *op, int32_t min_entries);
+/* .. and of the build's two parts: kernel sdp_transitions, and the device work of sort + gather + row pointers
+ * (everything is allocated before the events that bracket it) */
+int sdp_transop_build_ms(sdp_transop *op, double *entries_ms, double *sort_ms);
+
 /* Make the last J_k the next J_next without leaving the device. */
 int sdp_problem_swap(sdp_problem *p);
 

@@ -8,8 +8,8 @@ HIP kernels on gfx950 through the C ABI of include/sdp_hip.h.
     from stodynprog_amd import SysDescription, DPSolver
 """
 from .sysdesc import SysDescription
-from .solver import DPSolver
+from .solver import DPSolver, TransitionOperator
 from .interp import MlinInterpolator
 
 __version__ = '0.1.0'
-__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator']
+__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator']

@@ -113,6 +113,17 @@ def _declare(lib):
         'sdp_problem_simulate': (C.c_int, [vp, vp, i64, i64, vp, vp, dbl, vp, vp, vp]),
         'sdp_problem_montecarlo': (C.c_int, [vp, vp, i64, i64, i64, C.c_uint64, C.c_uint64, vp, vp, i32, vp, dbl,
                                              i64, vp, vp, vp, vp]),
+        'sdp_transop_create': (C.c_int, [vp, vp, dbl, P(vp)]),
+        'sdp_transop_from_coo': (C.c_int, [C.c_int, i64, i64, vp, vp, vp, P(vp)]),
+        'sdp_transop_destroy': (C.c_int, [vp]),
+        'sdp_transop_push': (C.c_int, [vp, vp, i32]),
+        'sdp_transop_push_until': (C.c_int, [vp, i32, i32, dbl, P(i32), P(dbl)]),
+        'sdp_transop_get': (C.c_int, [vp, vp]),
+        'sdp_transop_get_csr': (C.c_int, [vp, vp, vp, vp]),
+        'sdp_transop_get_mean_cost': (C.c_int, [vp, vp]),
+        'sdp_transop_last_kernel_ms': (C.c_int, [vp, P(dbl)]),
+        'sdp_transop_set_long_rows': (C.c_int, [vp, i32]),
+        'sdp_transop_build_ms': (C.c_int, [vp, P(dbl), P(dbl)]),
         'sdp_host_alloc': (C.c_int, [C.c_size_t, P(vp)]),
         'sdp_host_free': (C.c_int, [vp]),
         'sdp_comm_library': (C.c_char_p, []),

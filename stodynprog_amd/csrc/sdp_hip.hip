@@ -16,6 +16,8 @@
 #include <algorithm>
 #include <utility>
 
+#include <rocprim/rocprim.hpp>
+
 #include "../../include/sdp_hip.h"
 #include "sdp_device.h"
 
@@ -936,7 +938,7 @@ struct sdp_problem {
     int64_t stamp_words = 0;
     size_t scratch_bytes = 0;
     hipModule_t mod = nullptr;
-    hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr;
+    hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr, f_transitions = nullptr;
     // several controlled state variables (csrc/sdp_lead_kernel.h): the kernel that reduces V over w, launched
     // before every sweep, and its outputs (A[S] and a copy of V, both plane-major; E[nodes per trailing block];
     // bits of max |V|)
@@ -1219,6 +1221,10 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if (hipModuleGetFunction(&p->f_montecarlo, p->mod, "sdp_montecarlo") != hipSuccess) {
         (void)hipGetLastError();
         p->f_montecarlo = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_transitions, p->mod, "sdp_transitions") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_transitions = nullptr;
     }
     // lifted model constants (codegen: `__constant__ sdp_real sdp_model_prm[]`), if any
     if (hipModuleGetGlobal(&p->prm_dev, &p->prm_bytes, p->mod, "sdp_model_prm") != hipSuccess) {
@@ -2372,6 +2378,508 @@ extern "C" int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int6
     HIP_TRY(hipMemcpy(host_n_outside, dout.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_x_final, dx.p, (size_t)p->d * B * rs, hipMemcpyDeviceToHost));
     if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, (size_t)p->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Transition operator of a policy (stodynprog_amd/forward.py is the definition): the CSR of P^T on the device
+// and the propagation of a state distribution, mu' = P^T mu.  See include/sdp_hip.h.
+//   entries  : kernel sdp_transitions of the model's code object (csrc/sdp_trans_kernel.h), or the host's
+//   CSR      : a STABLE sort of the entry positions by target (rocPRIM's radix sort, on the bits a node id has),
+//              a gather of the values and of the sources, row pointers from a histogram and a scan
+//   k_push   : one lane per short row; k_push_group: one WAVE per row of SDP_PUSH_LONG entries or more, its lanes forming
+//              the products from coalesced loads and one chain adding them in entry order.  Either way the row's
+//              adds happen in entry order (the library is compiled with -ffp-contract=off: one rounded multiply and
+//              one rounded add per entry), so both give the bits of forward.py
+// ---------------------------------------------------------------------------
+struct sdp_transop {
+    int dtype = SDP_F64;
+    int64_t S = 0, nnz = 0;
+    DevBuf indptr, indices, data, gbar, mu[2], stats;
+    DevBuf long_rows;                      // ids of the rows of long_min entries or more (k_push_group), ascending:
+    int64_t n_long = 0, n_wide = 0;        //   first the n_long - n_wide below SDP_PUSH_WIDE entries, then the n_wide others
+    int32_t long_min = 0;                  // 0: every row takes the lane path
+    std::vector<int64_t> h_indptr;         // host copy of the row pointers (the list is made from it)
+    int cur = 0;                           // mu[cur] is the resident vector
+    bool has_gbar = false, has_mu = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    double last_kernel_ms = 0, entries_ms = 0, sort_ms = 0;
+    int cus = 256;
+    ~sdp_transop()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (ev2) (void)hipEventDestroy(ev2);
+        if (ev3) (void)hipEventDestroy(ev3);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+__global__ void __launch_bounds__(256) k_iota(uint32_t *__restrict__ pos, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) pos[i] = (uint32_t)i;
+}
+
+// data[k] = val[pos[k]], indices[k] = the source of entry pos[k]: src[pos[k]], or pos[k] / per_node without a list
+template <typename real>
+__global__ void __launch_bounds__(256) k_trans_gather(const uint32_t *__restrict__ pos, const real *__restrict__ val,
+                                                      const int32_t *__restrict__ src, uint32_t per_node,
+                                                      real *__restrict__ data, int32_t *__restrict__ indices, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const uint32_t e = pos[k];
+        data[k] = val[e];
+        indices[k] = src ? src[e] : (int32_t)(e / per_node);
+    }
+}
+
+// counts[t + 1] += 1 per entry of target t (integer sums do not depend on the order); counts[0] stays 0
+__global__ void __launch_bounds__(256) k_trans_count(const int32_t *__restrict__ tgt, int64_t n,
+                                                     unsigned long long *__restrict__ counts)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride)
+        atomicAdd(counts + 1 + tgt[k], 1ull);
+}
+
+// A row of this many entries or more is pushed by a whole wave (k_push_group), a shorter one by one lane (k_push).
+// The lane path walks a row through a chain of dependent loads, one trip to memory per entry, and a grid of S lanes
+// is under two waves per SIMD on the grids this library meets (measured on Searev's 115 351 rows: 2.3 us per trip,
+// 72 trips on average); a wave costs one coalesced trip per 64 entries and then adds at register speed.  From 8
+// entries on the trip saved outweighs the 56 idle lanes.
+#define SDP_PUSH_LONG 8
+
+// out[t] = sum over the row of data[k] * mu[indices[k]], k ascending: acc = 0; acc = acc + data[k] * mu[..]
+// (row pointers and sources are trusted: the build made them from node ids, sdp_transop_from_coo checked its own).
+// Rows of long_min entries or more are left to k_push_group (long_min = 0: none is).
+template <typename real>
+__global__ void __launch_bounds__(256) k_push(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                              const real *__restrict__ data, const real *__restrict__ mu,
+                                              real *__restrict__ out, int64_t S, int32_t long_min)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < S; t += stride) {
+        const int64_t b = indptr[t], e = indptr[t + 1];
+        if (long_min > 0 && e - b >= long_min) continue;
+        real acc = real(0);
+        for (int64_t k = b; k < e; ++k) acc = acc + data[k] * mu[indices[k]];
+        out[t] = acc;
+    }
+}
+
+// A listed row takes a GROUP of G lanes, 64 / G rows to a wave: G entries at a time, lane l of the group forms the
+// product of entry off + l (coalesced loads of data and indices, a gather of mu), then ONE chain per group adds the
+// products in entry order -- acc = acc + product of lane 0, 1, .. of the group, read through a cross-lane shuffle --
+// so the sum has the roundings of the lane path; positions past the row's end add nothing.  One instruction of the
+// chain serves the 64 / G rows of the wave.  acc is the same in every lane of a group; its lane 0 stores it.
+// G = 16 for rows below SDP_PUSH_WIDE entries, G = 64 from there on (a trip to memory per 64 entries, not per 16).
+#define SDP_PUSH_WIDE 256
+template <typename real, int G>
+__global__ void __launch_bounds__(256) k_push_group(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                    const real *__restrict__ data, const real *__restrict__ mu,
+                                                    real *__restrict__ out, const int32_t *__restrict__ rows, int64_t n_rows)
+{
+    constexpr int PER = 64 / G;                                // rows of a wave
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1), grp = lane / G;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t w = wave; w * PER < n_rows; w += waves) {     // the same trips in every lane of a wave
+        const int64_t r = w * PER + grp;
+        const bool live = r < n_rows;
+        const int32_t t = live ? rows[r] : 0;
+        int64_t b = 0, e = 0;
+        if (live) { b = indptr[t]; e = indptr[t + 1]; }
+        long long longest = e - b;                             // of the wave's rows: every lane runs that many chunks
+#pragma unroll
+        for (int m = G; m < 64; m <<= 1) {
+            const long long o = __shfl_xor(longest, m, 64);
+            longest = o > longest ? o : longest;
+        }
+        real acc = real(0);
+        for (int64_t off = 0; off < longest; off += G) {
+            const int64_t k = b + off + sub;
+            real p = real(0);
+            if (k < e) p = data[k] * mu[indices[k]];
+            const int64_t left = e - b - off;
+            const int n = left < G ? (left > 0 ? (int)left : 0) : G;      // entries of this group's row in the chunk
+#pragma unroll 16
+            for (int i = 0; i < G; ++i) {
+                const real q = __shfl(p, i, G);
+                acc = i < n ? acc + q : acc;
+            }
+        }
+        if (live && sub == 0) out[t] = acc;
+    }
+}
+
+static unsigned stream_blocks(const sdp_transop *op, int64_t n)
+{
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > (int64_t)op->cus * 8) blocks = (int64_t)op->cus * 8;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+static int transop_new(int dtype, int64_t S, int64_t nnz, sdp_transop **out)
+{
+    sdp_transop *op = new sdp_transop();
+    op->dtype = dtype; op->S = S; op->nnz = nnz; op->cus = device_cus();
+    std::unique_ptr<sdp_transop> guard(op);
+    HIP_TRY(hipStreamCreate(&op->stream));
+    HIP_TRY(hipEventCreate(&op->ev0));
+    HIP_TRY(hipEventCreate(&op->ev1));
+    HIP_TRY(hipEventCreate(&op->ev2));
+    HIP_TRY(hipEventCreate(&op->ev3));
+    guard.release();
+    *out = op;
+    return SDP_OK;
+}
+
+// entries in emission order on the device (tgt, val; src or, without one, per_node entries per source) -> the CSR
+// the list of rows of `min_len` entries or more, from the host copy of the row pointers (min_len <= 0: no list)
+static int transop_list_long_rows(sdp_transop *op, int32_t min_len)
+{
+    std::vector<int32_t> rows, wide;
+    if (min_len > 0)
+        for (int64_t t = 0; t < op->S; ++t) {
+            const int64_t len = op->h_indptr[(size_t)t + 1] - op->h_indptr[(size_t)t];
+            if (len >= min_len) (len >= SDP_PUSH_WIDE ? wide : rows).push_back((int32_t)t);
+        }
+    op->n_wide = (int64_t)wide.size();
+    rows.insert(rows.end(), wide.begin(), wide.end());
+    HIP_TRY(hipStreamSynchronize(op->stream));             // (no push in flight reads the old list)
+    int rc;
+    if ((rc = upload(op->long_rows, rows.data(), rows.size() * 4))) return rc;
+    op->n_long = (int64_t)rows.size();
+    op->long_min = min_len > 0 ? min_len : 0;
+    return SDP_OK;
+}
+
+// entries in emission order on the device (tgt, val; src or, without one, per_node entries per source) -> the CSR.
+// Everything is allocated first; ev2 .. ev3 then bracket the device work alone (sort, gather, histogram, scan).
+static int transop_build_csr(sdp_transop *op, const int32_t *tgt, const void *val, const int32_t *src, uint32_t per_node)
+{
+    const size_t rs = real_size(op->dtype);
+    const int64_t n = op->nnz, S = op->S;
+    int rc;
+    DevBuf counts, keys_out, pos, pos_out, tmp_sort, tmp_scan;
+    if ((rc = op->indptr.alloc((size_t)(S + 1) * 8))) return rc;
+    if ((rc = op->indices.alloc((size_t)n * 4))) return rc;
+    if ((rc = op->data.alloc((size_t)n * rs))) return rc;
+    if ((rc = counts.alloc((size_t)(S + 1) * 8))) return rc;
+    unsigned bits = 1;                                     // bits of the largest node id
+    while (bits < 32 && ((int64_t)1 << bits) < S) ++bits;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    if (n > 0) {
+        if ((rc = keys_out.alloc((size_t)n * 4))) return rc;
+        if ((rc = pos.alloc((size_t)n * 4))) return rc;
+        if ((rc = pos_out.alloc((size_t)n * 4))) return rc;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t *)tgt, (uint32_t *)keys_out.p, (const uint32_t *)pos.p,
+                                          (uint32_t *)pos_out.p, (size_t)n, 0u, bits, op->stream));
+        if ((rc = tmp_sort.alloc(sort_bytes))) return rc;
+    }
+    HIP_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, (const int64_t *)counts.p, (int64_t *)op->indptr.p, (size_t)(S + 1),
+                                    rocprim::plus<int64_t>(), op->stream));
+    if ((rc = tmp_scan.alloc(scan_bytes))) return rc;
+    HIP_TRY(hipEventRecord(op->ev2, op->stream));
+    HIP_TRY(hipMemsetAsync(counts.p, 0, (size_t)(S + 1) * 8, op->stream));
+    if (n > 0) {
+        hipLaunchKernelGGL(k_iota, dim3(stream_blocks(op, n)), dim3(256), 0, op->stream, (uint32_t *)pos.p, n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::radix_sort_pairs(tmp_sort.p, sort_bytes, (const uint32_t *)tgt, (uint32_t *)keys_out.p, (const uint32_t *)pos.p,
+                                          (uint32_t *)pos_out.p, (size_t)n, 0u, bits, op->stream));
+        if (op->dtype == SDP_F32)
+            hipLaunchKernelGGL(k_trans_gather<float>, dim3(stream_blocks(op, n)), dim3(256), 0, op->stream, (const uint32_t *)pos_out.p,
+                               (const float *)val, src, per_node, (float *)op->data.p, (int32_t *)op->indices.p, n);
+        else
+            hipLaunchKernelGGL(k_trans_gather<double>, dim3(stream_blocks(op, n)), dim3(256), 0, op->stream, (const uint32_t *)pos_out.p,
+                               (const double *)val, src, per_node, (double *)op->data.p, (int32_t *)op->indices.p, n);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_trans_count, dim3(stream_blocks(op, n)), dim3(256), 0, op->stream, tgt, n, (unsigned long long *)counts.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(rocprim::inclusive_scan(tmp_scan.p, scan_bytes, (const int64_t *)counts.p, (int64_t *)op->indptr.p, (size_t)(S + 1),
+                                    rocprim::plus<int64_t>(), op->stream));
+    HIP_TRY(hipEventRecord(op->ev3, op->stream));
+    op->h_indptr.resize((size_t)S + 1);
+    HIP_TRY(hipMemcpyAsync(op->h_indptr.data(), op->indptr.p, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));             // (the temporaries go out of scope)
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev2, op->ev3));
+    op->sort_ms = ms;
+    return transop_list_long_rows(op, SDP_PUSH_LONG);
+}
+
+extern "C" int sdp_transop_create(sdp_problem *p, const void *host_pol, double t_k, sdp_transop **out)
+{
+    if (!p || !host_pol || !out) return fail(SDP_EINVAL, "NULL argument");
+    if (p->comm && p->comm->nranks > 1) return fail(SDP_EINVAL, "a transition operator is built on one GPU");
+    if (!p->f_transitions) return fail(SDP_EMODULE, "the model's code object has no sdp_transitions kernel");
+    const size_t rs = real_size(p->dtype);
+    const int64_t W = p->W > 0 ? p->W : 1, V = (int64_t)1 << p->d;
+    const int64_t nnz = p->S * W * V;
+    if (nnz >= (int64_t)1 << 32)
+        return fail(SDP_EINVAL, "an operator of %lld entries: entry positions are 32-bit words (at most 2^32 - 1 entries)", (long long)nnz);
+    sdp_transop *op = nullptr;
+    int rc;
+    if ((rc = transop_new(p->dtype, p->S, nnz, &op))) return rc;
+    std::unique_ptr<sdp_transop> guard(op);
+    DevBuf dpol, done, tgt, val;
+    if ((rc = upload(dpol, host_pol, (size_t)p->S * p->nu * rs))) return rc;
+    if (p->W <= 0) {                                       // a deterministic system: the law of one point of weight 1
+        const double one8 = 1.0;
+        const float one4 = 1.0f;
+        if ((rc = upload(done, p->dtype == SDP_F32 ? (const void *)&one4 : (const void *)&one8, rs))) return rc;
+    }
+    if ((rc = tgt.alloc((size_t)nnz * 4))) return rc;
+    if ((rc = val.alloc((size_t)nnz * rs))) return rc;
+    if ((rc = op->gbar.alloc((size_t)p->S * rs))) return rc;
+    SdpTransArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.axes = p->axes.p;
+    a.wtab = p->W > 0 ? p->wgrid.p : nullptr;
+    a.proba = p->W > 0 ? p->proba.p : done.p;
+    a.tgt = (int32_t *)tgt.p; a.val = val.p; a.gbar = op->gbar.p;
+    a.S = p->S; a.t_k = t_k; a.W = (int32_t)W;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    int64_t blocks = (p->S * V + 255) / 256;
+    if (blocks > (int64_t)p->cus * 8) blocks = (int64_t)p->cus * 8;
+    HIP_TRY(hipStreamSynchronize(p->stream));        // lifted constants set on the problem stream
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    HIP_TRY(hipModuleLaunchKernel(p->f_transitions, (unsigned)blocks, 1, 1, 256, 1, 1, 0, op->stream, nullptr, extra));
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    if ((rc = transop_build_csr(op, (const int32_t *)tgt.p, val.p, nullptr, (uint32_t)(W * V)))) return rc;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    op->entries_ms = ms;
+    op->last_kernel_ms = op->entries_ms + op->sort_ms;
+    op->has_gbar = true;
+    guard.release();
+    *out = op;
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_from_coo(int dtype, int64_t S, int64_t nnz, const int32_t *tgt, const int32_t *src,
+                                    const void *val, sdp_transop **out)
+{
+    if (!out) return fail(SDP_EINVAL, "NULL argument");
+    if (dtype != SDP_F64 && dtype != SDP_F32) return fail(SDP_EINVAL, "dtype must be SDP_F64 or SDP_F32");
+    if (S < 1 || S >= (int64_t)1 << 31) return fail(SDP_EINVAL, "S = %lld: an operator has 1 to 2^31 - 1 nodes", (long long)S);
+    if (nnz < 0 || nnz >= (int64_t)1 << 32) return fail(SDP_EINVAL, "nnz = %lld: 0 to 2^32 - 1 entries (32-bit entry positions)", (long long)nnz);
+    if (nnz > 0 && (!tgt || !src || !val)) return fail(SDP_EINVAL, "NULL argument");
+    for (int64_t k = 0; k < nnz; ++k) {                    // before anything is allocated or launched
+        if (tgt[k] < 0 || tgt[k] >= S) return fail(SDP_EINVAL, "entry %lld: target %d outside [0, %lld)", (long long)k, (int)tgt[k], (long long)S);
+        if (src[k] < 0 || src[k] >= S) return fail(SDP_EINVAL, "entry %lld: source %d outside [0, %lld)", (long long)k, (int)src[k], (long long)S);
+    }
+    const size_t rs = real_size(dtype);
+    sdp_transop *op = nullptr;
+    int rc;
+    if ((rc = transop_new(dtype, S, nnz, &op))) return rc;
+    std::unique_ptr<sdp_transop> guard(op);
+    DevBuf dtgt, dsrc, dval;
+    if ((rc = upload(dtgt, tgt, (size_t)nnz * 4))) return rc;
+    if ((rc = upload(dsrc, src, (size_t)nnz * 4))) return rc;
+    if ((rc = upload(dval, val, (size_t)nnz * rs))) return rc;
+    if ((rc = transop_build_csr(op, (const int32_t *)dtgt.p, dval.p, (const int32_t *)dsrc.p, 1u))) return rc;
+    op->last_kernel_ms = op->sort_ms;
+    guard.release();
+    *out = op;
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_destroy(sdp_transop *op)
+{
+    if (op) { (void)hipStreamSynchronize(op->stream); delete op; }
+    return SDP_OK;
+}
+
+template <typename real>
+static int transop_launch_push_as(sdp_transop *op)
+{
+    const real *in = (const real *)op->mu[op->cur].p;
+    real *outp = (real *)op->mu[1 - op->cur].p;
+    const int64_t *indptr = (const int64_t *)op->indptr.p;
+    const int32_t *indices = (const int32_t *)op->indices.p;
+    const real *data = (const real *)op->data.p;
+    // the short rows, one lane each: at most the workgroups that are resident, the rest in a grid-stride loop
+    if (op->n_long < op->S) {
+        int64_t blocks = (op->S + 255) / 256;
+        if (blocks > (int64_t)op->cus * 8) blocks = (int64_t)op->cus * 8;
+        hipLaunchKernelGGL(k_push<real>, dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp, op->S,
+                           op->long_min);
+        HIP_TRY(hipGetLastError());
+    }
+    // the long rows: four to a wave (sixteen to a workgroup), the widest one to a wave
+    const int32_t *rows = (const int32_t *)op->long_rows.p;
+    const int64_t n_mid = op->n_long - op->n_wide;
+    if (n_mid > 0) {
+        int64_t blocks = (n_mid + 15) / 16;
+        if (blocks > (int64_t)op->cus * 64) blocks = (int64_t)op->cus * 64;
+        hipLaunchKernelGGL((k_push_group<real, 16>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp,
+                           rows, n_mid);
+        HIP_TRY(hipGetLastError());
+    }
+    if (op->n_wide > 0) {
+        int64_t blocks = (op->n_wide + 3) / 4;
+        if (blocks > (int64_t)op->cus * 64) blocks = (int64_t)op->cus * 64;
+        hipLaunchKernelGGL((k_push_group<real, 64>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp,
+                           rows + n_mid, op->n_wide);
+        HIP_TRY(hipGetLastError());
+    }
+    op->cur = 1 - op->cur;
+    return SDP_OK;
+}
+
+static int transop_launch_push(sdp_transop *op)
+{
+    return op->dtype == SDP_F32 ? transop_launch_push_as<float>(op) : transop_launch_push_as<double>(op);
+}
+
+static int transop_set(sdp_transop *op, const void *host_mu)
+{
+    const size_t bytes = (size_t)op->S * real_size(op->dtype);
+    int rc;
+    for (int k = 0; k < 2; ++k)
+        if (!op->mu[k].p && (rc = op->mu[k].alloc(bytes))) return rc;
+    if (host_mu) {
+        HIP_TRY(hipMemcpyAsync(op->mu[op->cur].p, host_mu, bytes, hipMemcpyHostToDevice, op->stream));
+        HIP_TRY(hipStreamSynchronize(op->stream));         // `host_mu` may be reused by the caller
+        op->has_mu = true;
+    }
+    if (!op->has_mu) return fail(SDP_EINVAL, "no resident vector: the first push needs host_mu");
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_push(sdp_transop *op, const void *host_mu, int32_t n_steps)
+{
+    if (!op) return fail(SDP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(SDP_EINVAL, "n_steps must not be negative");
+    int rc;
+    if ((rc = transop_set(op, host_mu))) return rc;
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    for (int32_t k = 0; k < n_steps; ++k)
+        if ((rc = transop_launch_push(op))) return rc;
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    op->last_kernel_ms = ms;
+    return SDP_OK;
+}
+
+// delta = max |new - old| over the nodes: max(dmax, -dmin) of k_diff_stats (NaN if any difference is); 24 bytes back
+static int transop_delta(sdp_transop *op, double &delta)
+{
+    int rc;
+    if (!op->stats.p && (rc = op->stats.alloc(3 * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(op->stats.p, 0, 3 * 8, op->stream));
+    SdpStatRanges r;
+    memset(&r, 0, sizeof(r));
+    r.n = 1; r.b[0] = 0; r.e[0] = op->S;
+    const int vec = op->dtype == SDP_F32 ? 4 : 2;
+    int64_t blocks = (op->S / vec + 255) / 256;
+    if (blocks > (int64_t)op->cus * 4) blocks = (int64_t)op->cus * 4;
+    if (blocks < 1) blocks = 1;
+    unsigned long long *acc = (unsigned long long *)op->stats.p;
+    const void *cur = op->mu[op->cur].p, *old = op->mu[1 - op->cur].p;
+    if (op->dtype == SDP_F32)
+        hipLaunchKernelGGL(k_diff_stats<float>, dim3((unsigned)blocks), dim3(256), 0, op->stream,
+                           (const float *)cur, (const float *)old, (int64_t)-1, (int64_t)-1, r, acc);
+    else
+        hipLaunchKernelGGL(k_diff_stats<double>, dim3((unsigned)blocks), dim3(256), 0, op->stream,
+                           (const double *)cur, (const double *)old, (int64_t)-1, (int64_t)-1, r, acc);
+    HIP_TRY(hipGetLastError());
+    unsigned long long keys[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(keys, op->stats.p, 3 * 8, hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    if (keys[2]) { delta = NAN; return SDP_OK; }
+    const double dmin = sdp_key_value(~keys[0]), dmax = sdp_key_value(keys[1]);
+    delta = dmax > -dmin ? dmax : -dmin;
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_push_until(sdp_transop *op, int32_t n_max, int32_t check_every, double tol,
+                                      int32_t *n_done, double *delta)
+{
+    if (!op || !n_done || !delta) return fail(SDP_EINVAL, "NULL argument");
+    if (n_max < 1) return fail(SDP_EINVAL, "n_max must be at least 1");
+    if (check_every < 1) return fail(SDP_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0)) return fail(SDP_EINVAL, "tol must be a number >= 0");
+    int rc;
+    if ((rc = transop_set(op, nullptr))) return rc;
+    int32_t done = 0;
+    double d = NAN;
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    for (int32_t k = 0; k < n_max; ++k) {
+        if ((rc = transop_launch_push(op))) return rc;
+        done = k + 1;
+        if (done % check_every == 0 || done == n_max) {
+            if ((rc = transop_delta(op, d))) return rc;
+            if (d <= tol) break;                            // NaN never converges
+        }
+    }
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    op->last_kernel_ms = ms;
+    *n_done = done;
+    *delta = d;
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_get(sdp_transop *op, void *host_mu)
+{
+    if (!op || !host_mu) return fail(SDP_EINVAL, "NULL argument");
+    if (!op->has_mu) return fail(SDP_EINVAL, "no resident vector: nothing was pushed yet");
+    HIP_TRY(hipMemcpyAsync(host_mu, op->mu[op->cur].p, (size_t)op->S * real_size(op->dtype), hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_get_csr(sdp_transop *op, int64_t *indptr, int32_t *indices, void *data)
+{
+    if (!op) return fail(SDP_EINVAL, "NULL argument");
+    if (indptr) HIP_TRY(hipMemcpyAsync(indptr, op->indptr.p, (size_t)(op->S + 1) * 8, hipMemcpyDeviceToHost, op->stream));
+    if (indices && op->nnz) HIP_TRY(hipMemcpyAsync(indices, op->indices.p, (size_t)op->nnz * 4, hipMemcpyDeviceToHost, op->stream));
+    if (data && op->nnz) HIP_TRY(hipMemcpyAsync(data, op->data.p, (size_t)op->nnz * real_size(op->dtype), hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_get_mean_cost(sdp_transop *op, void *host_gbar)
+{
+    if (!op || !host_gbar) return fail(SDP_EINVAL, "NULL argument");
+    if (!op->has_gbar) return fail(SDP_EINVAL, "an operator made of host entries has no mean cost");
+    HIP_TRY(hipMemcpyAsync(host_gbar, op->gbar.p, (size_t)op->S * real_size(op->dtype), hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_last_kernel_ms(sdp_transop *op, double *ms)
+{
+    if (!op || !ms) return fail(SDP_EINVAL, "NULL argument");
+    *ms = op->last_kernel_ms;
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_set_long_rows(sdp_transop *op, int32_t min_entries)
+{
+    if (!op) return fail(SDP_EINVAL, "NULL argument");
+    if (min_entries < 0) return fail(SDP_EINVAL, "min_entries must not be negative");
+    return transop_list_long_rows(op, min_entries);
+}
+
+extern "C" int sdp_transop_build_ms(sdp_transop *op, double *entries_ms, double *sort_ms)
+{
+    if (!op || !entries_ms || !sort_ms) return fail(SDP_EINVAL, "NULL argument");
+    *entries_ms = op->entries_ms;
+    *sort_ms = op->sort_ms;
     return SDP_OK;
 }
 

@@ -141,6 +141,25 @@ struct SdpMcArgs {
     int32_t axis_off[SDP_MAXD];
 };
 
+// Entries of the transition operator of a policy (sdp_trans_kernel.h): per node s (flat C-order id), point j of
+// the flat law and vertex v of the interpolation cell of the next state, the target node and the weight at
+// position (s W + j) 2^d + v, and the mean cost of every node.
+struct SdpTransArgs {
+    const void *pol;       // [S][nu] policy (control VALUES at the nodes), C order whatever the unit's layout
+    const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
+    const void *wtab;      // [W] perturbation values; several variables: [m][W]; not read by a deterministic unit
+    const void *proba;     // [W] weights of the flat law (a deterministic system: the one weight 1)
+    int32_t *tgt;          // [S W 2^d] target nodes, flat C-order ids
+    void *val;             // [S W 2^d] weights (reals)
+    void *gbar;            // [S] mean cost of one step under the policy (reals)
+    int64_t S;             // state nodes
+    double t_k;            // time index (non-stationary systems)
+    int32_t W;             // points of the flat law (>= 1)
+    int32_t pad_;
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+};
+
 // Stand-alone multilinear interpolation (multilinear_cython.pyx:17-49).
 struct SdpInterpArgs {
     const void *values;    // [n_v][S]

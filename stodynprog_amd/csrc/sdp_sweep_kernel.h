@@ -130,6 +130,7 @@ SDP_DEV void sdp_grid_from_args(const SdpSweepArgs &a, SdpGrid<sdp_real, SDP_D> 
 
 #if defined(SDP_NW) && SDP_NW >= 2
 #include "sdp_multiw_kernel.h"  // the kernels below and sdp_meta for several perturbation variables (w a vector)
+#include "sdp_trans_kernel.h"   // sdp_transitions on the flat law
 #else
 // expected cost of one (node, control): sum_w p_w * (g + J_next(f))
 template <bool SHIFT = false>
@@ -293,6 +294,7 @@ extern "C" __global__ void __launch_bounds__(64) sdp_simulate(SdpSimArgs a)
 #if SDP_HAS_W
 #include "sdp_mc_kernel.h"      // sdp_montecarlo: the same loop with the perturbation drawn on the device, reduced per trajectory
 #endif
+#include "sdp_trans_kernel.h"   // sdp_transitions: the entries of the policy's transition operator (deterministic units too)
 
 // what this code object was generated for (sdp_kernel_args.h, SDP_META_*); units that include
 // sdp_column_kernel.h define it at the end of that file, where the column macros are complete

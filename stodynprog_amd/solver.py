@@ -29,12 +29,13 @@ import numpy as np
 from . import _native as nat
 from . import codegen
 from . import convergence as conv
+from . import forward
 from . import montecarlo as mc
 from . import perturb
 from .interp import MlinInterpolator
 from .trace import TraceError, trace_model, trace_box, callable_fingerprint, _fp_value, _NoFingerprint
 
-__all__ = ['DPSolver']
+__all__ = ['DPSolver', 'TransitionOperator']
 
 
 class _DeviceProblem(object):
@@ -234,6 +235,121 @@ class _DeviceProblem(object):
         return loop.value, kern.value
 
 
+class TransitionOperator(object):
+    """The transition operator of a policy on the device (`DPSolver.transition_operator`): P^T as a CSR matrix in
+    device memory, owner of one sdp_transop handle (include/sdp_hip.h).  `stodynprog_amd.forward` is the definition
+    of every number it returns.  NOT in the reference API.
+
+    shape     : the state grid's
+    nnz       : entries, S W 2^d
+    mean_cost : gbar, the expected cost of one step from every node (grid shape)
+    path      : 'device' (entries from kernel sdp_transitions) or 'host' (callables evaluated on the host, entries
+                uploaded: models that cannot be traced)"""
+
+    def __init__(self, handle, shape, dtype, nnz, mean_cost, path):
+        self.h = handle
+        self.shape = tuple(shape)
+        self.dtype = np.dtype(dtype)
+        self.S = int(np.prod(self.shape))
+        self.nnz = int(nnz)
+        self.mean_cost = mean_cost
+        self.path = path
+        self.nbytes = forward.operator_bytes(self.nnz, self.S, self.dtype.itemsize)
+        self.info = dict(nnz=self.nnz, bytes=self.nbytes, path=path)
+        entries_ms, sort_ms = C.c_double(0.0), C.c_double(0.0)
+        nat.check(nat.lib().sdp_transop_build_ms(self.h, C.byref(entries_ms), C.byref(sort_ms)))
+        self.info.update(build_ms=entries_ms.value + sort_ms.value, entries_ms=entries_ms.value, sort_ms=sort_ms.value)
+
+    @classmethod
+    def from_coo(cls, shape, tgt, src, val, mean_cost=None, path='host'):
+        """the operator of host-given entries in emission order (sdp_transop_from_coo): tgt, src node ids, val reals
+        (their type is the operator's)"""
+        nat.require_gpu()
+        shape = tuple(int(n) for n in np.atleast_1d(shape))
+        S = int(np.prod(shape))
+        val = np.ascontiguousarray(val)
+        tgt = np.ascontiguousarray(tgt, dtype=np.int32)
+        src = np.ascontiguousarray(src, dtype=np.int32)
+        if not (tgt.shape == src.shape == val.shape and tgt.ndim == 1):
+            raise ValueError('tgt, src and val must be vectors of one length')
+        h = C.c_void_p()
+        nat.check(nat.lib().sdp_transop_from_coo(nat.np_real(val.dtype), S, tgt.size, nat.ptr(tgt), nat.ptr(src),
+                                                 nat.ptr(val), C.byref(h)))
+        return cls(h, shape, val.dtype, tgt.size, mean_cost, path)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            nat.lib().sdp_transop_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError('the operator is closed')
+        return self.h
+
+    def _vector(self, mu):
+        mu = np.asarray(mu)
+        if mu.size != self.S:
+            raise ValueError('mu has {} entries, the grid {} nodes'.format(mu.size, self.S))
+        return np.ascontiguousarray(mu, dtype=self.dtype).reshape(-1)
+
+    def _kernel_ms(self):
+        ms = C.c_double(0.0)
+        nat.check(nat.lib().sdp_transop_last_kernel_ms(self._handle(), C.byref(ms)))
+        return ms.value
+
+    def push(self, mu, n_steps=1):
+        """mu after n_steps steps under the policy, (P^T)^n mu: an array of grid shape in the problem's dtype.  The
+        steps run back to back on the device."""
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError('n_steps must not be negative')
+        nat.check(nat.lib().sdp_transop_push(self._handle(), nat.ptr(self._vector(mu)), n_steps))
+        self.info.update(push_ms=self._kernel_ms(), pushes=n_steps)
+        out = np.empty(self.S, dtype=self.dtype)
+        nat.check(nat.lib().sdp_transop_get(self.h, nat.ptr(out)))
+        return out.reshape(self.shape)
+
+    def stationary(self, mu0=None, tol=1e-12, n_max=10000, check_every=10):
+        """Power iteration mu <- P^T mu from mu0 (default: uniform) until max |mu_{k+1} - mu_k| <= tol at a checked
+        push (every check_every-th and the n_max-th), without renormalisation or damping (`forward.stationary` is the
+        definition).  Returns a `forward.Stationary` record: mu (grid shape), n_done, converged, delta,
+        average_cost = dot(mu, mean_cost) (computed on the host) and mass = mu.sum()."""
+        tol, check_every = conv.validate(tol, check_every)
+        n_max = int(n_max)
+        if n_max < 1:
+            raise ValueError('n_max must be at least 1')
+        mu0 = forward.uniform(self.S, self.dtype) if mu0 is None else self._vector(mu0)
+        nat.check(nat.lib().sdp_transop_push(self._handle(), nat.ptr(mu0), 0))
+        n_done, delta = C.c_int32(0), C.c_double(0.0)
+        nat.check(nat.lib().sdp_transop_push_until(self.h, n_max, check_every, tol, C.byref(n_done), C.byref(delta)))
+        self.info.update(push_ms=self._kernel_ms(), pushes=n_done.value)
+        mu = np.empty(self.S, dtype=self.dtype)
+        nat.check(nat.lib().sdp_transop_get(self.h, nat.ptr(mu)))
+        return forward.finish(mu.reshape(self.shape), n_done.value, delta.value, tol, self.mean_cost)
+
+    def set_long_rows(self, min_entries):
+        """Which rows a push gives to a whole wave instead of one lane: those of `min_entries` entries or more (the
+        build sets 8; 0: every row to one lane).  A tuning and measuring knob (tools/forward_times.py): both paths add a
+        row's products in entry order, so no result depends on it."""
+        nat.check(nat.lib().sdp_transop_set_long_rows(self._handle(), int(min_entries)))
+        self.info['long_rows_from'] = int(min_entries)
+
+    def tocsr(self):
+        """(indptr int64 [S + 1], indices int32 [nnz], data [nnz]) of P^T, e.g. for scipy.sparse.csr_matrix"""
+        indptr = np.empty(self.S + 1, dtype=np.int64)
+        indices = np.empty(self.nnz, dtype=np.int32)
+        data = np.empty(self.nnz, dtype=self.dtype)
+        nat.check(nat.lib().sdp_transop_get_csr(self._handle(), nat.ptr(indptr), nat.ptr(indices), nat.ptr(data)))
+        return indptr, indices, data
+
+
 class DPSolver(object):
     # Diagnostic / A-B switches of the generated kernels (codegen.DEBUG_NAMES): None in the product.
     # Tests and tools/ set a dict here (on an instance, or on the class for a block of solvers);
@@ -257,6 +373,10 @@ class DPSolver(object):
     steps_per_launch = 1024
     # .. and the host loop of untraceable models draws and keeps this many steps at a time
     MC_HOST_BLOCK = 64
+    # transition_operator: the most bytes an operator may take on the device (values, sources and row pointers,
+    # forward.operator_bytes; the build needs about three times that for a moment).  A cap, not a tuning knob: beyond
+    # it the call raises before anything is allocated
+    TRANSITION_MAX_BYTES = 2 << 30
     _debug_after_create = None
     STAGED_MIN_NODES = 32768          # 'auto': grids of at most this many nodes run the direct kernel, not the staged tiles (see _kernel_plan_now);
     STAGED_MIN_WORK = 1024            #         up to 4 x as many where a node has this many control x perturbation points or more
@@ -1931,6 +2051,70 @@ class DPSolver(object):
                     np.add.at(occ, tuple(mc.nearest_nodes(xs[i], self.state_grid, np.float64).T), 1)   # (host states are float64)
             x = xs[n]
         return acc, n_out, x.astype(dt), occ
+
+    # ------------------------------------------------------------ state distributions under a policy
+    def _transition_size(self):
+        """(S, nnz, bytes) of the transition operator of the current discretisation"""
+        shape = self._shape()
+        S = int(np.prod(shape))
+        nnz = S * max(self._law_points(), 1) * (1 << len(shape))
+        return S, nnz, forward.operator_bytes(nnz, S, self.dtype.itemsize)
+
+    def transition_operator(self, pol, t_k=None):
+        """The Markov chain on the grid that `eval_policy(pol, ..)` implies, as an operator on state distributions:
+        (P J)(s) = sum_w p_w interp(J)(dyn(x_s, pol[s], w)) is the linear part of one evaluation step, and the
+        `TransitionOperator` returned applies its transpose, mu' = P^T mu, on the device.  NOT in the reference API.
+
+        pol : policy array, shape state_dims + (nb_control,), as for eval_policy
+        t_k : time index of a non-stationary system (as in `control_grids`; default 0, like eval_policy)
+
+        `stodynprog_amd.forward` defines every entry.  The interpolation extrapolates: where the model leaves the
+        grid, weights are negative or above 1 (each source's weights still sum to 1) -- nothing is clamped, so that
+        P^T is the exact adjoint of what eval_policy computes.  An operator stores S W 2^d entries;
+        DPSolver.TRANSITION_MAX_BYTES (2 GiB) caps it, one GPU only."""
+        dims = self._shape()
+        nu = len(self.sys.control)
+        self._check_supported()
+        if self.comm is not None:
+            raise NotImplementedError('transition_operator runs on one GPU (no communicator)')
+        pol = np.asarray(pol)
+        if pol.shape != dims + (nu,):
+            raise ValueError('pol must have shape {}, not {}'.format(dims + (nu,), pol.shape))
+        S, nnz, nbytes = self._transition_size()
+        if nbytes > self.TRANSITION_MAX_BYTES:
+            raise ValueError('the transition operator of this grid has nnz = {} entries and takes {} bytes: more than '
+                             'DPSolver.TRANSITION_MAX_BYTES = {} bytes'.format(nnz, nbytes, self.TRANSITION_MAX_BYTES))
+        if nnz >= 1 << 32:
+            raise ValueError('the transition operator of this grid has nnz = {} entries ({} bytes): entry positions are '
+                             '32-bit words, at most 2**32 - 1 entries whatever the cap'.format(nnz, nbytes))
+        t_trace = None if self.sys.stationnary else (0 if t_k is None else t_k)
+        model = self._trace_now(t_trace)
+        if isinstance(model, TraceError):
+            # callables that cannot be traced: the entries from the definition, on the host
+            e = forward.entries(self, pol, t_trace, time_index='int')
+            op = TransitionOperator.from_coo(dims, e.tgt, e.src, e.val, e.mean_cost.reshape(dims), 'host')
+            self.backend_info = dict(mode='host entries', reason=str(model))
+        else:
+            prob = self._problem(t_trace, model)
+            pol_d = np.ascontiguousarray(pol, dtype=self.dtype)                    # [S][nu]
+            h = C.c_void_p()
+            nat.check(nat.lib().sdp_transop_create(prob.h, nat.ptr(pol_d), float(0 if t_trace is None else t_trace),
+                                                   C.byref(h)))
+            gbar = np.empty(dims, dtype=self.dtype)
+            nat.check(nat.lib().sdp_transop_get_mean_cost(h, nat.ptr(gbar)))
+            op = TransitionOperator(h, dims, self.dtype, nnz, gbar, 'device')
+        # (the operator's record: push times are added to it as the operator is used)
+        self.backend_info = dict(self.backend_info, transition=op.info)
+        return op
+
+    def stationary_distribution(self, pol, t_k=None, **kw):
+        """`transition_operator(pol, t_k).stationary(**kw)` in one call: the stationary distribution of the state
+        under `pol` (a `forward.Stationary` record: mu, n_done, converged, delta, average_cost, mass)."""
+        op = self.transition_operator(pol, t_k)
+        try:
+            return op.stationary(**kw)
+        finally:
+            op.close()
 
     # ------------------------------------------------------------------ reporting
     def print_summary(self):
