@@ -277,6 +277,31 @@ int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int64_t B, int6
                            int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
                            void *host_x_final, uint64_t *host_occupancy);
 
+/*
+ * The same two loops under a TIME-INDEXED policy -- the forward half of a finite-horizon problem, the loop the
+ * reference's examples/01 Deterministic storage control ends with (one interpolator of pol[k] and one sys.dyn(k, ..)
+ * call per step).  Step k of the call (k = 0..T-1) runs at time index t0 + k and looks its controls up in slice k of
+ *     host_pol [n_pol_steps][nu][S]      n_pol_steps == T: the caller hands over the slices of the steps it runs
+ * and, when the code object has lifted constants (a model traced for one concrete time index), evaluates the model
+ * with row k of
+ *     host_prm [T][n_params]             reals; NULL, 0 for a code object without lifted constants
+ * (sdp_problem_set_params is not consulted).  The policy is uploaded in chunks of whole steps of at most chunk_bytes
+ * (a step larger than that is a chunk of its own) and every chunk is run before the next goes up, with the state --
+ * for Monte Carlo also the sums -- in device buffers in between: chunk_bytes and steps_per_launch do not change a bit
+ * of the results.  Everything else as for sdp_problem_simulate and sdp_problem_montecarlo; the Philox counter's step
+ * is k, the step of the call.  One GPU.  SDP_EMODULE for a code object built before these kernels existed.
+ */
+int sdp_problem_simulate_h(sdp_problem *p, int64_t n_pol_steps, const void *host_pol, const void *host_prm,
+                           int32_t n_params, int64_t chunk_bytes, int64_t B, int64_t T,
+                           const void *host_x0, const void *host_w, double t0,
+                           void *host_x, void *host_u, void *host_g);
+int sdp_problem_montecarlo_h(sdp_problem *p, int64_t n_pol_steps, const void *host_pol, const void *host_prm,
+                             int32_t n_params, int64_t chunk_bytes, int64_t B, int64_t T, int64_t n_burn,
+                             uint64_t seed, uint64_t traj_offset, const void *host_x0,
+                             const double *host_cum, int32_t n_law, const void *host_law_grid, double t0,
+                             int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                             void *host_x_final, uint64_t *host_occupancy);
+
 /* ---- transition operator of a policy: the forward half of the model -------------
  * Under a fixed policy the backup of sdp_problem_eval_policy is (P J)(s) + gbar(s), with
  * (P J)(s) = sum_j P[j] interp(J)(dyn(x_s, pol[s], w_j)).  A sdp_transop holds P^T as a CSR matrix on

@@ -203,18 +203,30 @@ def _emit_body(model, nodes, lines, names=None):
     return names
 
 
-def model_function_source(model):
-    """C++ text of sdp_model_cell for a TracedModel: the whole dyn + cost."""
+def model_function_source(model, at=False):
+    """C++ text of sdp_model_cell for a TracedModel: the whole dyn + cost.
+    at: sdp_model_cell_at instead, the same body with the lifted constants read from a row `prm` the caller hands
+    over (csrc/sdp_horizon_kernel.h: a table with one row per time step) instead of the unit's __constant__ array."""
     assert isinstance(model, TracedModel)
     if model.n_perturb > MAX_PERTURB:
         raise NotImplementedError('{} perturbation variables: at most {} are supported'.format(model.n_perturb, MAX_PERTURB))
     # (several perturbation variables, csrc/sdp_multiw_kernel.h: variable w<i> is w[i])
     w_arg = 'const sdp_real *w' if model.n_perturb >= 2 else 'sdp_real w'
-    lines = ['SDP_DEV void sdp_model_cell(const sdp_real *x, const sdp_real *u, {},'.format(w_arg),
-             '                            sdp_real t, sdp_real *xn, sdp_real &g)',
-             '{',
-             '    (void)x; (void)u; (void)w; (void)t;']
-    names = _emit_body(model, model.live_nodes(), lines)
+    if at:
+        lines = ['SDP_DEV void sdp_model_cell_at(const sdp_real *x, const sdp_real *u, {},'.format(w_arg),
+                 '                               sdp_real t, const sdp_real *__restrict__ prm, sdp_real *xn, sdp_real &g)',
+                 '{',
+                 '    (void)x; (void)u; (void)w; (void)t; (void)prm;']
+        body = []
+        names = _emit_body(model, model.live_nodes(), body)
+        lines += [ln.replace('sdp_model_prm[', 'prm[') for ln in body]
+        names = {k: v.replace('sdp_model_prm[', 'prm[') for k, v in names.items()}
+    else:
+        lines = ['SDP_DEV void sdp_model_cell(const sdp_real *x, const sdp_real *u, {},'.format(w_arg),
+                 '                            sdp_real t, sdp_real *xn, sdp_real &g)',
+                 '{',
+                 '    (void)x; (void)u; (void)w; (void)t;']
+        names = _emit_body(model, model.live_nodes(), lines)
     for k, n in enumerate(model.x_next):
         lines.append('    xn[{}] = {};'.format(k, names[n.id]))
     lines.append('    g = {};'.format(names[model.cost.id]))
@@ -472,6 +484,9 @@ def _prologue_lines(model, real, lanes, debug, peer_stores=False):
     if tables:
         lines.append(tables)
     lines += [model_function_source(model), '']
+    if getattr(model, 'param_index', None):
+        # the same model with the constants of a step of the caller's choice (sdp_simulate_h, sdp_montecarlo_h)
+        lines += [model_function_source(model, at=True), '']
     return lines
 
 
@@ -1340,7 +1355,7 @@ HIPCC_FLAGS = ['--genco', '--offload-arch=gfx950', '-O3', '-ffp-contract=off',
 
 _HEADERS = ('sdp_kernel_args.h', 'sdp_device.h', 'sdp_sweep_kernel.h', 'sdp_mc_kernel.h', 'sdp_trans_kernel.h', 'sdp_column_kernel.h', 'sdp_colfilter_kernel.h', 'sdp_colres_kernel.h',
             'sdp_colfull_kernel.h', 'sdp_colu_kernel.h',
-            'sdp_lead_kernel.h', 'sdp_staged_kernel.h')
+            'sdp_lead_kernel.h', 'sdp_staged_kernel.h', 'sdp_horizon_kernel.h')
 _digest_cache = {}
 
 

@@ -939,6 +939,7 @@ struct sdp_problem {
     size_t scratch_bytes = 0;
     hipModule_t mod = nullptr;
     hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr, f_transitions = nullptr;
+    hipFunction_t f_simulate_h = nullptr, f_montecarlo_h = nullptr;      // the loops under a time-indexed policy (sdp_horizon_kernel.h)
     // several controlled state variables (csrc/sdp_lead_kernel.h): the kernel that reduces V over w, launched
     // before every sweep, and its outputs (A[S] and a copy of V, both plane-major; E[nodes per trailing block];
     // bits of max |V|)
@@ -1221,6 +1222,14 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if (hipModuleGetFunction(&p->f_montecarlo, p->mod, "sdp_montecarlo") != hipSuccess) {
         (void)hipGetLastError();
         p->f_montecarlo = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_simulate_h, p->mod, "sdp_simulate_h") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_simulate_h = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_montecarlo_h, p->mod, "sdp_montecarlo_h") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_montecarlo_h = nullptr;
     }
     if (hipModuleGetFunction(&p->f_transitions, p->mod, "sdp_transitions") != hipSuccess) {
         (void)hipGetLastError();
@@ -2291,8 +2300,13 @@ extern "C" int sdp_problem_simulate(sdp_problem *p, const void *host_pol, int64_
     int64_t blocks = (B + 63) / 64;
     if (blocks > (int64_t)p->cus * 32) blocks = (int64_t)p->cus * 32;
     HIP_TRY(hipStreamSynchronize(p->stream));        // lifted constants set on the problem stream
+    HIP_TRY(hipEventRecord(p->ev0, p->stream));
     HIP_TRY(hipModuleLaunchKernel(p->f_simulate, (unsigned)blocks, 1, 1, 64, 1, 1, 0, p->stream, nullptr, extra));
+    HIP_TRY(hipEventRecord(p->ev1, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+    p->last_kernel_ms = ms;
     HIP_TRY(hipMemcpy(host_x, dx.p, (size_t)(T + 1) * p->d * B * rs, hipMemcpyDeviceToHost));
     if (T > 0) HIP_TRY(hipMemcpy(host_u, du.p, (size_t)T * p->nu * B * rs, hipMemcpyDeviceToHost));
     if (host_g && T > 0) HIP_TRY(hipMemcpy(host_g, dg.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
@@ -2374,6 +2388,179 @@ extern "C" int sdp_problem_montecarlo(sdp_problem *p, const void *host_pol, int6
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
     p->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, (size_t)p->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, (size_t)p->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---- the same two loops under a time-indexed policy (kernels sdp_simulate_h / sdp_montecarlo_h of the model's code
+// object, csrc/sdp_horizon_kernel.h): see include/sdp_hip.h.  The policy [n_pol_steps][nu][S] goes up a CHUNK of whole
+// steps at a time (at most chunk_bytes; a step larger than that is a chunk of its own), every chunk is run before
+// the next one is uploaded, and the state -- for Monte Carlo also the sums -- stays in device buffers in between.
+static int horizon_checks(sdp_problem *p, const char *what, int64_t n_pol_steps, int64_t T, const void *host_prm,
+                          int32_t n_params, int64_t chunk_bytes)
+{
+    if (n_pol_steps != T) return fail(SDP_EINVAL, "%s: %lld policy steps for %lld steps", what, (long long)n_pol_steps, (long long)T);
+    if (chunk_bytes < 1) return fail(SDP_EINVAL, "%s: chunk_bytes = %lld: at least 1", what, (long long)chunk_bytes);
+    if (n_params < 0 || (n_params > 0 && !host_prm)) return fail(SDP_EINVAL, "%s: bad parameter table", what);
+    if ((size_t)n_params * real_size(p->dtype) != p->prm_bytes)
+        return fail(SDP_EINVAL, "%s: the code object declares %zu parameter(s) per step, the table has %d", what,
+                    p->prm_bytes / real_size(p->dtype), (int)n_params);
+    return SDP_OK;
+}
+
+// steps of policy that one chunk holds
+static int64_t horizon_chunk_steps(const sdp_problem *p, int64_t T, int64_t chunk_bytes)
+{
+    const size_t step_bytes = (size_t)p->nu * p->S * real_size(p->dtype);
+    int64_t n = (int64_t)((size_t)chunk_bytes / step_bytes);
+    if (n < 1) n = 1;
+    if (n > T) n = T;
+    return n;
+}
+
+extern "C" int sdp_problem_simulate_h(sdp_problem *p, int64_t n_pol_steps, const void *host_pol, const void *host_prm,
+                                      int32_t n_params, int64_t chunk_bytes, int64_t B, int64_t T,
+                                      const void *host_x0, const void *host_w, double t0,
+                                      void *host_x, void *host_u, void *host_g)
+{
+    if (!p || !host_pol || !host_x0 || !host_x || !host_u) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    int rc;
+    if ((rc = horizon_checks(p, "sdp_problem_simulate_h", n_pol_steps, T, host_prm, n_params, chunk_bytes))) return rc;
+    if (p->comm && p->comm->nranks > 1) return fail(SDP_EINVAL, "a time-indexed simulation runs on one GPU");
+    if (!p->f_simulate_h) return fail(SDP_EMODULE, "the model's code object has no sdp_simulate_h kernel (built before the time-indexed loops)");
+    if (p->W > 0 && T > 0 && !host_w) return fail(SDP_EINVAL, "a stochastic system needs the perturbation sequences");
+    if (B == 0) return SDP_OK;
+    const size_t rs = real_size(p->dtype);
+    const size_t step_bytes = (size_t)p->nu * p->S * rs;
+    const int64_t per_chunk = T > 0 ? horizon_chunk_steps(p, T, chunk_bytes) : 0;
+    DevBuf dpol, dprm, dw, dx, du, dg;
+    if (T > 0 && (rc = dpol.alloc((size_t)per_chunk * step_bytes))) return rc;
+    if (n_params > 0 && T > 0 && (rc = upload(dprm, host_prm, (size_t)T * n_params * rs))) return rc;
+    if (host_w && T > 0 && (rc = upload(dw, host_w, (size_t)T * (p->n_perturb > 1 ? p->n_perturb : 1) * B * rs))) return rc;     // [T][n_perturb][B]
+    if ((rc = dx.alloc((size_t)(T + 1) * p->d * B * rs))) return rc;
+    if ((rc = du.alloc((size_t)T * p->nu * B * rs))) return rc;
+    if (host_g && (rc = dg.alloc((size_t)T * B * rs))) return rc;
+    HIP_TRY(hipMemcpy(dx.p, host_x0, (size_t)p->d * B * rs, hipMemcpyHostToDevice));       // row 0 of x
+    SdpSimHArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.prm = (n_params > 0 && T > 0) ? dprm.p : nullptr; a.axes = p->axes.p;
+    a.w = (host_w && T > 0) ? dw.p : nullptr;
+    a.x = dx.p; a.u = du.p; a.g = host_g ? dg.p : nullptr;
+    a.B = B; a.S = p->S; a.t0 = t0;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    int64_t blocks = (B + 63) / 64;
+    if (blocks > (int64_t)p->cus * 32) blocks = (int64_t)p->cus * 32;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    double kernel_ms = 0;
+    for (int64_t k = 0; k < T; k += per_chunk) {
+        const int64_t n = (T - k < per_chunk) ? T - k : per_chunk;
+        // (the kernel of the previous chunk has finished: the stream is synchronised at the end of every round)
+        HIP_TRY(hipMemcpy(dpol.p, (const char *)host_pol + (size_t)k * step_bytes, (size_t)n * step_bytes, hipMemcpyHostToDevice));
+        a.chunk_first = k; a.step_begin = k; a.step_end = k + n;
+        HIP_TRY(hipEventRecord(p->ev0, p->stream));
+        HIP_TRY(hipModuleLaunchKernel(p->f_simulate_h, (unsigned)blocks, 1, 1, 64, 1, 1, 0, p->stream, nullptr, extra));
+        HIP_TRY(hipEventRecord(p->ev1, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        kernel_ms += ms;
+    }
+    p->last_kernel_ms = kernel_ms;
+    HIP_TRY(hipMemcpy(host_x, dx.p, (size_t)(T + 1) * p->d * B * rs, hipMemcpyDeviceToHost));
+    if (T > 0) HIP_TRY(hipMemcpy(host_u, du.p, (size_t)T * p->nu * B * rs, hipMemcpyDeviceToHost));
+    if (host_g && T > 0) HIP_TRY(hipMemcpy(host_g, dg.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_problem_montecarlo_h(sdp_problem *p, int64_t n_pol_steps, const void *host_pol, const void *host_prm,
+                                        int32_t n_params, int64_t chunk_bytes, int64_t B, int64_t T, int64_t n_burn,
+                                        uint64_t seed, uint64_t traj_offset, const void *host_x0,
+                                        const double *host_cum, int32_t n_law, const void *host_law_grid, double t0,
+                                        int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                                        void *host_x_final, uint64_t *host_occupancy)
+{
+    if (!p || !host_pol || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (p->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw: use sdp_problem_simulate_h");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    if (p->comm && p->comm->nranks > 1) return fail(SDP_EINVAL, "Monte Carlo evaluation runs on one GPU");
+    int rc;
+    if ((rc = horizon_checks(p, "sdp_problem_montecarlo_h", n_pol_steps, T, host_prm, n_params, chunk_bytes))) return rc;
+    if (!p->f_montecarlo_h) return fail(SDP_EMODULE, "the model's code object has no sdp_montecarlo_h kernel (built before the time-indexed loops)");
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(p->dtype);
+    const size_t nw = p->n_perturb > 1 ? (size_t)p->n_perturb : 1;
+    if ((size_t)(n_law - 1) * 8 + nw * n_law * rs > 65536)
+        return fail(SDP_EINVAL, "a law of %d points of %d variables needs %zu bytes of LDS: at most 65536", (int)n_law, (int)nw, (size_t)(n_law - 1) * 8 + nw * n_law * rs);
+    const size_t step_bytes = (size_t)p->nu * p->S * rs;
+    const int64_t per_chunk = T > 0 ? horizon_chunk_steps(p, T, chunk_bytes) : 0;
+    DevBuf dpol, dprm, dx, dacc, dout, dcum, dlaw, docc;
+    if (T > 0 && (rc = dpol.alloc((size_t)per_chunk * step_bytes))) return rc;
+    if (n_params > 0 && T > 0 && (rc = upload(dprm, host_prm, (size_t)T * n_params * rs))) return rc;
+    if ((rc = upload(dx, host_x0, (size_t)p->d * B * rs))) return rc;
+    if ((rc = upload(dcum, host_cum, (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, (size_t)nw * n_law * rs))) return rc;      // [n_perturb][n_law]
+    if ((rc = dacc.alloc((size_t)B * rs))) return rc;
+    if ((rc = dout.alloc((size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, (size_t)B * rs, p->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, (size_t)B * 8, p->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc((size_t)p->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, (size_t)p->S * 8, p->stream));
+    }
+    SdpMcHArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.prm = (n_params > 0 && T > 0) ? dprm.p : nullptr; a.axes = p->axes.p;
+    a.cum = (const double *)dcum.p; a.law_grid = dlaw.p;
+    a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.S = p->S; a.seed = seed; a.traj_offset = traj_offset; a.n_burn = n_burn; a.t0 = t0; a.n_law = n_law;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    // (the launch shape of sdp_problem_montecarlo)
+    const int threads = 256;
+    const unsigned lds = (unsigned)((size_t)(n_law - 1) * 8 + nw * n_law * rs);      // cumulative table, then the values
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p->f_montecarlo_h, threads, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 8) per_cu = 8;
+    int64_t blocks = (B + threads - 1) / threads;
+    if (blocks > (int64_t)p->cus * per_cu) blocks = (int64_t)p->cus * per_cu;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    double kernel_ms = 0;
+    for (int64_t c = 0; c < T; c += per_chunk) {
+        const int64_t c_end = (T - c < per_chunk) ? T : c + per_chunk;
+        HIP_TRY(hipMemcpy(dpol.p, (const char *)host_pol + (size_t)c * step_bytes, (size_t)(c_end - c) * step_bytes, hipMemcpyHostToDevice));
+        a.chunk_first = c;
+        HIP_TRY(hipEventRecord(p->ev0, p->stream));
+        for (int64_t k = c; k < c_end; k += steps_per_launch) {
+            a.step_begin = k;
+            a.step_end = (c_end - k < steps_per_launch) ? c_end : k + steps_per_launch;
+            HIP_TRY(hipModuleLaunchKernel(p->f_montecarlo_h, (unsigned)blocks, 1, 1, threads, 1, 1, lds, p->stream, nullptr, extra));
+        }
+        HIP_TRY(hipEventRecord(p->ev1, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        kernel_ms += ms;
+    }
+    p->last_kernel_ms = kernel_ms;
     HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, (size_t)B * rs, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_n_outside, dout.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_x_final, dx.p, (size_t)p->d * B * rs, hipMemcpyDeviceToHost));

@@ -141,6 +141,53 @@ struct SdpMcArgs {
     int32_t axis_off[SDP_MAXD];
 };
 
+// The same two loops under a TIME-INDEXED policy (sdp_horizon_kernel.h: kernels `sdp_simulate_h` and
+// `sdp_montecarlo_h`): step k of the call looks its controls up in slice k of the policy and, in a unit with
+// lifted constants, evaluates the model with row k of a table of them.  A launch runs the steps
+// [step_begin, step_end) of the call with the policy slices of a chunk [chunk_first, ..) on the device.
+struct SdpSimHArgs {
+    const void *pol;       // [steps of this launch's chunk][nu][S]: step k reads slice k - chunk_first
+    const void *prm;       // [steps of the call][SDP_NPARAMS] lifted constants, row k for step k (null: none)
+    const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
+    const void *w;         // [T][B] perturbation sequences of the whole call (null: deterministic); several variables: [T][m][B]
+    void *x;               // [T+1][d][B] states of the whole call: row step_begin read (row 0 = x0, put there by the host), rows step_begin + 1 .. step_end written
+    void *u;               // [T][nu][B] controls applied
+    void *g;               // [T][B] instantaneous costs (may be null)
+    int64_t B;             // trajectories
+    int64_t S;             // state nodes
+    int64_t step_begin;    // first step of this launch (step of the call)
+    int64_t step_end;      // one past its last step
+    int64_t chunk_first;   // step of the call whose policy slice is pol[0]
+    double t0;             // time index of step 0 of the call
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+};
+
+struct SdpMcHArgs {
+    const void *pol;       // [steps of this launch's chunk][nu][S], like SdpSimHArgs
+    const void *prm;       // [steps of the call][SDP_NPARAMS], like SdpSimHArgs (null: none)
+    const void *axes;      // concatenated state-grid axes
+    const double *cum;     // as SdpMcArgs from here on
+    const void *law_grid;
+    void *x;
+    void *acc;
+    long long *n_outside;
+    unsigned long long *occupancy;
+    int64_t B;
+    int64_t S;
+    uint64_t seed;
+    uint64_t traj_offset;
+    int64_t step_begin;
+    int64_t step_end;
+    int64_t n_burn;
+    int64_t chunk_first;   // step of the call whose policy slice is pol[0]
+    double t0;
+    int32_t n_law;
+    int32_t pad_;
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+};
+
 // Entries of the transition operator of a policy (sdp_trans_kernel.h): per node s (flat C-order id), point j of
 // the flat law and vertex v of the interpolation cell of the next state, the target node and the weight at
 // position (s W + j) 2^d + v, and the mean cost of every node.

@@ -88,82 +88,5 @@ SDP_DEV void sdp_mc_visit(unsigned long long *occ, int node, bool count)
 
 extern "C" __global__ void __launch_bounds__(SDP_MC_THREADS) sdp_montecarlo(SdpMcArgs a)
 {
-    extern __shared__ double sdp_mc_lds[];                 // cum[W-1] (doubles), then law_grid[W] (reals)
-    const int W = a.n_law;
-    double *cum = sdp_mc_lds;
-    sdp_real *wgrid = (sdp_real *)(sdp_mc_lds + (W - 1));
-    for (int i = threadIdx.x; i < W - 1; i += blockDim.x) cum[i] = a.cum[i];
-    for (int i = threadIdx.x; i < W; i += blockDim.x) wgrid[i] = ((const sdp_real *)a.law_grid)[i];
-    __syncthreads();
-
-    SdpGrid<sdp_real, SDP_D> grid;
-    sdp_real smin[SDP_D], smax[SDP_D];
-    {
-        const sdp_real *axes = (const sdp_real *)a.axes;
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) {
-            smin[k] = axes[a.axis_off[k]];
-            smax[k] = axes[a.axis_off[k] + a.orders[k] - 1];
-        }
-        sdp_make_grid<sdp_real, SDP_D>(grid, a.orders, smin, smax);
-    }
-    const sdp_real *__restrict__ pol = (const sdp_real *)a.pol;
-    sdp_real *xs = (sdp_real *)a.x;
-    sdp_real *accs = (sdp_real *)a.acc;
-    const unsigned k0 = (unsigned)a.seed, k1 = (unsigned)(a.seed >> 32);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    // the loop bound is the same in every lane of a wave (the ballots and shuffles of the occupancy need them all)
-    const int64_t first = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
-    for (int64_t base = first; base < a.B; base += stride) {
-        const int64_t b = base + (threadIdx.x & 63);
-        const bool live = b < a.B;
-        // An idle lane of the last wave runs along (the ballots and shuffles of the occupancy need every lane) on a copy
-        // of the last row's state and stores nothing.  Whatever it reads is harmless -- its results are dropped, its
-        // gathers are clamped to the grid like everyone's and its visits are not counted -- so nothing here depends on
-        // the order of that read and the live lane's store at the end (xs and accs are not __restrict__ for that reason).
-        const int64_t row = live ? b : a.B - 1;
-        const unsigned long long id = a.traj_offset + (unsigned long long)row;
-        sdp_real x[SDP_D];
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) x[k] = xs[k * a.B + row];
-        sdp_real acc = accs[row];
-        int n_out = 0;                                     // (of this launch: fewer than 2^31 steps)
-        for (int64_t step = a.step_begin; step < a.step_end; ++step) {
-            const bool counted = step >= a.n_burn;
-            SdpCell<sdp_real, SDP_D, double> cell;
-            bool outside = false;
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) {
-                sdp_locate_axis<sdp_real, SDP_D, double>(grid, k, x[k], cell);
-                outside = outside || !(x[k] >= smin[k] && x[k] <= smax[k]);
-            }
-            n_out += (counted && outside) ? 1 : 0;
-            if (a.occupancy) {
-                int node = 0;
-#pragma unroll
-                for (int k = 0; k < SDP_D; ++k) {
-                    const int q = cell.off[k] + ((cell.lam[k] >= (sdp_real)0.5) ? grid.M[k] : 0);     // M[k] * (cell + 1)
-                    node += max(min(q, grid.M[k] * (a.orders[k] - 1)), 0);
-                }
-                sdp_mc_visit(a.occupancy, node, counted && live);
-            }
-            sdp_real u[SDP_NU], xn[SDP_D], g;
-#pragma unroll
-            for (int c = 0; c < SDP_NU; ++c)               // sdp_interp_point<sdp_real, SDP_D, double>, the cell located once
-                u[c] = (sdp_real)SdpLerp<sdp_real, SDP_D, double, 0, false>::eval(pol + c * a.S, grid, cell, 0);
-            const SdpPhilox r = sdp_philox4x32_10((unsigned)id, (unsigned)(id >> 32), (unsigned)step,
-                                                  (unsigned)((unsigned long long)step >> 32), k0, k1);
-            const sdp_real w = wgrid[sdp_mc_index(cum, W - 1, sdp_mc_uniform(r))];
-            sdp_model_cell(x, u, w, (sdp_real)(a.t0 + (double)step), xn, g);
-            if (counted) acc = acc + g;
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) x[k] = xn[k];
-        }
-        if (live) {
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) xs[k * a.B + b] = x[k];
-            accs[b] = acc;
-            a.n_outside[b] += n_out;
-        }
-    }
+    sdp_montecarlo_loop<false>(a);     // (sdp_horizon_kernel.h)
 }

@@ -132,48 +132,7 @@ extern "C" __global__ void __launch_bounds__(256) sdp_evalpol(SdpSweepArgs a)
 // perturbation of step k and trajectory b is the vector w[k][.][b]
 extern "C" __global__ void __launch_bounds__(64) sdp_simulate(SdpSimArgs a)
 {
-    SdpGrid<sdp_real, SDP_D> grid;
-    {
-        const sdp_real *axes = (const sdp_real *)a.axes;
-        sdp_real smin[SDP_D], smax[SDP_D];
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) {
-            smin[k] = axes[a.axis_off[k]];
-            smax[k] = axes[a.axis_off[k] + a.orders[k] - 1];
-        }
-        sdp_make_grid<sdp_real, SDP_D>(grid, a.orders, smin, smax);
-    }
-    const sdp_real *__restrict__ pol = (const sdp_real *)a.pol;
-    const sdp_real *__restrict__ wseq = (const sdp_real *)a.w;
-    sdp_real *__restrict__ xo = (sdp_real *)a.x;
-    sdp_real *__restrict__ uo = (sdp_real *)a.u;
-    sdp_real *__restrict__ go = (sdp_real *)a.g;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += stride) {
-        sdp_real x[SDP_D];
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) {
-            x[k] = ((const sdp_real *)a.x0)[k * a.B + b];
-            xo[k * a.B + b] = x[k];
-        }
-        for (int64_t step = 0; step < a.T; ++step) {
-            sdp_real u[SDP_NU], w[SDP_NW], xn[SDP_D], g;
-#pragma unroll
-            for (int c = 0; c < SDP_NU; ++c)
-                u[c] = sdp_interp_point<sdp_real, SDP_D, double>(pol + c * a.S, grid, x);
-#pragma unroll
-            for (int i = 0; i < SDP_NW; ++i) w[i] = wseq[(step * SDP_NW + i) * a.B + b];
-            sdp_model_cell(x, u, w, (sdp_real)(a.t0 + (double)step), xn, g);
-#pragma unroll
-            for (int c = 0; c < SDP_NU; ++c) uo[(step * SDP_NU + c) * a.B + b] = u[c];
-            if (go) go[step * a.B + b] = g;
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) {
-                x[k] = xn[k];
-                xo[((step + 1) * SDP_D + k) * a.B + b] = xn[k];
-            }
-        }
-    }
+    sdp_simulate_loop<false>(a);       // (sdp_horizon_kernel.h: w[k][.][b] with SDP_NW defined)
 }
 
 // ---- Monte Carlo policy evaluation: sdp_montecarlo of sdp_mc_kernel.h on the flat law ----
@@ -241,84 +200,7 @@ SDP_DEV void sdp_mc_visit(unsigned long long *occ, int node, bool count)
 
 extern "C" __global__ void __launch_bounds__(SDP_MC_THREADS) sdp_montecarlo(SdpMcArgs a)
 {
-    extern __shared__ double sdp_mc_lds[];                 // cum[W-1] (doubles), then law_grid[SDP_NW][W] (reals)
-    const int W = a.n_law;
-    double *cum = sdp_mc_lds;
-    sdp_real *wtab = (sdp_real *)(sdp_mc_lds + (W - 1));
-    for (int i = threadIdx.x; i < W - 1; i += blockDim.x) cum[i] = a.cum[i];
-    for (int i = threadIdx.x; i < SDP_NW * W; i += blockDim.x) wtab[i] = ((const sdp_real *)a.law_grid)[i];
-    __syncthreads();
-
-    SdpGrid<sdp_real, SDP_D> grid;
-    sdp_real smin[SDP_D], smax[SDP_D];
-    {
-        const sdp_real *axes = (const sdp_real *)a.axes;
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) {
-            smin[k] = axes[a.axis_off[k]];
-            smax[k] = axes[a.axis_off[k] + a.orders[k] - 1];
-        }
-        sdp_make_grid<sdp_real, SDP_D>(grid, a.orders, smin, smax);
-    }
-    const sdp_real *__restrict__ pol = (const sdp_real *)a.pol;
-    sdp_real *xs = (sdp_real *)a.x;
-    sdp_real *accs = (sdp_real *)a.acc;
-    const unsigned k0 = (unsigned)a.seed, k1 = (unsigned)(a.seed >> 32);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    // the loop bound is the same in every lane of a wave (the ballots and shuffles of the occupancy need them all)
-    const int64_t first = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
-    for (int64_t base = first; base < a.B; base += stride) {
-        const int64_t b = base + (threadIdx.x & 63);
-        const bool live = b < a.B;
-        // an idle lane of the last wave runs along on a copy of the last row's state and stores nothing
-        // (sdp_mc_kernel.h: its gathers are clamped to the grid, its visits are not counted)
-        const int64_t row = live ? b : a.B - 1;
-        const unsigned long long id = a.traj_offset + (unsigned long long)row;
-        sdp_real x[SDP_D];
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) x[k] = xs[k * a.B + row];
-        sdp_real acc = accs[row];
-        int n_out = 0;                                     // (of this launch: fewer than 2^31 steps)
-        for (int64_t step = a.step_begin; step < a.step_end; ++step) {
-            const bool counted = step >= a.n_burn;
-            SdpCell<sdp_real, SDP_D, double> cell;
-            bool outside = false;
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) {
-                sdp_locate_axis<sdp_real, SDP_D, double>(grid, k, x[k], cell);
-                outside = outside || !(x[k] >= smin[k] && x[k] <= smax[k]);
-            }
-            n_out += (counted && outside) ? 1 : 0;
-            if (a.occupancy) {
-                int node = 0;
-#pragma unroll
-                for (int k = 0; k < SDP_D; ++k) {
-                    const int q = cell.off[k] + ((cell.lam[k] >= (sdp_real)0.5) ? grid.M[k] : 0);     // M[k] * (cell + 1)
-                    node += max(min(q, grid.M[k] * (a.orders[k] - 1)), 0);
-                }
-                sdp_mc_visit(a.occupancy, node, counted && live);
-            }
-            sdp_real u[SDP_NU], w[SDP_NW], xn[SDP_D], g;
-#pragma unroll
-            for (int c = 0; c < SDP_NU; ++c)               // sdp_interp_point<sdp_real, SDP_D, double>, the cell located once
-                u[c] = (sdp_real)SdpLerp<sdp_real, SDP_D, double, 0, false>::eval(pol + c * a.S, grid, cell, 0);
-            const SdpPhilox r = sdp_philox4x32_10((unsigned)id, (unsigned)(id >> 32), (unsigned)step,
-                                                  (unsigned)((unsigned long long)step >> 32), k0, k1);
-            const int j = sdp_mc_index(cum, W - 1, sdp_mc_uniform(r));     // 0 <= j <= W - 1
-#pragma unroll
-            for (int i = 0; i < SDP_NW; ++i) w[i] = wtab[i * W + j];
-            sdp_model_cell(x, u, w, (sdp_real)(a.t0 + (double)step), xn, g);
-            if (counted) acc = acc + g;
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) x[k] = xn[k];
-        }
-        if (live) {
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) xs[k * a.B + b] = x[k];
-            accs[b] = acc;
-            a.n_outside[b] += n_out;
-        }
-    }
+    sdp_montecarlo_loop<false>(a);     // (sdp_horizon_kernel.h: column j of law_grid[SDP_NW][n_law])
 }
 
 // what this code object was generated for (sdp_kernel_args.h, SDP_META_*); word 15: perturbation variables

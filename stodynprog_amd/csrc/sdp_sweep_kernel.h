@@ -128,9 +128,15 @@ SDP_DEV void sdp_grid_from_args(const SdpSweepArgs &a, SdpGrid<sdp_real, SDP_D> 
     sdp_make_grid<sdp_real, SDP_D>(g, a.orders, smin, smax);
 }
 
+// the per-trajectory loops of the closed-loop kernels (`sdp_simulate`, `sdp_montecarlo` and their time-indexed twins):
+// defined once in sdp_horizon_kernel.h, which is included after the entry points and the draw helpers it uses
+template <bool H, typename Args> SDP_DEV void sdp_simulate_loop(const Args &a);
+template <bool H, typename Args> SDP_DEV void sdp_montecarlo_loop(const Args &a);
+
 #if defined(SDP_NW) && SDP_NW >= 2
 #include "sdp_multiw_kernel.h"  // the kernels below and sdp_meta for several perturbation variables (w a vector)
 #include "sdp_trans_kernel.h"   // sdp_transitions on the flat law
+#include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy
 #else
 // expected cost of one (node, control): sum_w p_w * (g + J_next(f))
 template <bool SHIFT = false>
@@ -248,53 +254,14 @@ extern "C" __global__ void __launch_bounds__(256) sdp_evalpol(SdpSweepArgs a)
 // (examples/20 Searev storage control/storage_control.py:242-251).
 extern "C" __global__ void __launch_bounds__(64) sdp_simulate(SdpSimArgs a)
 {
-    SdpGrid<sdp_real, SDP_D> grid;
-    {
-        const sdp_real *axes = (const sdp_real *)a.axes;
-        sdp_real smin[SDP_D], smax[SDP_D];
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) {
-            smin[k] = axes[a.axis_off[k]];
-            smax[k] = axes[a.axis_off[k] + a.orders[k] - 1];
-        }
-        sdp_make_grid<sdp_real, SDP_D>(grid, a.orders, smin, smax);
-    }
-    const sdp_real *__restrict__ pol = (const sdp_real *)a.pol;
-    const sdp_real *__restrict__ wseq = (const sdp_real *)a.w;
-    sdp_real *__restrict__ xo = (sdp_real *)a.x;
-    sdp_real *__restrict__ uo = (sdp_real *)a.u;
-    sdp_real *__restrict__ go = (sdp_real *)a.g;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += stride) {
-        sdp_real x[SDP_D];
-#pragma unroll
-        for (int k = 0; k < SDP_D; ++k) {
-            x[k] = ((const sdp_real *)a.x0)[k * a.B + b];
-            xo[k * a.B + b] = x[k];
-        }
-        for (int64_t step = 0; step < a.T; ++step) {
-            sdp_real u[SDP_NU], xn[SDP_D], g;
-#pragma unroll
-            for (int c = 0; c < SDP_NU; ++c)
-                u[c] = sdp_interp_point<sdp_real, SDP_D, double>(pol + c * a.S, grid, x);
-            const sdp_real w = wseq ? wseq[step * a.B + b] : (sdp_real)0;
-            sdp_model_cell(x, u, w, (sdp_real)(a.t0 + (double)step), xn, g);
-#pragma unroll
-            for (int c = 0; c < SDP_NU; ++c) uo[(step * SDP_NU + c) * a.B + b] = u[c];
-            if (go) go[step * a.B + b] = g;
-#pragma unroll
-            for (int k = 0; k < SDP_D; ++k) {
-                x[k] = xn[k];
-                xo[((step + 1) * SDP_D + k) * a.B + b] = xn[k];
-            }
-        }
-    }
+    sdp_simulate_loop<false>(a);       // (sdp_horizon_kernel.h)
 }
 
 #if SDP_HAS_W
 #include "sdp_mc_kernel.h"      // sdp_montecarlo: the same loop with the perturbation drawn on the device, reduced per trajectory
 #endif
 #include "sdp_trans_kernel.h"   // sdp_transitions: the entries of the policy's transition operator (deterministic units too)
+#include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy (every unit)
 
 // what this code object was generated for (sdp_kernel_args.h, SDP_META_*); units that include
 // sdp_column_kernel.h define it at the end of that file, where the column macros are complete

@@ -373,6 +373,10 @@ class DPSolver(object):
     steps_per_launch = 1024
     # .. and the host loop of untraceable models draws and keeps this many steps at a time
     MC_HOST_BLOCK = 64
+    # simulate / monte_carlo under a time-indexed policy: the policy goes to the device in chunks of whole steps of at
+    # most this many bytes (a step larger than that is a chunk of its own; the state stays on the device between the
+    # chunks, so the cut changes no bit)
+    horizon_chunk_bytes = 256 << 20
     # transition_operator: the most bytes an operator may take on the device (values, sources and row pointers,
     # forward.operator_bytes; the build needs about three times that for a moment).  A cap, not a tuning knob: beyond
     # it the call raises before anything is allocated
@@ -1814,7 +1818,10 @@ class DPSolver(object):
         dynamics).  NOT in the reference API.
 
         pol : policy array on the state grid, shape state_dims + (nb_control,)
-              (as returned by value_iteration / policy_iteration)
+              (as returned by value_iteration / policy_iteration), or a TIME-INDEXED policy of shape
+              (T_pol,) + state_dims + (nb_control,) (as returned by bellman_recursion with t_ini = 0): step k
+              of the call runs at time index t0 + k with the controls of pol[t0 + k] (kernel
+              sdp_simulate_h; also on a stationary system: a receding schedule)
         x0  : start state(s), shape (nb_state,) or (B, nb_state)
         w   : perturbation sequence(s), shape (T,) or (T, B); None for a deterministic
               system (then give n_steps); m >= 2 perturbation variables: (T, m) or (T, m, B)
@@ -1825,8 +1832,7 @@ class DPSolver(object):
         model is `bit_exact` (backend_info)."""
         dims = self._state_grid_shape
         d, nu = len(dims), len(self.sys.control)
-        pol = np.asarray(pol)
-        assert pol.shape == dims + (nu,)
+        pol, timed = self._check_policy_shape(pol)
         x0 = np.asarray(x0, dtype=float)
         single = x0.ndim == 1
         x0 = np.atleast_2d(x0)
@@ -1847,10 +1853,29 @@ class DPSolver(object):
         else:
             assert n_steps is not None, 'give n_steps for a deterministic system'
             T = int(n_steps)
+        self._check_horizon(pol, timed, T, t0)
         t_trace = None if self.sys.stationnary else t0
         model = self._trace_now(t_trace)
-        if isinstance(model, TraceError) or (model.t_value is not None):
+        table = self._horizon_table(model, timed, T, t0)
+        if table is not None:
+            # a time-indexed policy, or a model traced step by step (`data[k]`): one device call with the policy slice
+            # and the constants of every step
+            prob = self._problem(t_trace, model)
+            self.backend_info['horizon_path'] = 'device'
+            dt = self.dtype
+            pol_d = self._horizon_policy(pol, timed, T, t0)                          # [T][nu][S]
+            x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
+            w_d = np.ascontiguousarray(w[:T], dtype=dt) if n_w else None            # [T][B]; several variables: [T][m][B]
+            x = np.empty((T + 1, d, B), dtype=dt)
+            u = np.empty((T, nu, B), dtype=dt)
+            g = np.empty((T, B), dtype=dt)
+            nat.check(nat.lib().sdp_problem_simulate_h(prob.h, T, nat.ptr(pol_d), nat.ptr(table), table.shape[1],
+                                                       int(self.horizon_chunk_bytes), B, T, nat.ptr(x0_d), nat.ptr(w_d),
+                                                       float(t0), nat.ptr(x), nat.ptr(u), nat.ptr(g)))
+            x, u = np.moveaxis(x, 1, 2), np.moveaxis(u, 1, 2)
+        elif isinstance(model, TraceError) or (model.t_value is not None):
             x, u, g = self._simulate_host(pol, x0, w, T, t0)
+            self.backend_info = dict(getattr(self, 'backend_info', None) or {}, horizon_path='host')
         else:
             prob = self._problem(t_trace, model)
             dt = self.dtype
@@ -1868,18 +1893,91 @@ class DPSolver(object):
             return x[:, 0], u[:, 0], g[:, 0]
         return np.ascontiguousarray(x), np.ascontiguousarray(u), g
 
+    def _check_policy_shape(self, pol):
+        """(pol as an array, whether it has a leading time axis); a ValueError names the two shapes accepted"""
+        dims = self._state_grid_shape
+        nu = len(self.sys.control)
+        pol = np.asarray(pol)
+        if pol.shape == dims + (nu,):
+            return pol, False
+        if pol.ndim == len(dims) + 2 and pol.shape[1:] == dims + (nu,):
+            return pol, True
+        raise ValueError('pol must have shape {} (a stationary policy) or (T_pol,) + {} (a time-indexed one), not {}'.format(
+            dims + (nu,), dims + (nu,), pol.shape))
+
+    def _check_horizon(self, pol, timed, n_steps, t0):
+        """the steps t0 .. t0 + n_steps - 1 of a time-indexed policy exist; such a run takes one GPU"""
+        if not timed:
+            return
+        if int(t0) != t0:
+            raise ValueError('t0 = {} must be an integer to index a time-indexed policy'.format(t0))
+        if t0 < 0 or t0 + n_steps > pol.shape[0]:
+            raise ValueError('t0 = {} and n_steps = {} need the policy steps {} .. {}: the policy has T_pol = {}'.format(
+                t0, n_steps, t0, t0 + n_steps - 1, pol.shape[0]))
+        if self.comm is not None and self.comm.nranks > 1:
+            raise NotImplementedError('a time-indexed policy runs on one GPU')
+
+    def _horizon_models(self, n_steps, t0):
+        """the traces of the steps t0 .. t0 + n_steps - 1 of a system whose callables need a concrete time index
+        (trace_model(.., t_value=t)), or None when a step does not trace"""
+        s = self.sys
+        out = []
+        for t in range(int(t0), int(t0) + int(n_steps)):
+            try:
+                out.append(trace_model(s.dyn, s.cost, len(s.state), len(s.control), len(s.perturb), s.params,
+                                       s.stationnary, t_value=t))
+            except TraceError:
+                return None
+        return out
+
+    def _horizon_table(self, model, timed, n_steps, t0):
+        """The lifted constants of every step of a device run over a horizon, as an array (n_steps, n_params) in the
+        problem's reals (rounded once, as set_params does), or None when the run is not one for the horizon kernels:
+        a stationary policy on a model with a symbolic trace (kernels sdp_simulate / sdp_montecarlo), or a model that the host loop runs --
+        no trace, a step that does not trace, or steps whose traces differ in structure (structure_key: the
+        operators, the interpolation tables, the number of constants)."""
+        if isinstance(model, TraceError):
+            return None
+        if model.t_value is None:
+            if not timed:
+                return None
+            row = model.param_values() if model.param_index is not None else []
+            return np.ascontiguousarray(np.tile(np.asarray(row, dtype=float), (n_steps, 1)), dtype=self.dtype).reshape(n_steps, len(row))
+        if n_steps < 1 or int(t0) != t0 or (self.comm is not None and self.comm.nranks > 1):
+            return None
+        steps = self._horizon_models(n_steps, t0)
+        if steps is None:
+            return None
+        key = model.structure_key()
+        if any(m.structure_key() != key for m in steps):
+            return None
+        rows = [m.param_values() for m in steps]
+        return np.ascontiguousarray(np.asarray(rows, dtype=float).reshape(n_steps, len(model.param_index)), dtype=self.dtype)
+
+    def _horizon_policy(self, pol, timed, n_steps, t0):
+        """the policy slices of the steps t0 .. t0 + n_steps - 1 as [n_steps][nu][S] in the problem's reals"""
+        if timed:
+            part = np.moveaxis(pol[int(t0):int(t0) + n_steps], -1, 1)
+        else:
+            part = np.broadcast_to(np.moveaxis(pol, -1, 0), (n_steps,) + pol.shape[-1:] + pol.shape[:-1])
+        return np.ascontiguousarray(part, dtype=self.dtype)
+
     def _simulate_host(self, pol, x0, w, T, t0):
         """the reference's loop as written (callables on the host, one interpolator call
         per step, batched over the trajectories): models that cannot be traced"""
         d, nu = len(self._state_grid_shape), len(self.sys.control)
         B = x0.shape[0]
-        laws = [self.interp_on_state(np.ascontiguousarray(pol[..., c])) for c in range(nu)]
+        timed = pol.ndim == d + 2          # a time-indexed policy: per step the interpolators of pol[t0 + k]
+        if not timed:
+            laws = [self.interp_on_state(np.ascontiguousarray(pol[..., c])) for c in range(nu)]
         x = np.zeros((T + 1, B, d))
         u = np.zeros((T, B, nu))
         g = np.zeros((T, B))
         x[0] = x0
         for k in range(T):
             xs = tuple(x[k, :, i] for i in range(d))
+            if timed:
+                laws = [self.interp_on_state(np.ascontiguousarray(pol[t0 + k][..., c])) for c in range(nu)]
             for c in range(nu):
                 u[k, :, c] = laws[c](*xs)
             args = xs + tuple(u[k, :, c] for c in range(nu)) + (
@@ -1952,7 +2050,8 @@ class DPSolver(object):
         reference's examples (examples/20 Searev storage control/storage_control.py:197-265)
         without T x B reals up and (T+1) d B + T nu B + T B reals down.  NOT in the reference API.
 
-        pol      : policy array, shape state_dims + (nb_control,)
+        pol      : policy array, shape state_dims + (nb_control,), or a time-indexed policy of shape
+                   (T_pol,) + state_dims + (nb_control,): step k takes the controls of pol[t0 + k], as in `simulate`
         x0       : start state (nb_state,) -- then give n_traj -- or one per trajectory (B, nb_state)
         n_steps  : steps per trajectory
         seed     : the run is a function of (seed, trajectory id, step) alone (Philox4x32-10, see
@@ -1974,9 +2073,7 @@ class DPSolver(object):
         grid, proba = self._mc_law(law)
         if self.comm is not None and self.comm.nranks > 1:
             raise NotImplementedError('monte_carlo runs on one GPU')
-        pol = np.asarray(pol)
-        if pol.shape != dims + (nu,):
-            raise ValueError('pol must have shape {}, not {}'.format(dims + (nu,), pol.shape))
+        pol, timed = self._check_policy_shape(pol)
         x0 = np.asarray(x0, dtype=float)
         if x0.ndim == 1:
             if x0.shape != (d,):
@@ -1998,12 +2095,34 @@ class DPSolver(object):
         if spl < 1:
             raise ValueError('steps_per_launch must be at least 1')
         dt = self.dtype
+        self._check_horizon(pol, timed, n_steps, t0)
         t_trace = None if self.sys.stationnary else t0
         model = self._trace_now(t_trace)
-        if isinstance(model, TraceError) or (model.t_value is not None):
+        table = self._horizon_table(model, timed, n_steps, t0)
+        if table is not None:
+            prob = self._problem(t_trace, model)
+            self.backend_info['horizon_path'] = 'device'
+            pol_d = self._horizon_policy(pol, timed, n_steps, t0)                   # [T][nu][S]
+            x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
+            cum = np.ascontiguousarray(mc.cumulative(proba))
+            law_d = np.ascontiguousarray(grid, dtype=dt)                            # [n]; several variables: [m][n]
+            cost_sum = np.empty(B, dtype=dt)
+            n_out = np.empty(B, dtype=np.int64)
+            x_final = np.empty((d, B), dtype=dt)
+            occ = np.empty(int(np.prod(dims)), dtype=np.uint64) if occupancy else None
+            nat.check(nat.lib().sdp_problem_montecarlo_h(
+                prob.h, n_steps, nat.ptr(pol_d), nat.ptr(table), table.shape[1], int(self.horizon_chunk_bytes), B,
+                n_steps, n_burn, seed, int(traj_offset), nat.ptr(x0_d), nat.ptr(cum), len(proba), nat.ptr(law_d),
+                float(t0), spl, nat.ptr(cost_sum), nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
+            x_final = np.ascontiguousarray(x_final.T)
+            if occ is not None:
+                occ = occ.astype(np.int64).reshape(dims)
+            path = 'device'
+        elif isinstance(model, TraceError) or (model.t_value is not None):
             cost_sum, n_out, x_final, occ = self._monte_carlo_host(pol, x0, n_steps, n_burn, seed, ids, grid, proba,
                                                                    occupancy, t0)
             path = 'host'
+            self.backend_info = dict(getattr(self, 'backend_info', None) or {}, horizon_path='host')
         else:
             prob = self._problem(t_trace, model)
             pol_d = np.ascontiguousarray(np.moveaxis(pol, -1, 0), dtype=dt)        # [nu][S]

@@ -1,0 +1,272 @@
+"""DPSolver.simulate and monte_carlo under a time-indexed policy (kernels sdp_simulate_h and sdp_montecarlo_h,
+csrc/sdp_horizon_kernel.h) against the pinned oracle chained step by step (tests/horizon_sim.simulate_indexed): states,
+controls, costs and the Monte Carlo reductions bit for bit, in every unit of tests/horizon_sim.py, at every cut of the
+run into chunks and launches."""
+import contextlib
+import io
+
+import numpy as np
+import pytest
+
+import horizon_cases as hc
+import horizon_sim as hs
+import multi_perturb as mp
+import policies as P
+from conftest import golden
+from test_gpu_montecarlo import _reduce, _same as _same_mc
+from test_gpu_simulate_forms import _same, _starts
+from stodynprog_amd import models, perturb, _native as nat
+
+pytestmark = pytest.mark.gpu
+
+KINDS = ('smooth', 'outside', 'special')
+
+
+def _quiet(f, *a, **kw):
+    with contextlib.redirect_stdout(io.StringIO()), np.errstate(all='ignore'):
+        return f(*a, **kw)
+
+
+def _close(s):
+    for k in [k for k in s._cache if k[0] == 'problem']:
+        s._cache.pop(k).close()
+
+
+def _noise(s, T, B, rng):
+    """perturbations of T steps for B trajectories: (what simulate takes, what the oracle takes).  One variable: (T, B)
+    values, every 7th trajectory with five times the spread.  Several: indices j into the flat law for the oracle's
+    adapter, and the columns wtab[:, j] as (T, m, B) for the device."""
+    if len(s.sys.perturb) >= 2:
+        wtab, _ = perturb.product_law(s.perturb_grid, s.perturb_proba)
+        j = rng.integers(0, wtab.shape[1], (T, B))
+        return np.ascontiguousarray(np.moveaxis(wtab[:, j], 0, 1)), j.astype(float)
+    w = s.perturb_grid[0]
+    out = rng.normal(0.0, (w[-1] - w[0]) / 6.0, (T, B))
+    out[:, ::7] *= 5.0
+    return out, out
+
+
+def _starts_of(T):
+    """(t0, n_steps): the whole horizon, and a later start that runs to its end"""
+    late = 3 if T > 4 else 1
+    return ((0, T), (late, T - late))
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('unit', sorted(hs.SIMULATE))
+def test_simulate_in_every_unit(gpu, unit):
+    make, int_time, T = hs.SIMULATE[unit]
+    s = make()
+    spec = hs.spec_of(s, int_time)
+    rng = np.random.default_rng(len(unit))
+    try:
+        for kind in KINDS:
+            pol = hs.policies(s, kind, T)
+            for B in (1, 63, 64, 65, 257):
+                for t0, n in _starts_of(T):
+                    x0 = _starts(s, B, rng)
+                    w_dev, w_ref = _noise(s, n, B, rng)
+                    got = _quiet(s.simulate, pol, x0, w_dev, n_steps=n, t0=t0)
+                    assert s.backend_info['horizon_path'] == 'device', s.backend_info
+                    assert s.backend_info['time_specialized'] == int_time, s.backend_info
+                    ref = hs.simulate_indexed(spec, pol, x0, w_ref, n, t0, s.dtype)
+                    _same(got, ref, '{} {} B={} t0={}'.format(unit, kind, B, t0))
+    finally:
+        _close(s)
+
+
+def _hand_loop(sto_sys, solver, pol, E0, T):
+    """the forward pass of examples/pv_storage.py as it was written by hand"""
+    E = np.zeros(T + 1)
+    E[0] = E0
+    P_sto, cost = np.zeros(T), np.zeros(T)
+    for k in range(T):
+        P_sto[k] = solver.interp_on_state(pol[k, :, 0])(E[k])
+        E[k + 1], = sto_sys.dyn(k, E[k], P_sto[k])
+        cost[k] = float(sto_sys.cost(k, E[k], P_sto[k]))
+    return E, P_sto, cost
+
+
+@pytest.mark.timeout(300)
+def test_pv_storage_with_the_reference_policy(gpu):
+    """the committed policy of the real reference (48 steps, 50 nodes): one device call equals the oracle chained and the
+    example's hand loop"""
+    g = golden('g9_pv_storage')
+    sto_sys, s = models.pv_storage()
+    pol = np.asarray(g['pol'])
+    assert pol.shape == (48, 50, 1)
+    try:
+        x0 = np.array([[1.0], [0.0], [2.0], [0.37], [2.5]])
+        got = _quiet(s.simulate, pol, x0, n_steps=48)
+        info = dict(s.backend_info)
+        assert info['horizon_path'] == 'device' and info['time_specialized'] and info['lifted_constants'] > 0, info
+        ref = hs.simulate_indexed(hs.spec_of(s, True), pol, x0, None, 48, 0, np.float64)
+        _same(got, ref, 'pv_storage')
+        # a later start, one trajectory
+        x, u, c = _quiet(s.simulate, pol, [1.0], n_steps=20, t0=28)
+        ref = hs.simulate_indexed(hs.spec_of(s, True), pol, [[1.0]], None, 20, 28, np.float64)
+        _same((x[:, None], u[:, None], c[:, None]), ref, 'pv_storage t0=28')
+        with np.errstate(all='ignore'):
+            E, P_sto, cost = _hand_loop(sto_sys, s, pol, 1.0, 48)
+        assert np.array_equal(got[0][:, 0, 0], E) and np.array_equal(got[1][:, 0, 0], P_sto)
+        assert np.array_equal(got[2][:, 0], cost)
+    finally:
+        _close(s)
+
+
+def _mc_reference(s, spec, pol, x0, T, seed, n_burn, t0=0, traj_offset=0):
+    idx, w = s.monte_carlo_draws(seed, x0.shape[0], T, traj_offset=traj_offset)
+    w_ref = idx.astype(float) if len(s.sys.perturb) >= 2 else w
+    x, _, g = hs.simulate_indexed(spec, pol, x0, w_ref, T, t0, s.dtype)
+    return _reduce(s, x, g, n_burn, True)
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('unit', sorted(hs.MONTE_CARLO))
+def test_monte_carlo_against_the_replayed_draws(gpu, unit):
+    make, int_time, T = hs.MONTE_CARLO[unit]
+    s = make()
+    spec = hs.spec_of(s, int_time)
+    rng = np.random.default_rng(5)
+    B = 257
+    try:
+        for kind in ('smooth', 'outside'):
+            pol = hs.policies(s, kind, T)
+            x0 = _starts(s, B, rng)
+            for n_burn in (0, 3):
+                res = _quiet(s.monte_carlo, pol, x0, T, seed=11, n_burn=n_burn, occupancy=True)
+                assert res.path == 'device' and s.backend_info['horizon_path'] == 'device'
+                ref = _mc_reference(s, spec, pol, x0, T, 11, n_burn)
+                _same_mc(res, ref, '{} {} n_burn={}'.format(unit, kind, n_burn), n_counted=B * (T - n_burn))
+            # a batch split in two with traj_offset equals the whole (n_burn = 3, the last run)
+            cut = 100
+            a = _quiet(s.monte_carlo, pol, x0[:cut], T, seed=11, n_burn=3, occupancy=True)
+            b = _quiet(s.monte_carlo, pol, x0[cut:], T, seed=11, n_burn=3, occupancy=True, traj_offset=cut)
+            assert np.array_equal(np.concatenate([a.cost_sum, b.cost_sum]), res.cost_sum, equal_nan=True)
+            assert np.array_equal(np.concatenate([a.x_final, b.x_final]), res.x_final, equal_nan=True)
+            assert np.array_equal(np.concatenate([a.n_outside, b.n_outside]), res.n_outside)
+            assert np.array_equal(a.occupancy + b.occupancy, res.occupancy)
+        # a later start: steps 0 .. of the call draw with the call's step, look up pol[t0 + k]
+        t0, n = _starts_of(T)[1]
+        res = _quiet(s.monte_carlo, pol, x0, n, seed=4, occupancy=True, t0=t0)
+        _same_mc(res, _mc_reference(s, spec, pol, x0, n, 4, 0, t0=t0), '{} t0={}'.format(unit, t0))
+    finally:
+        _close(s)
+
+
+@pytest.mark.timeout(300)
+def test_cuts_into_chunks_and_launches_change_no_bit(gpu):
+    s = hc.storage()
+    T, B = hc.T, 257
+    rng = np.random.default_rng(8)
+    pol = hs.policies(s, 'outside', T)
+    x0 = _starts(s, B, rng)
+    w, _ = _noise(s, T, B, rng)
+    step_bytes = int(np.prod(s._state_grid_shape)) * len(s.sys.control) * s.dtype.itemsize
+    try:
+        whole = _quiet(s.simulate, pol, x0, w)
+        whole_mc = _quiet(s.monte_carlo, pol, x0, T, seed=3, n_burn=2, occupancy=True)
+        for chunk in (step_bytes, 3 * step_bytes + 5, T * step_bytes, 1):
+            s.horizon_chunk_bytes = chunk
+            _same(_quiet(s.simulate, pol, x0, w), whole, 'chunk of {} bytes'.format(chunk))
+            for spl in (1, 2, 1024):
+                s.steps_per_launch = spl
+                res = _quiet(s.monte_carlo, pol, x0, T, seed=3, n_burn=2, occupancy=True)
+                what = 'chunk of {} bytes, {} steps per launch'.format(chunk, spl)
+                assert np.array_equal(res.cost_sum, whole_mc.cost_sum, equal_nan=True), what
+                assert np.array_equal(res.x_final, whole_mc.x_final, equal_nan=True), what
+                assert np.array_equal(res.n_outside, whole_mc.n_outside), what
+                assert np.array_equal(res.occupancy, whole_mc.occupancy), what
+    finally:
+        _close(s)
+
+
+@pytest.mark.timeout(600)
+def test_simulate_past_the_launch_cap(gpu):
+    """more trajectories than the launch's blocks x 64 lanes: the grid-stride loop reaches every one of them (the twin
+    of tests/test_gpu_simulate_forms.test_simulate_past_the_launch_cap)"""
+    cus = int(nat.device_info(0)['compute_units'])
+    B = cus * 32 * 64 + 129
+    s = hc.storage()
+    rng = np.random.default_rng(9)
+    pol = hs.policies(s, 'smooth', 2)
+    x0 = _starts(s, B, rng)
+    w, _ = _noise(s, 2, B, rng)
+    try:
+        got = _quiet(s.simulate, pol, x0, w)
+        assert s.backend_info['horizon_path'] == 'device'
+        _same(got, hs.simulate_indexed(hs.spec_of(s), pol, x0, w, 2, 0, s.dtype), 'B = {}'.format(B))
+    finally:
+        _close(s)
+
+
+@pytest.mark.timeout(300)
+def test_stationary_policy_on_a_time_specialised_model_runs_on_the_device(gpu):
+    from oracle import vi_numpy
+    s = hc.storage(data=True)
+    rng = np.random.default_rng(10)
+    pol = P.policy(s, 'smooth', seed=1)
+    try:
+        for t0, n in ((0, hc.T), (3, 5)):
+            x0 = _starts(s, 65, rng)
+            w, _ = _noise(s, n, 65, rng)
+            got = _quiet(s.simulate, pol, x0, w, t0=t0)
+            assert s.backend_info['horizon_path'] == 'device' and s.backend_info['time_specialized']
+            with np.errstate(all='ignore'):
+                ref = vi_numpy.simulate(hs.spec_of(s, True), pol, x0, w, n, t0=t0, dtype=s.dtype)
+            _same(got, ref, 'stationary policy t0={}'.format(t0))
+        res = _quiet(s.monte_carlo, pol, x0, 5, seed=2, t0=3)
+        assert res.path == 'device'
+        _, wd = s.monte_carlo_draws(2, 65, 5)
+        with np.errstate(all='ignore'):
+            x, _, g = vi_numpy.simulate(hs.spec_of(s, True), pol, x0, wd, 5, t0=3, dtype=s.dtype)
+        acc, n_out, x_final, _ = _reduce(s, x, g, 0, False)
+        assert np.array_equal(res.cost_sum, acc) and np.array_equal(res.x_final, x_final)
+        assert np.array_equal(res.n_outside, n_out)
+    finally:
+        _close(s)
+
+
+@pytest.mark.timeout(300)
+def test_a_structure_change_mid_horizon_takes_the_host_loop(gpu):
+    s = hs.switching()
+    rng = np.random.default_rng(11)
+    pol = hs.policies(s, 'smooth', hc.T)
+    x0 = _starts(s, 65, rng)
+    w, _ = _noise(s, hc.T, 65, rng)
+    try:
+        got = _quiet(s.simulate, pol, x0, w)
+        assert s.backend_info['horizon_path'] == 'host', s.backend_info
+        _same(got, hs.simulate_indexed(hs.spec_of(s, True), pol, x0, w, hc.T, 0, np.float64), 'structure change')
+        res = _quiet(s.monte_carlo, pol, x0, hc.T, seed=1)
+        assert res.path == 'host' and s.backend_info['horizon_path'] == 'host'
+        # steps that do share a structure run on the device: 1 .. 3 (data <= 0)
+        got = _quiet(s.simulate, pol, x0, w[:3], t0=1)
+        assert s.backend_info['horizon_path'] == 'device', s.backend_info
+        _same(got, hs.simulate_indexed(hs.spec_of(s, True), pol, x0, w, 3, 1, np.float64), 'steps 1 .. 3')
+    finally:
+        _close(s)
+
+
+@pytest.mark.timeout(300)
+def test_equal_slices_give_the_stationary_call(gpu):
+    rng = np.random.default_rng(12)
+    for make in (hc.storage, lambda: models.storage_ar1()[1]):
+        s = make()
+        pol = P.policy(s, 'outside', seed=2)
+        timed = np.broadcast_to(pol, (hc.T,) + pol.shape)
+        x0 = _starts(s, 65, rng)
+        w, _ = _noise(s, hc.T, 65, rng)
+        try:
+            ref = _quiet(s.simulate, pol, x0, w)
+            assert 'horizon_path' not in s.backend_info                 # today's kernel
+            got = _quiet(s.simulate, timed, x0, w)
+            assert s.backend_info['horizon_path'] == 'device'
+            _same(got, ref, 'equal slices')
+            a = _quiet(s.monte_carlo, pol, x0, hc.T, seed=6, occupancy=True)
+            b = _quiet(s.monte_carlo, timed, x0, hc.T, seed=6, occupancy=True)
+            assert np.array_equal(a.cost_sum, b.cost_sum, equal_nan=True)
+            assert np.array_equal(a.x_final, b.x_final, equal_nan=True)
+            assert np.array_equal(a.n_outside, b.n_outside) and np.array_equal(a.occupancy, b.occupancy)
+        finally:
+            _close(s)
