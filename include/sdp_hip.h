@@ -302,6 +302,34 @@ int sdp_problem_montecarlo_h(sdp_problem *p, int64_t n_pol_steps, const void *ho
                              int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
                              void *host_x_final, uint64_t *host_occupancy);
 
+/*
+ * One-step lookahead at arbitrary states -- the reference's _value_at_state_vect (stodynprog.py:639-691) for a batch,
+ * and the closed loop that applies it.  The handle must be that of a LOOKAHEAD unit (a node-order code object
+ * generated with SDP_LOOKAHEAD: kernel sdp_lookahead; with SDP_LOOKAHEAD_BOX also its own box function and kernel
+ * sdp_simulate_lookahead); SDP_EMODULE otherwise.  One GPU.  The definition is stodynprog_amd/lookahead.py.
+ *
+ * sdp_problem_lookahead: at every state b of host_x [d][B], with the cost-to-go host_V [S] (C order),
+ *     host_J [B], host_u [nu][B], host_idx [B]   min / argmin over the state's control lattice of
+ *                                                 E_w[g(x, u, w) + J_next(f(x, u, w))], control values, flat index
+ * The lattice of state b is host_lo, host_hi [nu][B] (reals; the centre twice where n == 1) and host_n [nu][B]
+ * (host_n[0][b] == 0: no valid lattice, the results are NaN, NaN, -1) -- or, with host_n NULL, made on the device by
+ * the unit's box function from steps [nu], the control step hints (float64), with the same bits.
+ *
+ * sdp_problem_simulate_lookahead: B closed-loop trajectories of T steps; step k runs at time index t0 + k, looks
+ * ahead into slice k of host_V [n_V_steps][S] (n_V_steps == T), or into the one host_V [S] (n_V_steps == 0), and then
+ * takes the model's own step at the optimal control.  host_x [T+1][d][B], host_u [T][nu][B], host_g [T][B] as
+ * sdp_problem_simulate; host_q [T][B] the minimised expected values.  A time-indexed cost-to-go is uploaded in chunks
+ * of whole steps of at most chunk_bytes, the state stays on the device in between: no cut changes a bit.  Needs a
+ * unit with its own box function and without lifted constants.
+ */
+int sdp_problem_lookahead(sdp_problem *p, const void *host_V, int64_t B, const void *host_x,
+                          const void *host_lo, const void *host_hi, const int32_t *host_n,
+                          const double *steps, double t_k, void *host_J, void *host_u, int32_t *host_idx);
+int sdp_problem_simulate_lookahead(sdp_problem *p, int64_t n_V_steps, const void *host_V, int64_t chunk_bytes,
+                                   int64_t B, int64_t T, const void *host_x0, const void *host_w,
+                                   const double *steps, double t0,
+                                   void *host_x, void *host_u, void *host_g, void *host_q);
+
 /* ---- transition operator of a policy: the forward half of the model -------------
  * Under a fixed policy the backup of sdp_problem_eval_policy is (P J)(s) + gbar(s), with
  * (P J)(s) = sum_j P[j] interp(J)(dyn(x_s, pol[s], w_j)).  A sdp_transop holds P^T as a CSR matrix on

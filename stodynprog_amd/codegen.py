@@ -724,7 +724,39 @@ def line_functions_source(model):
     return '\n\n'.join(out)
 
 
-def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False):
+def box_function_source(box):
+    """C++ text of `sdp_model_box(const double *x, double t, double *lo, double *hi)` for a TracedBox: the ends of the
+    admissible box of every control at a state, in DOUBLE whatever the unit's reals (csrc/sdp_lookahead_kernel.h
+    widens a 4-byte state first, as the host's scalar calls do).  The body is `_emit_body`'s and the np.interp tables
+    are `interp_tables_source`'s, printed once more under names of their own with `double` for `sdp_real`: every
+    helper the emitter names is a template or has a double overload (csrc/sdp_device.h), so no box that traces is
+    left without its function."""
+    lines = ['SDP_DEV void sdp_model_box(const sdp_real *x, sdp_real t, sdp_real *lo, sdp_real *hi)',
+             '{',
+             '    (void)x; (void)t;']
+    names = _emit_body(box, box.live_nodes(), lines)
+    for c, (lo, hi) in enumerate(box.ends):
+        lines.append('    lo[{}] = {};'.format(c, names[lo.id]))
+        lines.append('    hi[{}] = {};'.format(c, names[hi.id]))
+    lines.append('}')
+    text = interp_tables_source(box) + '\n'.join(lines)
+    for old, new in (('sdp_np_interp', 'sdp_box_np_interp'), ('sdp_interp1_', 'sdp_box_interp1_'),
+                     ('sdp_tabx_', 'sdp_box_tabx_'), ('sdp_tabf_', 'sdp_box_tabf_'), ('sdp_real', 'double')):
+        text = text.replace(old, new)
+    return text
+
+
+def lookahead_unit(model, dtype, lanes, box=None, debug=None):
+    """The generated source of a LOOKAHEAD unit (csrc/sdp_lookahead_kernel.h): a direct-family unit -- node order,
+    `lanes` lanes per state, several perturbation variables through csrc/sdp_multiw_kernel.h -- that also carries
+    kernel `sdp_lookahead`, and, when `box` is the TracedBox of control_box (symbolic in the state and the time
+    index), the box function and kernel `sdp_simulate_lookahead`."""
+    if box is not None and (box.t_value is not None or box.inexact_ops()):
+        raise ValueError('the box function of a lookahead unit is a trace with a symbolic time index and exact operations')
+    return translation_unit(model, dtype, lanes, None, debug=debug, lookahead=box if box is not None else True)
+
+
+def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False, lookahead=None):
     """The generated source of one model code object.  `family`: what the unit is to hold beside the direct node-order
     kernels of csrc/sdp_sweep_kernel.h --
     None: nothing else;
@@ -736,8 +768,11 @@ def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=F
     an int W: the line kernel of csrc/sdp_line_kernel.h on W perturbation points.
     debug: None (the product), or a dict of diagnostic switches (see DEBUG_NAMES).
     peer_stores: the unit's backup kernels also store J into the buffers of other ranks (the direct exchange,
-    SdpSweepArgs.peer_J); without it they hold no code for that, and the library refuses the direct exchange."""
+    SdpSweepArgs.peer_J); without it they hold no code for that, and the library refuses the direct exchange.
+    lookahead: None, or what `lookahead_unit` hands over (True, or the TracedBox of the unit's box function)."""
     debug = check_debug(debug)
+    if lookahead is not None and family is not None:
+        raise ValueError('a lookahead unit is a direct-family unit')
     real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
     if model.n_perturb >= 2 and (family is not None or peer_stores):
         raise ValueError('the column, lead, line and staged families and the direct exchange take one perturbation variable')
@@ -784,6 +819,12 @@ def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=F
             head.append('#define SDP_LEAD_UNROLL {}'.format(int(_dbg(debug, 'SDP_LEAD_UNROLL'))))
         head += [lead_functions_source(model, int(lead_axes), lead_perm), '',
                  '#include "sdp_sweep_kernel.h"    // brings in sdp_lead_kernel.h', '']
+    elif lookahead is not None:
+        head.append('#define SDP_LOOKAHEAD 1        // the unit also carries sdp_lookahead (csrc/sdp_lookahead_kernel.h)')
+        if lookahead is not True:
+            head += [box_function_source(lookahead),
+                     '#define SDP_LOOKAHEAD_BOX 1    // .. its own box function, and sdp_simulate_lookahead']
+        head += ['#include "sdp_sweep_kernel.h"    // brings in sdp_lookahead_kernel.h', '']
     else:
         head += ['#include "sdp_sweep_kernel.h"', '']
     return '\n'.join(head)
@@ -1408,6 +1449,9 @@ def source_key(source):
             h.update(f.read())
     if '#define SDP_NW ' in source:
         with open(os.path.join(CSRC, 'sdp_multiw_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_LOOKAHEAD ' in source:
+        with open(os.path.join(CSRC, 'sdp_lookahead_kernel.h'), 'rb') as f:
             h.update(f.read())
     h.update(source.encode())
     h.update(' '.join(HIPCC_FLAGS[:-1]).encode())

@@ -940,6 +940,7 @@ struct sdp_problem {
     hipModule_t mod = nullptr;
     hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr, f_transitions = nullptr;
     hipFunction_t f_simulate_h = nullptr, f_montecarlo_h = nullptr;      // the loops under a time-indexed policy (sdp_horizon_kernel.h)
+    hipFunction_t f_lookahead = nullptr, f_simulate_lookahead = nullptr; // lookahead units only (sdp_lookahead_kernel.h); the second: units with their own box function
     // several controlled state variables (csrc/sdp_lead_kernel.h): the kernel that reduces V over w, launched
     // before every sweep, and its outputs (A[S] and a copy of V, both plane-major; E[nodes per trailing block];
     // bits of max |V|)
@@ -1230,6 +1231,14 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if (hipModuleGetFunction(&p->f_montecarlo_h, p->mod, "sdp_montecarlo_h") != hipSuccess) {
         (void)hipGetLastError();
         p->f_montecarlo_h = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_lookahead, p->mod, "sdp_lookahead") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_lookahead = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_simulate_lookahead, p->mod, "sdp_simulate_lookahead") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_simulate_lookahead = nullptr;
     }
     if (hipModuleGetFunction(&p->f_transitions, p->mod, "sdp_transitions") != hipSuccess) {
         (void)hipGetLastError();
@@ -2476,6 +2485,144 @@ extern "C" int sdp_problem_simulate_h(sdp_problem *p, int64_t n_pol_steps, const
     HIP_TRY(hipMemcpy(host_x, dx.p, (size_t)(T + 1) * p->d * B * rs, hipMemcpyDeviceToHost));
     if (T > 0) HIP_TRY(hipMemcpy(host_u, du.p, (size_t)T * p->nu * B * rs, hipMemcpyDeviceToHost));
     if (host_g && T > 0) HIP_TRY(hipMemcpy(host_g, dg.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One-step lookahead at arbitrary states (kernels sdp_lookahead / sdp_simulate_lookahead of a lookahead unit,
+// csrc/sdp_lookahead_kernel.h): see include/sdp_hip.h.
+// ---------------------------------------------------------------------------
+static int lookahead_checks(sdp_problem *p, const char *what, bool device_box, const double *steps)
+{
+    if (p->comm && p->comm->nranks > 1) return fail(SDP_EINVAL, "%s runs on one GPU", what);
+    if (p->layout != SDP_LAYOUT_NODES) return fail(SDP_EINVAL, "%s: a lookahead unit is in node order", what);
+    if (!p->f_lookahead) return fail(SDP_EMODULE, "%s: the model's code object is not a lookahead unit (no sdp_lookahead kernel)", what);
+    if (device_box) {
+        if (!p->f_simulate_lookahead) return fail(SDP_EMODULE, "%s: the code object has no box function of its own (built without SDP_LOOKAHEAD_BOX)", what);
+        if (!steps) return fail(SDP_EINVAL, "%s: a lattice made on the device needs the control step hints", what);
+        for (int c = 0; c < p->nu; ++c)
+            if (!(steps[c] == steps[c])) return fail(SDP_EINVAL, "%s: control step hint %d is NaN", what, c);
+    }
+    return SDP_OK;
+}
+
+extern "C" int sdp_problem_lookahead(sdp_problem *p, const void *host_V, int64_t B, const void *host_x,
+                                     const void *host_lo, const void *host_hi, const int32_t *host_n,
+                                     const double *steps, double t_k, void *host_J, void *host_u, int32_t *host_idx)
+{
+    if (!p || !host_V || !host_x || !host_J || !host_u || !host_idx) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0) return fail(SDP_EINVAL, "negative size");
+    if (host_n && (!host_lo || !host_hi)) return fail(SDP_EINVAL, "sdp_problem_lookahead: box arrays without their ends");
+    int rc;
+    if ((rc = lookahead_checks(p, "sdp_problem_lookahead", host_n == nullptr, steps))) return rc;
+    if (B == 0) return SDP_OK;
+    const size_t rs = real_size(p->dtype);
+    DevBuf dV, dx, dlo, dhi, dn, dJ, du, didx;
+    if ((rc = upload(dV, host_V, (size_t)p->S * rs))) return rc;
+    if ((rc = upload(dx, host_x, (size_t)p->d * B * rs))) return rc;
+    if (host_n) {
+        if ((rc = upload(dlo, host_lo, (size_t)p->nu * B * rs))) return rc;
+        if ((rc = upload(dhi, host_hi, (size_t)p->nu * B * rs))) return rc;
+        if ((rc = upload(dn, host_n, (size_t)p->nu * B * sizeof(int32_t)))) return rc;
+    }
+    if ((rc = dJ.alloc((size_t)B * rs))) return rc;
+    if ((rc = du.alloc((size_t)p->nu * B * rs))) return rc;
+    if ((rc = didx.alloc((size_t)B * sizeof(int32_t)))) return rc;
+    SdpLookArgs a;
+    memset(&a, 0, sizeof(a));
+    a.V = dV.p; a.axes = p->axes.p; a.wgrid = p->wgrid.p; a.proba = p->proba.p; a.x = dx.p;
+    a.box_lo = host_n ? dlo.p : nullptr; a.box_hi = host_n ? dhi.p : nullptr; a.box_n = host_n ? (const int32_t *)dn.p : nullptr;
+    a.J = dJ.p; a.idx = (int32_t *)didx.p; a.u = du.p;
+    a.B = B; a.S = p->S; a.t_k = t_k; a.W = p->W;
+    for (int c = 0; c < p->nu && steps; ++c) a.steps[c] = steps[c];
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    const unsigned blocks = sweep_blocks(p, B);          // (a multiple of 8: the kernel walks the tiles XCD by XCD)
+    HIP_TRY(hipStreamSynchronize(p->stream));            // lifted constants set on the problem stream
+    HIP_TRY(hipEventRecord(p->ev0, p->stream));
+    HIP_TRY(hipModuleLaunchKernel(p->f_lookahead, blocks, 1, 1, 256, 1, 1, 0, p->stream, nullptr, extra));
+    HIP_TRY(hipEventRecord(p->ev1, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+    p->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_J, dJ.p, (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_u, du.p, (size_t)p->nu * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_idx, didx.p, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_problem_simulate_lookahead(sdp_problem *p, int64_t n_V_steps, const void *host_V, int64_t chunk_bytes,
+                                              int64_t B, int64_t T, const void *host_x0, const void *host_w,
+                                              const double *steps, double t0,
+                                              void *host_x, void *host_u, void *host_g, void *host_q)
+{
+    if (!p || !host_V || !host_x0 || !host_x || !host_u || !host_g || !host_q) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_V_steps != 0 && n_V_steps != T)
+        return fail(SDP_EINVAL, "sdp_problem_simulate_lookahead: %lld cost-to-go steps for %lld steps (0: one for every step)", (long long)n_V_steps, (long long)T);
+    if (chunk_bytes < 1) return fail(SDP_EINVAL, "sdp_problem_simulate_lookahead: chunk_bytes = %lld: at least 1", (long long)chunk_bytes);
+    int rc;
+    if ((rc = lookahead_checks(p, "sdp_problem_simulate_lookahead", true, steps))) return rc;
+    if (p->prm_bytes) return fail(SDP_EINVAL, "sdp_problem_simulate_lookahead: a unit with lifted constants takes the host path");
+    if (p->W > 0 && T > 0 && !host_w) return fail(SDP_EINVAL, "a stochastic system needs the perturbation sequences");
+    if (B == 0) return SDP_OK;
+    const size_t rs = real_size(p->dtype);
+    const size_t step_bytes = (size_t)p->S * rs;
+    const bool timed = n_V_steps != 0;
+    int64_t per_chunk = T;
+    if (timed && T > 0) {
+        per_chunk = (int64_t)((size_t)chunk_bytes / step_bytes);
+        if (per_chunk < 1) per_chunk = 1;
+        if (per_chunk > T) per_chunk = T;
+    }
+    DevBuf dV, dw, dx, du, dg, dq;
+    if ((rc = dV.alloc((timed ? (size_t)per_chunk : 1) * step_bytes))) return rc;
+    if (!timed) HIP_TRY(hipMemcpy(dV.p, host_V, step_bytes, hipMemcpyHostToDevice));
+    if (host_w && T > 0 && (rc = upload(dw, host_w, (size_t)T * (p->n_perturb > 1 ? p->n_perturb : 1) * B * rs))) return rc;     // [T][n_perturb][B]
+    if ((rc = dx.alloc((size_t)(T + 1) * p->d * B * rs))) return rc;
+    if ((rc = du.alloc((size_t)T * p->nu * B * rs))) return rc;
+    if ((rc = dg.alloc((size_t)T * B * rs))) return rc;
+    if ((rc = dq.alloc((size_t)T * B * rs))) return rc;
+    HIP_TRY(hipMemcpy(dx.p, host_x0, (size_t)p->d * B * rs, hipMemcpyHostToDevice));       // row 0 of x
+    SdpLookSimArgs a;
+    memset(&a, 0, sizeof(a));
+    a.V = dV.p; a.axes = p->axes.p; a.wgrid = p->wgrid.p; a.proba = p->proba.p;
+    a.w = (host_w && T > 0) ? dw.p : nullptr;
+    a.x = dx.p; a.u = du.p; a.g = dg.p; a.q = dq.p;
+    a.B = B; a.S = p->S; a.V_stride = timed ? p->S : 0; a.t0 = t0; a.W = p->W;
+    for (int c = 0; c < p->nu; ++c) a.steps[c] = steps[c];
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    const int64_t per_block = (int64_t)(64 / p->lanes) * 4;          // trajectories of a workgroup of 256
+    int64_t blocks = (B + per_block - 1) / per_block;
+    if (blocks > (int64_t)p->cus * 8) blocks = (int64_t)p->cus * 8;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    double kernel_ms = 0;
+    for (int64_t k = 0; k < T; k += per_chunk) {
+        const int64_t n = (T - k < per_chunk) ? T - k : per_chunk;
+        // (the kernel of the previous chunk has finished: the stream is synchronised at the end of every round)
+        if (timed) HIP_TRY(hipMemcpy(dV.p, (const char *)host_V + (size_t)k * step_bytes, (size_t)n * step_bytes, hipMemcpyHostToDevice));
+        a.chunk_first = timed ? k : 0; a.step_begin = k; a.step_end = k + n;
+        HIP_TRY(hipEventRecord(p->ev0, p->stream));
+        HIP_TRY(hipModuleLaunchKernel(p->f_simulate_lookahead, (unsigned)blocks, 1, 1, 256, 1, 1, 0, p->stream, nullptr, extra));
+        HIP_TRY(hipEventRecord(p->ev1, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        kernel_ms += ms;
+    }
+    p->last_kernel_ms = kernel_ms;
+    HIP_TRY(hipMemcpy(host_x, dx.p, (size_t)(T + 1) * p->d * B * rs, hipMemcpyDeviceToHost));
+    if (T > 0) {
+        HIP_TRY(hipMemcpy(host_u, du.p, (size_t)T * p->nu * B * rs, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(host_g, dg.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(host_q, dq.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    }
     return SDP_OK;
 }
 

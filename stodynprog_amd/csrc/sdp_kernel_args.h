@@ -207,6 +207,58 @@ struct SdpTransArgs {
     int32_t axis_off[SDP_MAXD];
 };
 
+// One-step lookahead at arbitrary states (sdp_lookahead_kernel.h, kernel `sdp_lookahead` of a lookahead unit): the
+// backup of SdpSweepArgs with the node replaced by state b of a batch, its control lattice made by the host.
+struct SdpLookArgs {
+    const void *V;         // [S] cost-to-go J_next, C order
+    const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
+    const void *wgrid;     // [W] perturbation grid (null when W == 0); several variables: [m][W]
+    const void *proba;     // [W] perturbation weights
+    const void *x;         // [d][B] states
+    const void *box_lo;    // [nu][B] control lattice of every state: lower ends (the centre where n == 1)
+    const void *box_hi;    // [nu][B] upper ends
+    const int32_t *box_n;  // [nu][B] points; n[0][b] == 0: state b has no valid lattice (J and u NaN, idx -1).  Null: the unit's
+                           //   own box function (SDP_LOOKAHEAD_BOX) and `steps` make the lattice on the device
+    void *J;               // [B] minimised expected value
+    int32_t *idx;          // [B] flat C-order index of the optimal control in the state's lattice
+    void *u;               // [nu][B] optimal control VALUES
+    int64_t B;             // states
+    int64_t S;             // state nodes
+    double t_k;            // time index for non-stationary systems
+    double steps[SDP_MAXU];// control step hints (DPSolver.control_steps): read with a device-made lattice only
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+    int32_t W;             // perturbation points (0: deterministic system)
+    int32_t pad_;
+};
+
+// The closed loop under lookahead controls (kernel `sdp_simulate_lookahead`, units with SDP_LOOKAHEAD_BOX): per
+// step the backup at the carried state, then the model's own step at the optimal control.  A launch runs the steps
+// [step_begin, step_end) of the call with the cost-to-go slices of a chunk [chunk_first, ..) on the device.
+struct SdpLookSimArgs {
+    const void *V;         // [S] one cost-to-go for every step (V_stride == 0), or [steps of the chunk][S]: step k reads slice k - chunk_first
+    const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
+    const void *wgrid;     // the law the backup sums over, as SdpLookArgs
+    const void *proba;
+    const void *w;         // [T][B] perturbation sequences of the whole call (null: deterministic); several variables: [T][m][B]
+    void *x;               // [T+1][d][B] states of the whole call: row step_begin read, rows step_begin + 1 .. step_end written
+    void *u;               // [T][nu][B] controls applied
+    void *g;               // [T][B] instantaneous costs
+    void *q;               // [T][B] minimised expected values
+    int64_t B;             // trajectories
+    int64_t S;             // state nodes
+    int64_t V_stride;      // 0, or S (a time-indexed cost-to-go)
+    int64_t step_begin;    // first step of this launch (step of the call)
+    int64_t step_end;      // one past its last step
+    int64_t chunk_first;   // step of the call whose cost-to-go slice is V[0]
+    double t0;             // time index of step 0 of the call
+    double steps[SDP_MAXU];// control step hints
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+    int32_t W;
+    int32_t pad_;
+};
+
 // Stand-alone multilinear interpolation (multilinear_cython.pyx:17-49).
 struct SdpInterpArgs {
     const void *values;    // [n_v][S]

@@ -137,6 +137,9 @@ template <bool H, typename Args> SDP_DEV void sdp_montecarlo_loop(const Args &a)
 #include "sdp_multiw_kernel.h"  // the kernels below and sdp_meta for several perturbation variables (w a vector)
 #include "sdp_trans_kernel.h"   // sdp_transitions on the flat law
 #include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy
+#if defined(SDP_LOOKAHEAD)
+#include "sdp_lookahead_kernel.h" // sdp_lookahead: the backup at arbitrary states of a batch (lookahead units only)
+#endif
 #else
 // expected cost of one (node, control): sum_w p_w * (g + J_next(f))
 template <bool SHIFT = false>
@@ -262,6 +265,9 @@ extern "C" __global__ void __launch_bounds__(64) sdp_simulate(SdpSimArgs a)
 #endif
 #include "sdp_trans_kernel.h"   // sdp_transitions: the entries of the policy's transition operator (deterministic units too)
 #include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy (every unit)
+#if defined(SDP_LOOKAHEAD)
+#include "sdp_lookahead_kernel.h" // sdp_lookahead: the backup at arbitrary states of a batch (lookahead units only)
+#endif
 
 // what this code object was generated for (sdp_kernel_args.h, SDP_META_*); units that include
 // sdp_column_kernel.h define it at the end of that file, where the column macros are complete

@@ -1619,6 +1619,285 @@ class DPSolver(object):
         J, u = self._value_at_state_vect(x_k, J_next_interp)
         return (J, tuple(u))
 
+    # ------------------------------------------------------------ one-step lookahead at arbitrary states
+    def _lookahead_refusals(self, path):
+        """what lookahead and simulate_lookahead refuse before anything is traced or allocated"""
+        if self.comm is not None and self.comm.nranks > 1:
+            raise NotImplementedError('lookahead at arbitrary states runs on one GPU')
+        if path not in (None, 'device', 'host'):
+            raise ValueError("path must be None, 'device' or 'host', not {!r}".format(path))
+        self._check_supported()
+
+    def _lookahead_unit(self, t_k):
+        """(device problem of the lookahead unit or None, traced box or TraceError, traced model or TraceError) for
+        the time index t_k (None: a stationary system).  The unit is a direct-family unit whatever `self.kernel`
+        says (codegen.lookahead_unit), with `lanes_for` the largest lattice of the grid's nodes; it carries its own
+        box function when control_box traces with a symbolic time index.  A model that does not trace has no unit."""
+        box_t = None if self.sys.stationnary else t_k
+        model = self._trace_now(t_k)
+        tb = self._trace_box_now(box_t)
+        if isinstance(model, TraceError):
+            return None, tb, model
+        bp = self._box_plan(box_t)
+        box = tb if (not isinstance(tb, TraceError) and tb.t_value is None) else None
+        debug = codegen.check_debug(self.debug_defines)
+        source = codegen.lookahead_unit(model, self.dtype, bp['lanes'], box, debug=debug)
+        key = ('lookahead', self._fingerprint(None), bp['lanes'], source)
+        prob = self._cache.get(key)
+        if prob is None:
+            nat.require_gpu()
+            for k in [k for k in self._cache if k[0] == 'lookahead']:
+                self._cache.pop(k).close()
+            shape, dt, nu = self._shape(), self.dtype, len(self.sys.control)
+            W = self._law_points()
+            arrays = dict(axes=[np.ascontiguousarray(g, dtype=dt) for g in self.state_grid],
+                          # (the sweep kernels of the unit are not launched: a one-point box stands in for theirs)
+                          box_lo=np.zeros((nu, 1), dtype=dt), box_hi=np.zeros((nu, 1), dtype=dt),
+                          box_n=np.ones((nu, 1), dtype=np.int32))
+            if W and model.n_perturb >= 2:
+                arrays['wgrid'], arrays['proba'] = perturb.product_law(self.perturb_grid, self.perturb_proba, dt)
+            elif W:
+                arrays['wgrid'] = np.ascontiguousarray(self.perturb_grid[0], dtype=dt)
+                arrays['proba'] = np.ascontiguousarray(self.perturb_proba[0], dtype=dt)
+            module = nat.compile_model(source)
+            prob = _DeviceProblem(arrays, module, dt, shape, nu, W, bp['lanes'], False, (0, int(np.prod(shape))),
+                                  n_perturb=model.n_perturb if model.n_perturb >= 2 else 0)
+            prob.look_box = box is not None
+            prob.info = dict(module=module, lanes=bp['lanes'])
+            self._cache[key] = prob
+        if model.param_index is not None:
+            prob.set_params(model.param_values())
+        return prob, tb, model
+
+    def _lookahead_boxes(self, tb, x, t_k):
+        """host-made lattices (lo, hi, n) of shape (nu, B) at the states x (B, d), already in the problem's reals:
+        the traced box evaluated on the batch, or scalar calls where control_box does not trace"""
+        from . import lookahead as la
+        xd = np.asarray(x, dtype=float)
+        box_t = None if self.sys.stationnary else t_k
+        if isinstance(tb, TraceError):
+            return la.lattice(self.sys.control_box, self.sys.params, self.control_steps, xd, box_t, self.dtype)
+        B, nu = xd.shape[0], len(self.sys.control)
+        ends = tb.evaluate([xd[:, i] for i in range(xd.shape[1])], box_t)
+        lo = np.empty((nu, B))
+        hi = np.empty((nu, B))
+        for c, (a, b) in enumerate(ends):
+            lo[c], hi[c] = a, b
+        return la.lattice_of_ends(lo, hi, self.control_steps, self.dtype)
+
+    def _lookahead_step(self, J_k, x, t_k, path):
+        """one lookahead of a batch: J_k on the grid, x (B, d) in the problem's reals.  Returns (J_opt, u_opt (B, nu),
+        idx) and leaves in backend_info how it was done."""
+        dt = self.dtype
+        B, d = x.shape
+        nu = len(self.sys.control)
+        prob, tb, model = self._lookahead_unit(t_k)
+        if prob is None:
+            out = self._lookahead_tabulated(J_k, x, t_k, tb)
+            self.backend_info = dict(mode='tabulated', reason=str(model), lookahead_path='host', lookahead_box='host')
+            return out
+        device_box = path != 'host' and prob.look_box
+        V = np.ascontiguousarray(J_k, dtype=dt)
+        x_d = np.ascontiguousarray(x.T, dtype=dt)                               # [d][B]
+        lo = hi = n = None
+        steps = np.ascontiguousarray(self.control_steps, dtype=float)
+        if not device_box:
+            lo, hi, n = (np.ascontiguousarray(a) for a in self._lookahead_boxes(tb, x, t_k))
+        J = np.empty(B, dtype=dt)
+        u = np.empty((nu, B), dtype=dt)
+        idx = np.empty(B, dtype=np.int32)
+        nat.check(nat.lib().sdp_problem_lookahead(prob.h, nat.ptr(V), B, nat.ptr(x_d), nat.ptr(lo), nat.ptr(hi), nat.ptr(n),
+                                                  nat.ptr(steps), 0.0 if t_k is None else float(t_k),
+                                                  nat.ptr(J), nat.ptr(u), nat.ptr(idx)))
+        self.backend_info = dict(prob.info, mode='traced', kernel='lookahead', lookahead_path='host' if path == 'host' else 'device',
+                                 lookahead_box='device' if device_box else 'host',
+                                 time_specialized=model.t_value is not None, lifted_constants=len(model.param_index or ()))
+        self._lookahead_prob = prob
+        return J, np.ascontiguousarray(u.T), idx
+
+    def _lookahead_tabulated(self, J_k, x, t_k, tb):
+        """a model that does not trace: the callables on the host for the whole batch, ONE sdp_tab_backup call with
+        all states' cells (what `_value_at_state_vect` does for one state; in float64, like the tabulated sweep)"""
+        from . import lookahead as la
+        nat.require_gpu()
+        B, d = x.shape
+        nu = len(self.sys.control)
+        w_args, proba, W = self._flat_law()
+        xd = np.asarray(x, dtype=float)
+        lo, hi, n = self._lookahead_boxes(tb, x, t_k)
+        lo, hi = lo.astype(float), hi.astype(float)
+        lead = () if (t_k is None or self.sys.stationnary) else (t_k,)
+        J = np.full(B, np.nan)
+        u = np.full((B, nu), np.nan)
+        idx = np.full(B, -1, dtype=np.int32)
+        live = [b for b in range(B) if n[0, b] > 0]
+        if not live:
+            return J.astype(self.dtype), u.astype(self.dtype), idx
+        grids, cells_x, cells_g = [], [], []
+        off = np.zeros(len(live) + 1, dtype=np.int64)
+        for i, b in enumerate(live):
+            dims = tuple(int(v) for v in n[:, b])
+            ug = [la.control_points(lo[c, b], hi[c, b], n[c, b]) for c in range(nu)]
+            mesh = [g.reshape((1,) * c + (-1,) + (1,) * (nu - c)) for c, g in enumerate(ug)]
+            args = lead + tuple(xd[b]) + tuple(mesh) + tuple(w_args)
+            lattice = dims + ((W,) if W else ())
+            x_next = self.sys.dyn(*args, **self.sys.params)
+            g_grid = self.sys.cost(*args, **self.sys.params)
+            cells_x.append(np.vstack([np.broadcast_to(np.asarray(v, dtype=float), lattice).ravel() for v in x_next]))
+            cells_g.append(np.broadcast_to(np.asarray(g_grid, dtype=float), lattice).ravel())
+            grids.append((ug, dims))
+            off[i + 1] = off[i] + cells_g[-1].size
+        xn = np.ascontiguousarray(np.concatenate(cells_x, axis=1))
+        gg = np.ascontiguousarray(np.concatenate(cells_g))
+        shape = self._shape()
+        smin = np.array([g[0] for g in self.state_grid], dtype=float)
+        smax = np.array([g[-1] for g in self.state_grid], dtype=float)
+        orders = np.array(shape, dtype=np.int64)
+        V = np.ascontiguousarray(J_k, dtype=float)
+        h = C.c_void_p()
+        nat.check(nat.lib().sdp_tab_create(len(shape), nat.ptr(smin), nat.ptr(smax), nat.ptr(orders), nat.ptr(V), C.byref(h)))
+        try:
+            Jb = np.zeros(len(live))
+            ib = np.zeros(len(live), dtype=np.int64)
+            nat.check(nat.lib().sdp_tab_backup(h, len(live), nat.ptr(off), W, nat.ptr(proba), nat.ptr(xn), nat.ptr(gg),
+                                               nat.ptr(Jb), nat.ptr(ib)))
+        finally:
+            nat.lib().sdp_tab_destroy(h)
+        for i, b in enumerate(live):
+            ug, dims = grids[i]
+            ind = np.unravel_index(int(ib[i]), dims)
+            J[b], idx[b] = Jb[i], ib[i]
+            u[b] = [ug[c][ind[c]] for c in range(nu)]
+        return J.astype(self.dtype), u.astype(self.dtype), idx
+
+    def _lookahead_time(self, t_k):
+        if self.sys.stationnary:
+            return None
+        if t_k is None:
+            raise ValueError('a time-dependent system needs the time index t_k')
+        return t_k
+
+    def lookahead(self, J_next, x, t_k=None, path=None):
+        """Optimal cost and control at ARBITRARY states, for a batch: at every state of `x`
+
+            (J_opt, u_opt, idx) = min / argmin over u of  E_w[ cost(x, u, w) + J_next(dyn(x, u, w)) ]
+
+        over the control lattice of the state -- the reference's `_value_at_state_vect(x_k, J_next_interp)`
+        (stodynprog.py:639-691), the body of its sweep, at states that need not be grid nodes, in ONE device call
+        for the batch (kernel sdp_lookahead).  NOT in the reference API.  The definition, operator for operator, is
+        `stodynprog_amd/lookahead.py`: the box is control_box at the state in float64, the lattice control_grids'
+        rule, the expectation the sweep's sequential sum, first-occurrence argmin; J_next extrapolates outside the
+        grid, nothing is clamped.  At a grid node the result is value_iteration's J, policy and
+        last_policy_index of that node.
+
+        J_next : cost-to-go on the state grid
+        x      : state(s), shape (nb_state,) or (B, nb_state); a 4-byte solver rounds them once
+        t_k    : time index (non-stationary systems)
+        path   : None / 'device': the lattice is made on the device where control_box traces (else by the host);
+                 'host': the lattice always comes from the host's evaluation of control_box (the same bits)
+
+        Returns (J_opt (B,), u_opt (B, nb_control), idx (B,) int32).  A state whose box has a non-finite end, or
+        whose lattice would have 2^31 points or more, gives NaN, NaN, -1 (the reference raises there).
+        backend_info['lookahead_path'] tells 'device' or 'host', ['lookahead_box'] where the lattice was made; a
+        model that does not trace takes the host path (callables on the host, one sdp_tab_backup call)."""
+        self._lookahead_refusals(path)
+        shape = self._shape()
+        J_next = np.asarray(J_next)
+        if J_next.shape != shape:
+            raise ValueError('J_next must have shape {}, not {}'.format(shape, J_next.shape))
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        if x.ndim != 2 or x.shape[1] != len(shape):
+            raise ValueError('x must have shape ({0},) or (B, {0}), not {1}'.format(len(shape), np.shape(x)))
+        t_k = self._lookahead_time(t_k)
+        x = x.astype(self.dtype)
+        if x.shape[0] == 0:
+            return (np.zeros(0, dtype=self.dtype), np.zeros((0, len(self.sys.control)), dtype=self.dtype),
+                    np.zeros(0, dtype=np.int32))
+        return self._lookahead_step(J_next, x, t_k, path)
+
+    def simulate_lookahead(self, J_next, x0, w=None, n_steps=None, t0=0, path=None):
+        """Closed-loop trajectories under LOOKAHEAD controls: at the state the plant is in, the control is
+
+            u_k = argmin over u of  E_w[ cost(x_k, u, w) + J_next(dyn(x_k, u, w)) ]        (`lookahead`)
+
+        followed by the model's own step, x_{k+1} = dyn(x_k, u_k, w_k), g_k = cost(x_k, u_k, w_k), formed as
+        `simulate` forms them -- how online control is run in practice, where `simulate` interpolates a tabulated
+        policy between nodes (a control that need not be admissible at the state in between).  The whole run is one
+        device call (kernel sdp_simulate_lookahead).  NOT in the reference API.
+
+        J_next : cost-to-go on the state grid, or a TIME-INDEXED one of shape (T_J,) + state_dims: step k of the
+                 call looks ahead into J_next[t0 + k].  From bellman_recursion's output (J, pol) with final cost
+                 J_fin that is `np.concatenate([J[1:], J_fin[None]])`: step k decides with the cost-to-go of k + 1.
+        x0, w, n_steps, t0 : as `simulate` (several perturbation variables and the single-trajectory form included)
+        path   : None / 'device', or 'host': the loop on the host, one lookahead call per step and the callables
+                 for the model's step (what also serves models that do not trace or are traced per step, `data[k]`)
+
+        Returns (x, u, g, q): x, u, g with `simulate`'s shapes, q (T[, B]) the minimised expected value of every
+        step.  backend_info['lookahead_path'] tells 'device' or 'host'."""
+        from . import lookahead as la
+        self._lookahead_refusals(path)
+        dims = self._shape()
+        d, nu = len(dims), len(self.sys.control)
+        x0 = np.asarray(x0, dtype=float)
+        single = x0.ndim == 1
+        x0 = np.atleast_2d(x0)
+        if x0.ndim != 2 or x0.shape[1] != d:
+            raise ValueError('x0 must have shape ({0},) or (B, {0}), not {1}'.format(d, x0.shape))
+        B = x0.shape[0]
+        n_w = len(self.sys.perturb)
+        if n_w:
+            if w is None:
+                raise ValueError('a stochastic system needs the perturbation sequence(s) w')
+            w = np.asarray(w, dtype=float)
+            if n_w >= 2:
+                w = w[:, :, None] if w.ndim == 2 else w
+                if w.ndim != 3 or w.shape[1] != n_w:
+                    raise ValueError('w must have shape (T, {0}) or (T, {0}, B), not {1}'.format(n_w, w.shape))
+            else:
+                w = w.reshape(-1, 1) if w.ndim == 1 else w
+                if w.ndim != 2:
+                    raise ValueError('w must have shape (T,) or (T, B), not {}'.format(w.shape))
+                w = w[:, None, :]
+            T = w.shape[0] if n_steps is None else int(n_steps)
+            if w.shape[-1] != B or w.shape[0] < T:
+                raise ValueError('w of shape {} does not give {} steps of {} trajectories'.format(w.shape, T, B))
+            w = w[:T]                                                              # (T, m, B)
+        else:
+            if n_steps is None:
+                raise ValueError('give n_steps for a deterministic system')
+            T, w = int(n_steps), None
+        J_next, timed = la.check_horizon(J_next, dims, T, t0)
+        dt = self.dtype
+        t_trace = None if self.sys.stationnary else t0
+        prob, tb, model = self._lookahead_unit(t_trace)
+        on_device = (path != 'host' and prob is not None and prob.look_box
+                     and model.t_value is None and model.param_index is None)
+        if on_device:
+            V = np.ascontiguousarray(J_next[int(t0):int(t0) + T] if timed else J_next, dtype=dt)
+            x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
+            w_d = None if w is None else np.ascontiguousarray(w if n_w >= 2 else w[:, 0], dtype=dt)
+            steps = np.ascontiguousarray(self.control_steps, dtype=float)
+            x = np.empty((T + 1, d, B), dtype=dt)
+            u = np.empty((T, nu, B), dtype=dt)
+            g = np.empty((T, B), dtype=dt)
+            q = np.empty((T, B), dtype=dt)
+            nat.check(nat.lib().sdp_problem_simulate_lookahead(
+                prob.h, T if timed else 0, nat.ptr(V), int(self.horizon_chunk_bytes), B, T, nat.ptr(x0_d), nat.ptr(w_d),
+                nat.ptr(steps), float(t0), nat.ptr(x), nat.ptr(u), nat.ptr(g), nat.ptr(q)))
+            x, u = np.ascontiguousarray(np.moveaxis(x, 1, 2)), np.ascontiguousarray(np.moveaxis(u, 1, 2))
+            self.backend_info = dict(prob.info, mode='traced', kernel='lookahead', lookahead_path='device', lookahead_box='device')
+            self._lookahead_prob = prob
+        else:
+            # the callables see the time index as `simulate`'s host loop hands it over where the model is traced per
+            # step or not at all (an int: `data[k]`), as the kernels do where the trace is symbolic (a real)
+            time_index = 'real' if (not isinstance(model, TraceError) and model.t_value is None) else 'int'
+            step = lambda J_k, x_k, t_k: self._lookahead_step(J_k, x_k, t_k, 'host')
+            x, u, g, q = la.simulate_lookahead(self, J_next, x0, w, T, t0, time_index, step=step)
+            self.backend_info = dict(getattr(self, 'backend_info', None) or {}, lookahead_path='host')
+        if single:
+            return x[:, 0], u[:, 0], g[:, 0], q[:, 0]
+        return x, u, g, q
+
     # ------------------------------------------------------------ policy evaluation
     def eval_policy(self, pol, n_iter, rel_dp=False, J_zero=None,
                     report_time=True, J_ref_full=False, tol=None, check_every=1):
