@@ -330,6 +330,23 @@ int sdp_problem_simulate_lookahead(sdp_problem *p, int64_t n_V_steps, const void
                                    const double *steps, double t0,
                                    void *host_x, void *host_u, void *host_g, void *host_q);
 
+/*
+ * Monte Carlo evaluation under LOOKAHEAD controls: sdp_problem_simulate_lookahead's closed loop with the perturbation
+ * of every step drawn on the device and only reductions coming back -- what sdp_problem_montecarlo is to
+ * sdp_problem_simulate.  host_V, n_V_steps, chunk_bytes, steps, t0: as sdp_problem_simulate_lookahead; the draw
+ * (seed, traj_offset, host_cum, n_law, host_law_grid; the Philox counter's step is k, the step of the call),
+ * n_burn, steps_per_launch and the outputs: as sdp_problem_montecarlo.  host_cum / host_law_grid are the law the
+ * PLANT draws from; the expectation inside the backup always runs over the law of the handle.  Neither chunk_bytes nor
+ * steps_per_launch changes a bit.  Needs a lookahead unit of a stochastic system with its own box function and without
+ * lifted constants (SDP_EMODULE for a code object without kernel sdp_montecarlo_lookahead).  One GPU.
+ */
+int sdp_problem_montecarlo_lookahead(sdp_problem *p, int64_t n_V_steps, const void *host_V, int64_t chunk_bytes,
+                                     int64_t B, int64_t T, int64_t n_burn, uint64_t seed, uint64_t traj_offset,
+                                     const void *host_x0, const double *host_cum, int32_t n_law,
+                                     const void *host_law_grid, const double *steps, double t0,
+                                     int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                                     void *host_x_final, uint64_t *host_occupancy);
+
 /* ---- transition operator of a policy: the forward half of the model -------------
  * Under a fixed policy the backup of sdp_problem_eval_policy is (P J)(s) + gbar(s), with
  * (P J)(s) = sum_j P[j] interp(J)(dyn(x_s, pol[s], w_j)).  A sdp_transop holds P^T as a CSR matrix on

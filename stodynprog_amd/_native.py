@@ -118,6 +118,8 @@ def _declare(lib):
                                                i32, vp, dbl, i64, vp, vp, vp, vp]),
         'sdp_problem_lookahead': (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp, dbl, vp, vp, vp]),
         'sdp_problem_simulate_lookahead': (C.c_int, [vp, i64, vp, i64, i64, i64, vp, vp, vp, dbl, vp, vp, vp, vp]),
+        'sdp_problem_montecarlo_lookahead': (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_uint64, C.c_uint64, vp, vp,
+                                                       i32, vp, vp, dbl, i64, vp, vp, vp, vp]),
         'sdp_transop_create': (C.c_int, [vp, vp, dbl, P(vp)]),
         'sdp_transop_from_coo': (C.c_int, [C.c_int, i64, i64, vp, vp, vp, P(vp)]),
         'sdp_transop_destroy': (C.c_int, [vp]),

@@ -941,6 +941,7 @@ struct sdp_problem {
     hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr, f_transitions = nullptr;
     hipFunction_t f_simulate_h = nullptr, f_montecarlo_h = nullptr;      // the loops under a time-indexed policy (sdp_horizon_kernel.h)
     hipFunction_t f_lookahead = nullptr, f_simulate_lookahead = nullptr; // lookahead units only (sdp_lookahead_kernel.h); the second: units with their own box function
+    hipFunction_t f_montecarlo_lookahead = nullptr;                      // .. and, of those, the units of a stochastic system
     // several controlled state variables (csrc/sdp_lead_kernel.h): the kernel that reduces V over w, launched
     // before every sweep, and its outputs (A[S] and a copy of V, both plane-major; E[nodes per trailing block];
     // bits of max |V|)
@@ -1239,6 +1240,10 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if (hipModuleGetFunction(&p->f_simulate_lookahead, p->mod, "sdp_simulate_lookahead") != hipSuccess) {
         (void)hipGetLastError();
         p->f_simulate_lookahead = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_montecarlo_lookahead, p->mod, "sdp_montecarlo_lookahead") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_montecarlo_lookahead = nullptr;
     }
     if (hipModuleGetFunction(&p->f_transitions, p->mod, "sdp_transitions") != hipSuccess) {
         (void)hipGetLastError();
@@ -2623,6 +2628,102 @@ extern "C" int sdp_problem_simulate_lookahead(sdp_problem *p, int64_t n_V_steps,
         HIP_TRY(hipMemcpy(host_g, dg.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(host_q, dq.p, (size_t)T * B * rs, hipMemcpyDeviceToHost));
     }
+    return SDP_OK;
+}
+
+// Monte Carlo evaluation under lookahead controls (kernel sdp_montecarlo_lookahead): the chunks of
+// sdp_problem_simulate_lookahead, the launch cuts, draw table and reductions of sdp_problem_montecarlo_h.
+extern "C" int sdp_problem_montecarlo_lookahead(sdp_problem *p, int64_t n_V_steps, const void *host_V, int64_t chunk_bytes,
+                                                int64_t B, int64_t T, int64_t n_burn, uint64_t seed, uint64_t traj_offset,
+                                                const void *host_x0, const double *host_cum, int32_t n_law,
+                                                const void *host_law_grid, const double *steps, double t0,
+                                                int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                                                void *host_x_final, uint64_t *host_occupancy)
+{
+    if (!p || !host_V || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_V_steps != 0 && n_V_steps != T)
+        return fail(SDP_EINVAL, "sdp_problem_montecarlo_lookahead: %lld cost-to-go steps for %lld steps (0: one for every step)", (long long)n_V_steps, (long long)T);
+    if (chunk_bytes < 1) return fail(SDP_EINVAL, "sdp_problem_montecarlo_lookahead: chunk_bytes = %lld: at least 1", (long long)chunk_bytes);
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (p->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw: use sdp_problem_simulate_lookahead");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    int rc;
+    if ((rc = lookahead_checks(p, "sdp_problem_montecarlo_lookahead", true, steps))) return rc;
+    if (p->prm_bytes) return fail(SDP_EINVAL, "sdp_problem_montecarlo_lookahead: a unit with lifted constants takes the host path");
+    if (!p->f_montecarlo_lookahead) return fail(SDP_EMODULE, "the model's code object has no sdp_montecarlo_lookahead kernel (built before Monte Carlo under lookahead controls)");
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(p->dtype);
+    const size_t nw = p->n_perturb > 1 ? (size_t)p->n_perturb : 1;
+    if ((size_t)(n_law - 1) * 8 + nw * n_law * rs > 65536)
+        return fail(SDP_EINVAL, "a law of %d points of %d variables needs %zu bytes of LDS: at most 65536", (int)n_law, (int)nw, (size_t)(n_law - 1) * 8 + nw * n_law * rs);
+    const size_t step_bytes = (size_t)p->S * rs;
+    const bool timed = n_V_steps != 0;
+    int64_t per_chunk = T;
+    if (timed && T > 0) {
+        per_chunk = (int64_t)((size_t)chunk_bytes / step_bytes);
+        if (per_chunk < 1) per_chunk = 1;
+        if (per_chunk > T) per_chunk = T;
+    }
+    DevBuf dV, dx, dacc, dout, dcum, dlaw, docc;
+    if ((rc = dV.alloc((timed ? (size_t)per_chunk : 1) * step_bytes))) return rc;
+    if (!timed) HIP_TRY(hipMemcpy(dV.p, host_V, step_bytes, hipMemcpyHostToDevice));
+    if ((rc = upload(dx, host_x0, (size_t)p->d * B * rs))) return rc;
+    if ((rc = upload(dcum, host_cum, (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, (size_t)nw * n_law * rs))) return rc;      // [n_perturb][n_law]
+    if ((rc = dacc.alloc((size_t)B * rs))) return rc;
+    if ((rc = dout.alloc((size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, (size_t)B * rs, p->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, (size_t)B * 8, p->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc((size_t)p->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, (size_t)p->S * 8, p->stream));
+    }
+    SdpLookMcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.V = dV.p; a.axes = p->axes.p; a.wgrid = p->wgrid.p; a.proba = p->proba.p;
+    a.cum = (const double *)dcum.p; a.law_grid = dlaw.p;
+    a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.S = p->S; a.V_stride = timed ? p->S : 0; a.seed = seed; a.traj_offset = traj_offset; a.n_burn = n_burn;
+    a.t0 = t0; a.W = p->W; a.n_law = n_law;
+    for (int c = 0; c < p->nu; ++c) a.steps[c] = steps[c];
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    // (the launch shape of sdp_problem_simulate_lookahead; the draw table in dynamic LDS: cumulative sums, then the values)
+    const unsigned lds = (unsigned)((size_t)(n_law - 1) * 8 + nw * n_law * rs);
+    const int64_t per_block = (int64_t)(64 / p->lanes) * 4;          // trajectories of a workgroup of 256
+    int64_t blocks = (B + per_block - 1) / per_block;
+    if (blocks > (int64_t)p->cus * 8) blocks = (int64_t)p->cus * 8;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    double kernel_ms = 0;
+    for (int64_t c = 0; c < T; c += per_chunk) {
+        const int64_t c_end = (T - c < per_chunk) ? T : c + per_chunk;
+        // (the kernels of the previous chunk have finished: the stream is synchronised at the end of every round)
+        if (timed) HIP_TRY(hipMemcpy(dV.p, (const char *)host_V + (size_t)c * step_bytes, (size_t)(c_end - c) * step_bytes, hipMemcpyHostToDevice));
+        a.chunk_first = timed ? c : 0;
+        HIP_TRY(hipEventRecord(p->ev0, p->stream));
+        for (int64_t k = c; k < c_end; k += steps_per_launch) {
+            a.step_begin = k;
+            a.step_end = (c_end - k < steps_per_launch) ? c_end : k + steps_per_launch;
+            HIP_TRY(hipModuleLaunchKernel(p->f_montecarlo_lookahead, (unsigned)blocks, 1, 1, 256, 1, 1, lds, p->stream, nullptr, extra));
+        }
+        HIP_TRY(hipEventRecord(p->ev1, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        kernel_ms += ms;
+    }
+    p->last_kernel_ms = kernel_ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, (size_t)p->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, (size_t)p->S * 8, hipMemcpyDeviceToHost));
     return SDP_OK;
 }
 

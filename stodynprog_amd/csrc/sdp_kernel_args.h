@@ -259,6 +259,38 @@ struct SdpLookSimArgs {
     int32_t pad_;
 };
 
+// Monte Carlo evaluation under lookahead controls (kernel `sdp_montecarlo_lookahead`, units with SDP_LOOKAHEAD_BOX
+// of a stochastic system): the closed loop of SdpLookSimArgs with the perturbation of every step DRAWN as
+// `sdp_montecarlo` draws it and only the reductions of SdpMcArgs kept.  The law the backup sums over (wgrid, proba)
+// is the solver's own; the law the plant draws from (cum, law_grid) is the caller's.
+struct SdpLookMcArgs {
+    const void *V;         // [S] one cost-to-go for every step (V_stride == 0), or [steps of the chunk][S]: step k reads slice k - chunk_first
+    const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
+    const void *wgrid;     // the law the backup sums over, as SdpLookArgs
+    const void *proba;
+    const double *cum;     // [n_law] float64 running sum of the drawn law's probabilities (the last entry is not read)
+    const void *law_grid;  // [n_law] drawn perturbation values (reals); several variables: [m][n_law]
+    void *x;               // [d][B] states: x at step_begin in, x at step_end out
+    void *acc;             // [B] running cost sums (reals)
+    long long *n_outside;  // [B] steps k >= n_burn whose x_k lies outside the state grid or is NaN
+    unsigned long long *occupancy;   // [S] visits of the node nearest to x_k, k >= n_burn (null: not counted)
+    int64_t B;             // trajectories
+    int64_t S;             // state nodes
+    int64_t V_stride;      // 0, or S (a time-indexed cost-to-go)
+    uint64_t seed;         // Philox key
+    uint64_t traj_offset;  // id of row 0 (Philox counter words 0 and 1 hold traj_offset + row)
+    int64_t step_begin;    // step of the call (Philox counter words 2 and 3) of this launch's first step
+    int64_t step_end;      // one past its last step
+    int64_t n_burn;        // steps before this one advance the state only
+    int64_t chunk_first;   // step of the call whose cost-to-go slice is V[0]
+    double t0;             // time index of step 0 of the call
+    double steps[SDP_MAXU];// control step hints
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+    int32_t W;             // points of the law the backup sums over
+    int32_t n_law;         // points of the drawn law (>= 1)
+};
+
 // Stand-alone multilinear interpolation (multilinear_cython.pyx:17-49).
 struct SdpInterpArgs {
     const void *values;    // [n_v][S]

@@ -1,5 +1,6 @@
-// sdp_lookahead_kernel.h -- one-step lookahead at ARBITRARY states (kernels `sdp_lookahead` and
-// `sdp_simulate_lookahead`): what turns a cost-to-go into a decision at the state the plant is in.
+// sdp_lookahead_kernel.h -- one-step lookahead at ARBITRARY states (kernels `sdp_lookahead`,
+// `sdp_simulate_lookahead` and `sdp_montecarlo_lookahead`): what turns a cost-to-go into a decision at the state the
+// plant is in.
 //
 // Included by sdp_sweep_kernel.h under SDP_LOOKAHEAD -- in the one-variable branch and in the branch of several
 // perturbation variables (SDP_NW >= 2) -- after the direct kernels, so only lookahead units carry it and every
@@ -13,6 +14,8 @@
 //                            trajectory run all the steps of a launch; per step the box at the carried state, the
 //                            lattice, the segmented argmin, then every lane of the group evaluates the model once at
 //                            u_opt and w[k][b] and lane 0 of the group stores x, u, g and q at their absolute steps.
+//   sdp_montecarlo_lookahead (.. of a stochastic system) that loop with w DRAWN on the device and reduced per trajectory:
+//                            the draw, the sums and the occupancy of `sdp_montecarlo`, nothing stored per step.
 //
 // The control lattice of a state comes from one of two places that give the same bits:
 //   * host-made arrays lo, hi, n of shape [nu][B] (SdpLookArgs.box_n not null): the host evaluated the box;
@@ -242,4 +245,119 @@ extern "C" __global__ void __launch_bounds__(256) sdp_simulate_lookahead(SdpLook
         }
     }
 }
+
+#if SDP_HAS_W
+// Monte Carlo evaluation under lookahead controls: the loop of `sdp_simulate_lookahead` with the perturbation of every
+// step drawn as `sdp_montecarlo_loop` draws it (Philox keyed by the seed, counter = (trajectory id, step of the call),
+// the cumulative table and the values staged once per workgroup in dynamic LDS) and nothing stored per step: per
+// trajectory acc = acc + g_k and the steps outside the grid over k >= n_burn, optionally the occupancy.  The
+// definition is stodynprog_amd/lookahead.py:monte_carlo_lookahead.
+//   * EVERY lane of a group computes the draw itself: it is a function of (seed, id, step) alone, so the lanes of a
+//     group get the same w without a shuffle, and a wave executes the ten rounds once whichever lanes want them.
+//   * A group past the end of the batch runs along on the FIRST trajectory of its own wave (the shuffles of the argmin
+//     and the ballots of the occupancy need every lane), stores nothing and counts nothing; a wave without a live
+//     trajectory skips the tile.  A wave reads its states before it stores them, so nobody reads a row that another
+//     wave is writing -- which trajectory 0 of the batch would be, the state being updated in place here.
+extern "C" __global__ void __launch_bounds__(256) sdp_montecarlo_lookahead(SdpLookMcArgs a)
+{
+    constexpr int L = SDP_LANES;
+    constexpr int NPW = 64 / L;                       // trajectories per wavefront
+#if defined(SDP_NW) && SDP_NW >= 2
+    constexpr int NW = SDP_NW;
+#else
+    constexpr int NW = 1;
+#endif
+    extern __shared__ double sdp_look_mc_lds[];       // cum[n_law - 1] (doubles), then law_grid[NW][n_law] (reals)
+    const int n_law = a.n_law;
+    double *cum = sdp_look_mc_lds;
+    sdp_real *wtab = (sdp_real *)(sdp_look_mc_lds + (n_law - 1));
+    for (int i = threadIdx.x; i < n_law - 1; i += blockDim.x) cum[i] = a.cum[i];
+    for (int i = threadIdx.x; i < NW * n_law; i += blockDim.x) wtab[i] = ((const sdp_real *)a.law_grid)[i];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & (L - 1);
+    const int slot = lane / L;
+    const int wave = threadIdx.x >> 6;
+    const int waves = blockDim.x >> 6;
+    const int64_t tile_traj = (int64_t)NPW * waves;
+
+    SdpSweepArgs s = {};
+    sdp_look_sweep_args(a, s);
+    SdpGrid<sdp_real, SDP_D> grid;
+    sdp_grid_from_args(s, grid);
+    sdp_real smax[SDP_D];
+#pragma unroll
+    for (int k = 0; k < SDP_D; ++k) smax[k] = ((const sdp_real *)a.axes)[a.axis_off[k] + a.orders[k] - 1];
+    sdp_real *xs = (sdp_real *)a.x;                   // (read at the start of a tile, written at its end: not __restrict__)
+    sdp_real *accs = (sdp_real *)a.acc;
+    const unsigned k0 = (unsigned)a.seed, k1 = (unsigned)(a.seed >> 32);
+
+    const int64_t n_tiles = (a.B + tile_traj - 1) / tile_traj;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t b_wave = tile * tile_traj + (int64_t)wave * NPW;
+        if (b_wave >= a.B) continue;                  // (wave-uniform: no trajectory of this wave is live)
+        const int64_t b = b_wave + slot;
+        const bool live = b < a.B;
+        const int64_t bb = live ? b : b_wave;
+        const unsigned long long id = a.traj_offset + (unsigned long long)bb;
+        sdp_real x[SDP_D];
+#pragma unroll
+        for (int k = 0; k < SDP_D; ++k) x[k] = xs[k * a.B + bb];
+        sdp_real acc = accs[bb];
+        int n_out = 0;                                // (of this launch: at most 2^30 steps)
+        // (the bound is the same in every lane of the wave: the shuffles of the argmin and the ballots run with every lane in step)
+        for (int64_t step = a.step_begin; step < a.step_end; ++step) {
+            const sdp_real *__restrict__ V = (const sdp_real *)a.V + (step - a.chunk_first) * a.V_stride;
+            const bool counted = step >= a.n_burn;
+            bool outside = false;
+#pragma unroll
+            for (int k = 0; k < SDP_D; ++k) outside = outside || !(x[k] >= grid.smin[k] && x[k] <= smax[k]);
+            n_out += (counted && outside) ? 1 : 0;
+            if (a.occupancy) {                        // (wave-uniform)
+                SdpCell<sdp_real, SDP_D, double> cell;
+                int node = 0;
+#pragma unroll
+                for (int k = 0; k < SDP_D; ++k) {
+                    sdp_locate_axis<sdp_real, SDP_D, double>(grid, k, x[k], cell);
+                    const int q = cell.off[k] + ((cell.lam[k] >= (sdp_real)0.5) ? grid.M[k] : 0);     // M[k] * (cell + 1)
+                    node += max(min(q, grid.M[k] * (a.orders[k] - 1)), 0);
+                }
+                sdp_mc_visit(a.occupancy, node, counted && live && sub == 0);
+            }
+            const double td = a.t0 + (double)step;
+            const sdp_real t = (sdp_real)td;
+            SdpBox box;
+            const bool valid = sdp_look_box_device(x, td, a.steps, box);
+            sdp_real best;
+            int ibest;
+            sdp_look_backup(s, grid, V, x, t, box, valid, sub, best, ibest);
+            sdp_real u[SDP_NU], xn[SDP_D], g;
+            if (valid) sdp_controls_at(box, ibest, u);
+#pragma unroll
+            for (int c = 0; c < SDP_NU; ++c) u[c] = valid ? u[c] : (sdp_real)NAN;
+            const SdpPhilox r = sdp_philox4x32_10((unsigned)id, (unsigned)(id >> 32), (unsigned)step,
+                                                  (unsigned)((unsigned long long)step >> 32), k0, k1);
+            const int j = sdp_mc_index(cum, n_law - 1, sdp_mc_uniform(r));     // 0 <= j <= n_law - 1
+#if defined(SDP_NW) && SDP_NW >= 2
+            sdp_real w[SDP_NW];
+#pragma unroll
+            for (int i = 0; i < SDP_NW; ++i) w[i] = wtab[i * n_law + j];
+#else
+            const sdp_real w = wtab[j];
+#endif
+            sdp_model_cell(x, u, w, t, xn, g);
+            if (counted) acc = acc + g;
+#pragma unroll
+            for (int k = 0; k < SDP_D; ++k) x[k] = xn[k];
+        }
+        if (live && sub == 0) {
+#pragma unroll
+            for (int k = 0; k < SDP_D; ++k) xs[k * a.B + b] = x[k];
+            accs[b] = acc;
+            a.n_outside[b] += n_out;
+        }
+    }
+}
+#endif  // SDP_HAS_W
 #endif

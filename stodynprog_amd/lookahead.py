@@ -34,6 +34,9 @@ The closed loop is that step followed by the model's own step: x_{k+1} = dyn(x_k
 g_k = cost(x_k, u_opt, w_k), formed exactly as `simulate` forms them, and q_k = J_opt, the minimised expected
 value.  With a time-indexed cost-to-go of shape (T_J,) + state_dims, step k of a call that starts at t0 looks
 ahead into J_next[t0 + k].
+
+`monte_carlo_lookahead` is that closed loop on the draws of `montecarlo.draws`, reduced per trajectory: the definition
+of `DPSolver.monte_carlo_lookahead` and of kernel `sdp_montecarlo_lookahead`.
 """
 import numpy as np
 
@@ -236,3 +239,51 @@ def simulate_lookahead(solver, J_next, x0, w, n_steps, t0=0, time_index='real', 
         q[k], u[k], _ = step(J_k, x[k], t_k)
         x[k + 1], g[k] = model_step(solver, x[k], u[k], None if w is None else w[k], t_k, time_index)
     return x, u, g, q
+
+
+def monte_carlo_lookahead(solver, J_next, x0, n_steps, seed, n_burn, ids, law_grid, law_proba, occupancy=False, t0=0,
+                          time_index='real', step=None, block=64):
+    """Monte Carlo evaluation under lookahead controls, as a definition (kernel `sdp_montecarlo_lookahead`):
+    (cost_sum (B,), n_outside (B,) int64, x_final (B, d), occupancy (state dims, int64) or None).
+
+    Composed of existing definitions only.  Draws: `montecarlo.draws(seed, ids, steps, law_proba)` with the Philox
+    counter's step k, the step of the call, and w = law_grid.astype(dt)[idx] (several variables: the column idx of
+    the joint table (m, n)).  Steps: `simulate_lookahead`'s -- the box at the carried state in float64, the lattice
+    rule with one rounding, the sequential expectation on the solver's OWN flat law, first-occurrence argmin, then
+    dyn / cost at u_opt and the drawn w.  Reductions over the steps k >= n_burn, with x_k the state BEFORE the step in
+    the problem's reals: acc = acc + g_k (one rounded add, k ascending), n_outside counts the x_k outside the grid or
+    NaN, occupancy counts `montecarlo.nearest_nodes(x_k)`; x_final = x_T.
+
+    (law_grid, law_proba) is the law the PLANT draws from; the expectation inside the backup always uses the solver's
+    discretised law.  A state without a valid lattice gets u = NaN: the state goes NaN and stays, acc becomes NaN and
+    every later counted step is outside -- nothing is special-cased.  `step`: the lookahead of one step, as in
+    `simulate_lookahead`; `block`: steps drawn at a time (it changes no bit)."""
+    from . import montecarlo as mc
+    dt = np.dtype(solver.dtype)
+    dims = tuple(len(g) for g in solver.state_grid)
+    T, n_burn = int(n_steps), int(n_burn)
+    J_next, timed = check_horizon(J_next, dims, T, t0)
+    x = np.atleast_2d(np.asarray(x0, dtype=float)).astype(dt)
+    B = x.shape[0]
+    ids = np.asarray(ids)
+    smin = np.array([dt.type(g[0]) for g in solver.state_grid], dtype=dt)
+    smax = np.array([dt.type(g[-1]) for g in solver.state_grid], dtype=dt)
+    wgrid = np.asarray(law_grid).astype(dt)
+    acc = np.zeros(B, dtype=dt)
+    n_out = np.zeros(B, dtype=np.int64)
+    occ = np.zeros(dims, dtype=np.int64) if occupancy else None
+    for k0 in range(0, T, int(block)):
+        n = min(int(block), T - k0)
+        idx = mc.draws(seed, ids, np.arange(k0, k0 + n, dtype=np.uint64), law_proba)
+        w = wgrid[idx][:, None, :] if wgrid.ndim == 1 else np.moveaxis(wgrid[:, idx], 0, 1)       # (n, m, B)
+        xs, _, g, _ = simulate_lookahead(solver, J_next, x, w, n, t0 + k0, time_index, step=step)
+        for i in range(n):
+            if k0 + i < n_burn:
+                continue
+            with np.errstate(all='ignore'):
+                acc = acc + g[i]
+                n_out += ~np.all((xs[i] >= smin) & (xs[i] <= smax), axis=1)
+            if occ is not None:
+                np.add.at(occ, tuple(mc.nearest_nodes(xs[i], solver.state_grid, dt).T), 1)
+        x = xs[n]
+    return acc, n_out, x, occ

@@ -2450,6 +2450,93 @@ class DPSolver(object):
             x = xs[n]
         return acc, n_out, x.astype(dt), occ
 
+    def monte_carlo_lookahead(self, J_next, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False,
+                              traj_offset=0, t0=0, path=None):
+        """Monte Carlo evaluation of a COST-TO-GO under lookahead controls: the closed loop of `simulate_lookahead`
+        for a batch of trajectories -- at the state the plant is in, u_k = argmin over u of
+        E_w[cost(x_k, u, w) + J_next(dyn(x_k, u, w))], then the model's own step -- with every step's perturbation
+        drawn ON THE DEVICE and only per-trajectory reductions coming back (kernel sdp_montecarlo_lookahead).  It is
+        to `simulate_lookahead` what `monte_carlo` is to `simulate`: no tabulated policy, no T x B reals up and no
+        (T+1) d B + T nu B + 2 T B reals down.  NOT in the reference API.  The definition is
+        `stodynprog_amd.lookahead.monte_carlo_lookahead`.
+
+        J_next   : cost-to-go on the state grid, or a time-indexed one of shape (T_J,) + state_dims read at t0 + k
+                   (as `simulate_lookahead`)
+        x0, n_traj, n_steps, seed, n_burn, traj_offset, occupancy, t0 : as `monte_carlo`
+        law      : the law the PLANT draws from, with `monte_carlo`'s meaning and checks (several perturbation
+                   variables: a joint table (m, n)); default: the solver's own.  The expectation INSIDE the backup
+                   always runs over the solver's own discretised law, whatever `law` is: a controller can be scored
+                   against a law it was not optimised for.
+        path     : None / 'device', or 'host' (as `simulate_lookahead`: one lookahead call per step, the draws of
+                   `montecarlo.draws` and the reductions in numpy, MC_HOST_BLOCK steps at a time; what also serves
+                   `data[k]` models and models that do not trace)
+
+        A state whose box has no valid lattice gets u = NaN: its trajectory's state and cost_sum go NaN and every
+        later counted step is outside.  Returns a `montecarlo.MonteCarloResult`; its `path` and
+        backend_info['lookahead_path'] tell 'device' or 'host'."""
+        from . import lookahead as la
+        if not self.sys.stochastic:
+            raise ValueError('a deterministic system has nothing to draw: use simulate_lookahead(J_next, x0, n_steps=...)')
+        self._lookahead_refusals(path)
+        dims = self._shape()
+        d = len(dims)
+        grid, proba = self._mc_law(law)
+        x0 = np.asarray(x0, dtype=float)
+        if x0.ndim == 1:
+            if x0.shape != (d,):
+                raise ValueError('x0 must have shape ({},) or (B, {})'.format(d, d))
+            if n_traj is None:
+                raise ValueError('give n_traj with a single start state')
+            x0 = np.broadcast_to(x0, (int(n_traj), d))
+        elif x0.ndim != 2 or x0.shape[1] != d:
+            raise ValueError('x0 must have shape ({},) or (B, {})'.format(d, d))
+        elif n_traj is not None and int(n_traj) != x0.shape[0]:
+            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[0]))
+        B = x0.shape[0]
+        n_steps, n_burn = int(n_steps), int(n_burn)
+        if n_steps < 1 or not 0 <= n_burn < n_steps:
+            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
+        seed = mc.check_seed(seed)
+        ids = self._mc_ids(B, traj_offset)
+        spl = int(self.steps_per_launch)
+        if spl < 1:
+            raise ValueError('steps_per_launch must be at least 1')
+        J_next, timed = la.check_horizon(J_next, dims, n_steps, t0)
+        dt = self.dtype
+        t_trace = None if self.sys.stationnary else t0
+        prob, tb, model = self._lookahead_unit(t_trace)
+        on_device = (path != 'host' and prob is not None and prob.look_box
+                     and model.t_value is None and model.param_index is None)
+        if on_device:
+            V = np.ascontiguousarray(J_next[int(t0):int(t0) + n_steps] if timed else J_next, dtype=dt)
+            x0_d = np.ascontiguousarray(x0.T, dtype=dt)                             # [d][B]
+            cum = np.ascontiguousarray(mc.cumulative(proba))
+            law_d = np.ascontiguousarray(grid, dtype=dt)                            # [n]; several variables: [m][n]
+            steps = np.ascontiguousarray(self.control_steps, dtype=float)
+            cost_sum = np.empty(B, dtype=dt)
+            n_out = np.empty(B, dtype=np.int64)
+            x_final = np.empty((d, B), dtype=dt)
+            occ = np.empty(int(np.prod(dims)), dtype=np.uint64) if occupancy else None
+            nat.check(nat.lib().sdp_problem_montecarlo_lookahead(
+                prob.h, n_steps if timed else 0, nat.ptr(V), int(self.horizon_chunk_bytes), B, n_steps, n_burn, seed,
+                int(traj_offset), nat.ptr(x0_d), nat.ptr(cum), len(proba), nat.ptr(law_d), nat.ptr(steps), float(t0), spl,
+                nat.ptr(cost_sum), nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
+            x_final = np.ascontiguousarray(x_final.T)
+            if occ is not None:
+                occ = occ.astype(np.int64).reshape(dims)
+            self.backend_info = dict(prob.info, mode='traced', kernel='lookahead', lookahead_path='device', lookahead_box='device')
+            self._lookahead_prob = prob
+            ran = 'device'
+        else:
+            time_index = 'real' if (not isinstance(model, TraceError) and model.t_value is None) else 'int'
+            step = lambda J_k, x_k, t_k: self._lookahead_step(J_k, x_k, t_k, 'host')
+            cost_sum, n_out, x_final, occ = la.monte_carlo_lookahead(
+                self, J_next, x0, n_steps, seed, n_burn, ids, grid, proba, bool(occupancy), t0, time_index, step=step,
+                block=self.MC_HOST_BLOCK)
+            self.backend_info = dict(getattr(self, 'backend_info', None) or {}, lookahead_path='host')
+            ran = 'host'
+        return mc.MonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seed, int(traj_offset), t0, ran)
+
     # ------------------------------------------------------------ state distributions under a policy
     def _transition_size(self):
         """(S, nnz, bytes) of the transition operator of the current discretisation"""
