@@ -419,6 +419,60 @@ int sdp_problem_bench_sweeps(sdp_problem *p, int32_t reps, int rel_dp, int64_t r
 int sdp_problem_debug_stamps(sdp_problem *p, int enable, unsigned long long *host,
                              int64_t n_words);
 
+/* ---- a family of same-shaped problems in one call (csrc/sdp_family_kernel.h) -------- */
+/*
+ * P problems that share the grid's shape, the number of controls and of perturbation points and one
+ * family code object (codegen.family_unit: kernel sdp_family_sweep, lifted constants), and differ in
+ * constants, grid ends, law and box table.  Every array of the descriptor is member-major; host arrays
+ * are only read during the call.  One launch backs up every listed member; member p of every result has
+ * the bits of the sdp_problem calls on problem p alone.  One GPU, node layout.
+ */
+typedef struct sdp_family sdp_family;
+typedef struct sdp_family_desc {
+    int32_t dtype;            /* SDP_F64 / SDP_F32 */
+    int32_t d;                /* state dimension, 1..4 */
+    int32_t nu;               /* control variables, 1..4 */
+    int32_t W;                /* perturbation points of every member (0: deterministic) */
+    int32_t P;                /* members, >= 1 */
+    int32_t n_params;         /* lifted constants per member (SDP_NPARAMS of the code object) */
+    int32_t box_per_node;     /* 0: box arrays [P][nu]; 1: [P][nu][S] */
+    int32_t lanes_per_node;   /* SDP_LANES of the code object: power of two in 1..64 */
+    int64_t orders[4];        /* grid points per state axis, the same for every member */
+    const void *axes;         /* [P][sum orders] reals: the members' axes, concatenated */
+    const void *wgrid;        /* [P][W] reals (NULL when W == 0) */
+    const void *proba;        /* [P][W] reals */
+    const void *box_lo;       /* reals */
+    const void *box_hi;       /* reals */
+    const int32_t *box_n;
+    const char *module_path;  /* family code object (.hsaco); its sdp_meta is checked */
+} sdp_family_desc;
+
+int sdp_family_create(const sdp_family_desc *desc, sdp_family **out);
+int sdp_family_destroy(sdp_family *f);
+/* J_next of every member, [P][S] reals in C order; every member is listed again for the sweeps that follow. */
+int sdp_family_set_value(sdp_family *f, const void *host_V);
+/* The lifted constants, [P][n] reals with n == n_params, for the launches that follow. */
+int sdp_family_set_params(sdp_family *f, const void *values, int32_t n);
+/* One backup of every member at time index t_k.  rel_dp: J[p] -= J[p][ref_index] afterwards, the
+ * subtracted values in J_ref_out[P] (as sdp_problem_vi_sweep does it, per member). */
+int sdp_family_vi_sweep(sdp_family *f, double t_k, int rel_dp, int64_t ref_index, double *J_ref_out);
+/* n_iter backups, each fed with the result of the one before; J_ref_out [n_iter][P] (rel_dp only). */
+int sdp_family_vi_sweeps(sdp_family *f, int32_t n_iter, int rel_dp, int64_t ref_index, double *J_ref_out);
+/*
+ * At most n_max backups with the convergence check of sdp_problem_vi_until per member, after sweeps
+ * check_every, 2 check_every, .. and n_max: one reduction launch for the members still listed and one
+ * readback of 24 bytes per such member.  A member whose span dmax - dmin <= tol leaves the list: nothing
+ * writes its slices afterwards.  n_done[P]: sweeps every member ran; stats [n_checks][P][2]: dmin, dmax of
+ * check c of member p (rows of checks the member did not run are left as they were); J_ref_out [n_max][P].
+ */
+int sdp_family_vi_until(sdp_family *f, int32_t n_max, int rel_dp, int64_t ref_index, int32_t check_every,
+                        double tol, int32_t *n_done, double *stats, double *J_ref_out);
+/* Results of every member's last sweep: [P][S] reals; [P][S][nu] reals (or NULL); [P][S] (or NULL). */
+int sdp_family_get_value(sdp_family *f, void *host_J);
+int sdp_family_get_policy(sdp_family *f, void *host_pol, int32_t *host_idx);
+/* HIP-event duration of the launches of the last sweep call (all its sweeps), milliseconds. */
+int sdp_family_last_kernel_ms(sdp_family *f, double *ms);
+
 /* ---- tabulated backup (models that cannot be traced into device code) ------- */
 /*
  * Replaces the numeric part of DPSolver._value_at_state_vect

@@ -10,6 +10,7 @@ HIP kernels on gfx950 through the C ABI of include/sdp_hip.h.
 from .sysdesc import SysDescription
 from .solver import DPSolver, TransitionOperator
 from .interp import MlinInterpolator
+from .family import SolverFamily
 
 __version__ = '0.1.0'
-__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator']
+__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator', 'SolverFamily']

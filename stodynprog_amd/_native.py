@@ -52,6 +52,17 @@ class sdp_problem_desc(C.Structure):
     ]
 
 
+class sdp_family_desc(C.Structure):
+    _fields_ = [
+        ('dtype', C.c_int32), ('d', C.c_int32), ('nu', C.c_int32), ('W', C.c_int32),
+        ('P', C.c_int32), ('n_params', C.c_int32), ('box_per_node', C.c_int32), ('lanes_per_node', C.c_int32),
+        ('orders', C.c_int64 * 4),
+        ('axes', C.c_void_p), ('wgrid', C.c_void_p), ('proba', C.c_void_p),
+        ('box_lo', C.c_void_p), ('box_hi', C.c_void_p), ('box_n', C.c_void_p),
+        ('module_path', C.c_char_p),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -120,6 +131,16 @@ def _declare(lib):
         'sdp_problem_simulate_lookahead': (C.c_int, [vp, i64, vp, i64, i64, i64, vp, vp, vp, dbl, vp, vp, vp, vp]),
         'sdp_problem_montecarlo_lookahead': (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_uint64, C.c_uint64, vp, vp,
                                                        i32, vp, vp, dbl, i64, vp, vp, vp, vp]),
+        'sdp_family_create': (C.c_int, [P(sdp_family_desc), P(vp)]),
+        'sdp_family_destroy': (C.c_int, [vp]),
+        'sdp_family_set_value': (C.c_int, [vp, vp]),
+        'sdp_family_set_params': (C.c_int, [vp, vp, i32]),
+        'sdp_family_vi_sweep': (C.c_int, [vp, dbl, C.c_int, i64, vp]),
+        'sdp_family_vi_sweeps': (C.c_int, [vp, i32, C.c_int, i64, vp]),
+        'sdp_family_vi_until': (C.c_int, [vp, i32, C.c_int, i64, i32, dbl, vp, vp, vp]),
+        'sdp_family_get_value': (C.c_int, [vp, vp]),
+        'sdp_family_get_policy': (C.c_int, [vp, vp, vp]),
+        'sdp_family_last_kernel_ms': (C.c_int, [vp, P(dbl)]),
         'sdp_transop_create': (C.c_int, [vp, vp, dbl, P(vp)]),
         'sdp_transop_from_coo': (C.c_int, [C.c_int, i64, i64, vp, vp, vp, P(vp)]),
         'sdp_transop_destroy': (C.c_int, [vp]),

@@ -756,6 +756,23 @@ def lookahead_unit(model, dtype, lanes, box=None, debug=None):
     return translation_unit(model, dtype, lanes, None, debug=debug, lookahead=box if box is not None else True)
 
 
+def family_unit(model, dtype, lanes):
+    """The generated source of a FAMILY unit (csrc/sdp_family_kernel.h, kernel `sdp_family_sweep`): the direct
+    prologue of a model with lifted constants, marked SDP_FAMILY, and the family header in the place of
+    sdp_sweep_kernel.h.  The kernel reads the constants of member p from row p of a table through
+    sdp_model_cell_at; `lanes` is the largest lane count of the members."""
+    if model.param_index is None:
+        raise ValueError('a family unit takes a model with lifted constants (TracedModel.lift_constants)')
+    if model.n_perturb >= 2:
+        raise NotImplementedError('a family unit takes one perturbation variable at most')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, lanes, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the unit carries sdp_family_sweep alone (csrc/sdp_family_kernel.h)')
+    head += ['#include "sdp_family_kernel.h"    // brings in the helpers of sdp_sweep_kernel.h', '']
+    return '\n'.join(head)
+
+
 def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False, lookahead=None):
     """The generated source of one model code object.  `family`: what the unit is to hold beside the direct node-order
     kernels of csrc/sdp_sweep_kernel.h --
@@ -1452,6 +1469,9 @@ def source_key(source):
             h.update(f.read())
     if '#define SDP_LOOKAHEAD ' in source:
         with open(os.path.join(CSRC, 'sdp_lookahead_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_FAMILY ' in source:
+        with open(os.path.join(CSRC, 'sdp_family_kernel.h'), 'rb') as f:
             h.update(f.read())
     h.update(source.encode())
     h.update(' '.join(HIPCC_FLAGS[:-1]).encode())

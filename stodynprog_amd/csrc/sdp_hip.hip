@@ -3686,3 +3686,434 @@ extern "C" int sdp_problem_attach_comm(sdp_problem *p, sdp_comm *c, int32_t n_ph
     p->red_V = nullptr;
     return SDP_OK;
 }
+
+// ---------------------------------------------------------------------------
+// a family of same-shaped problems (include/sdp_hip.h: sdp_family_*; kernel sdp_family_sweep of a family code
+// object, csrc/sdp_family_kernel.h).  Every device array is member-major.  Two value buffers [P][S] are used in
+// turn: sweep k reads one and writes the other, for the members still listed.  A member that has left the list
+// (sdp_family_vi_until) is written by nobody, so its result stays in the buffer of its last sweep: `where` says
+// which one.
+// ---------------------------------------------------------------------------
+template <typename real>
+__global__ void k_family_pick_ref(const real *__restrict__ J, int64_t S, int64_t ref, const int32_t *__restrict__ members,
+                                  int n_active, double *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_active) out[members[i]] = (double)J[(int64_t)members[i] * S + ref];
+}
+
+// k_shift per listed member: J[p][i] -= (real)ref[p]
+template <typename real>
+__global__ void __launch_bounds__(256) k_family_shift(real *__restrict__ J, int64_t S, const int32_t *__restrict__ members,
+                                                      const double *__restrict__ ref)
+{
+    const int64_t p = members[blockIdx.y];
+    const real r = (real)ref[p];
+    real *__restrict__ Jp = J + p * S;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < S; i += stride)
+        Jp[i] = Jp[i] - r;
+}
+
+// k_diff_stats per listed member (no shift): the three key words of member members[y] at acc[3 y ..]
+template <typename real>
+__global__ void __launch_bounds__(256) sdp_family_diff_stats(const real *__restrict__ J, const real *__restrict__ V, int64_t S,
+                                                             const int32_t *__restrict__ members,
+                                                             unsigned long long *__restrict__ acc)
+{
+    const int64_t p = members[blockIdx.y];
+    const real *__restrict__ Jp = J + p * S, *__restrict__ Vp = V + p * S;
+    real mn = real(INFINITY), mx = real(-INFINITY);
+    int nan = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < S; i += stride)
+        stat_node(Jp[i], Vp[i], mn, mx, nan);
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        const real omn = __shfl_xor(mn, off), omx = __shfl_xor(mx, off);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        nan |= __shfl_xor(nan, off);
+    }
+    __shared__ real s_mn[4], s_mx[4];
+    __shared__ int s_nan[4];
+    const int wave = threadIdx.x / warpSize;
+    if (threadIdx.x % warpSize == 0) { s_mn[wave] = mn; s_mx[wave] = mx; s_nan[wave] = nan; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int waves = (blockDim.x + warpSize - 1) / warpSize;
+        for (int w = 1; w < waves; ++w) {
+            mn = s_mn[w] < mn ? s_mn[w] : mn;
+            mx = s_mx[w] > mx ? s_mx[w] : mx;
+            nan |= s_nan[w];
+        }
+        unsigned long long *a = acc + 3 * (size_t)blockIdx.y;
+        atomicMax(a + 0, ~sdp_order_key((double)mn));
+        atomicMax(a + 1, sdp_order_key((double)mx));
+        if (nan) atomicMax(a + 2, 1ull);
+    }
+}
+
+struct sdp_family {
+    int dtype = SDP_F64, d = 0, nu = 0, W = 0, P = 0, n_params = 0, box_per_node = 0, lanes = 64;
+    int64_t S = 0;
+    int32_t orders[SDP_MAXD] = {0, 0, 0, 0};
+    int32_t axis_off[SDP_MAXD] = {0, 0, 0, 0};
+    int32_t n_axes = 0;
+    DevBuf axes, wgrid, proba, prm, box_lo, box_hi, box_n, buf[2], pol, idx, members, refs, stats;
+    int cur = 0;                           // buf[cur] is read (V), buf[cur ^ 1] written (J)
+    std::vector<int32_t> active;           // the members the next launch runs
+    std::vector<int> where;                // [P] the buffer that holds the member's latest values
+    bool list_changed = true;              // `active` differs from the device's copy
+    int refs_rows = 0;
+    hipModule_t mod = nullptr;
+    hipFunction_t f_sweep = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double last_kernel_ms = 0;
+    int cus = 256;
+    int32_t meta[SDP_META_WORDS] = {0};
+    ~sdp_family()
+    {
+        if (mod) (void)hipModuleUnload(mod);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+extern "C" int sdp_family_create(const sdp_family_desc *desc, sdp_family **out)
+{
+    if (!desc || !out) return fail(SDP_EINVAL, "NULL argument");
+    if (desc->dtype != SDP_F64 && desc->dtype != SDP_F32) return fail(SDP_EINVAL, "dtype must be SDP_F64 or SDP_F32");
+    if (desc->d < 1 || desc->d > SDP_MAXD)
+        return fail(SDP_EDIM, "state dimension %d: multilinear interpolation supports 1..4", desc->d);
+    if (desc->nu < 1 || desc->nu > SDP_MAXU) return fail(SDP_EINVAL, "number of controls %d outside 1..%d", desc->nu, SDP_MAXU);
+    if (desc->W < 0) return fail(SDP_EINVAL, "negative perturbation count");
+    if (desc->P < 1 || desc->P > 65535) return fail(SDP_EINVAL, "%d members: a family has 1..65535", (int)desc->P);
+    if (desc->n_params < 0) return fail(SDP_EINVAL, "negative number of lifted constants");
+    if (!desc->module_path) return fail(SDP_EMODULE, "no family code object given");
+    if (!desc->axes) return fail(SDP_EINVAL, "state axes missing");
+    if (!desc->box_lo || !desc->box_hi || !desc->box_n) return fail(SDP_EINVAL, "control box arrays missing");
+    sdp_family *f = new sdp_family();
+    std::unique_ptr<sdp_family> guard(f);
+    f->dtype = desc->dtype; f->d = desc->d; f->nu = desc->nu; f->W = desc->W; f->P = desc->P;
+    f->n_params = desc->n_params; f->box_per_node = desc->box_per_node ? 1 : 0; f->lanes = desc->lanes_per_node;
+    if (f->lanes < 1 || f->lanes > 64 || (f->lanes & (f->lanes - 1))) return fail(SDP_EINVAL, "lanes_per_node must be a power of two in 1..64");
+    const size_t rs = real_size(f->dtype);
+    int64_t S = 1, total = 0;
+    for (int k = 0; k < f->d; ++k) {
+        if (desc->orders[k] < 2) return fail(SDP_EINVAL, "state axis %d has %lld points: at least 2 needed to interpolate", k, (long long)desc->orders[k]);
+        f->orders[k] = (int32_t)desc->orders[k];
+        f->axis_off[k] = (int32_t)total;
+        total += desc->orders[k];
+        S *= desc->orders[k];
+        if (S >= (int64_t)1 << 31) return fail(SDP_EINVAL, "state grid too large: 32-bit vertex indices (pyx:164-165)");
+    }
+    f->S = S;
+    f->n_axes = (int32_t)total;
+    f->cus = device_cus();
+    const size_t P = (size_t)f->P;
+    int rc;
+    if ((rc = upload(f->axes, desc->axes, P * (size_t)total * rs))) return rc;
+    if (f->W > 0) {
+        if (!desc->wgrid || !desc->proba) return fail(SDP_EINVAL, "perturbation grid/weights missing");
+        if ((rc = upload(f->wgrid, desc->wgrid, P * f->W * rs))) return rc;
+        if ((rc = upload(f->proba, desc->proba, P * f->W * rs))) return rc;
+    }
+    const size_t nbox = P * (size_t)f->nu * (f->box_per_node ? (size_t)S : 1);
+    if ((rc = upload(f->box_lo, desc->box_lo, nbox * rs))) return rc;
+    if ((rc = upload(f->box_hi, desc->box_hi, nbox * rs))) return rc;
+    if ((rc = upload(f->box_n, desc->box_n, nbox * 4))) return rc;
+    if ((rc = f->prm.alloc(P * (size_t)f->n_params * rs))) return rc;
+    for (int b = 0; b < 2; ++b) {
+        if ((rc = f->buf[b].alloc(P * S * rs))) return rc;
+        HIP_TRY(hipMemset(f->buf[b].p, 0, P * S * rs));
+    }
+    if ((rc = f->pol.alloc(P * S * f->nu * rs))) return rc;
+    if ((rc = f->idx.alloc(P * S * 4))) return rc;
+    if ((rc = f->members.alloc(P * 4))) return rc;
+    if ((rc = f->stats.alloc(P * 3 * 8))) return rc;
+    HIP_TRY(hipMemset(f->pol.p, 0, P * S * f->nu * rs));
+    HIP_TRY(hipMemset(f->idx.p, 0, P * S * 4));
+    f->where.assign(P, 0);
+    f->active.resize(P);
+    for (size_t p = 0; p < P; ++p) f->active[p] = (int32_t)p;
+
+    hipError_t e = hipModuleLoad(&f->mod, desc->module_path);
+    if (e != hipSuccess) { f->mod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", desc->module_path, hipGetErrorString(e)); }
+    {
+        hipDeviceptr_t mptr = nullptr;
+        size_t mbytes = 0;
+        if (hipModuleGetGlobal(&mptr, &mbytes, f->mod, "sdp_meta") != hipSuccess || mbytes != sizeof(f->meta)) {
+            (void)hipGetLastError();
+            return fail(SDP_EMODULE, "code object %s does not declare `sdp_meta` (%d words, sdp_kernel_args.h): "
+                        "cannot check that it was built for this family", desc->module_path, SDP_META_WORDS);
+        }
+        HIP_TRY(hipMemcpyDtoH(f->meta, mptr, sizeof(f->meta)));
+        const int32_t *m = f->meta;
+        const char *what = nullptr;
+        char detail[160] = "";
+#define META_CHECK(cond, ...) if (!what && !(cond)) { what = #cond; snprintf(detail, sizeof(detail), __VA_ARGS__); }
+        META_CHECK(m[SDP_META_MAGIC_AT] == SDP_META_MAGIC, "bad magic 0x%x", (unsigned)m[SDP_META_MAGIC_AT]);
+        META_CHECK((m[SDP_META_FLAGS] & SDP_META_F_FAMILY) != 0, "not a family unit (flags 0x%x)", (unsigned)m[SDP_META_FLAGS]);
+        META_CHECK(m[SDP_META_REAL_BYTES] == (int)rs, "built for %d-byte reals, the family has %d-byte reals", m[SDP_META_REAL_BYTES], (int)rs);
+        META_CHECK(m[SDP_META_D] == f->d, "built for %d state variables, the family has %d", m[SDP_META_D], f->d);
+        META_CHECK(m[SDP_META_NU] == f->nu, "built for %d controls, the family has %d", m[SDP_META_NU], f->nu);
+        META_CHECK((m[SDP_META_HAS_W] != 0) == (f->W > 0), "built %s a perturbation, the family has W = %d", m[SDP_META_HAS_W] ? "with" : "without", f->W);
+        META_CHECK(m[SDP_META_NW] == 0, "built for %d perturbation variables, a family takes one", m[SDP_META_NW]);
+#undef META_CHECK
+        if (what)
+            return fail(SDP_EMODULE, "code object %s was not built for this family: %s", desc->module_path, detail);
+    }
+    e = hipModuleGetFunction(&f->f_sweep, f->mod, "sdp_family_sweep");
+    if (e != hipSuccess) return fail(SDP_EMODULE, "code object %s has no sdp_family_sweep kernel: %s", desc->module_path, hipGetErrorString(e));
+    {
+        // the table of constants is the caller's: the code object's own row only tells how many there are
+        hipDeviceptr_t pptr = nullptr;
+        size_t pbytes = 0;
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->mod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs)
+            return fail(SDP_EMODULE, "code object %s declares %zu lifted constant(s), the family has %d", desc->module_path, pbytes / rs, f->n_params);
+    }
+    HIP_TRY(hipStreamCreate(&f->stream));
+    HIP_TRY(hipEventCreate(&f->ev0));
+    HIP_TRY(hipEventCreate(&f->ev1));
+    guard.release();
+    *out = f;
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_destroy(sdp_family *f)
+{
+    if (f) { (void)hipDeviceSynchronize(); delete f; }
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_set_value(sdp_family *f, const void *host_V)
+{
+    if (!f || !host_V) return fail(SDP_EINVAL, "NULL argument");
+    const size_t bytes = (size_t)f->P * f->S * real_size(f->dtype);
+    HIP_TRY(hipMemcpyAsync(f->buf[f->cur].p, host_V, bytes, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    f->active.resize((size_t)f->P);
+    for (int p = 0; p < f->P; ++p) { f->active[(size_t)p] = p; f->where[(size_t)p] = f->cur; }
+    f->list_changed = true;
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_set_params(sdp_family *f, const void *values, int32_t n)
+{
+    if (!f || n < 0 || (n > 0 && !values)) return fail(SDP_EINVAL, "sdp_family_set_params: bad arguments");
+    if (n != f->n_params)
+        return fail(SDP_EINVAL, "sdp_family_set_params: the family has %d lifted constant(s) per member, %d given", f->n_params, (int)n);
+    const size_t bytes = (size_t)f->P * (size_t)n * real_size(f->dtype);
+    if (!bytes) return SDP_OK;
+    // on the family's stream: ordered after the launches that still read the old values
+    HIP_TRY(hipMemcpyAsync(f->prm.p, values, bytes, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));        // `values` may be reused by the caller
+    return SDP_OK;
+}
+
+static int family_send_list(sdp_family *f)
+{
+    if (!f->list_changed) return SDP_OK;
+    if (!f->active.empty()) {
+        HIP_TRY(hipMemcpyAsync(f->members.p, f->active.data(), f->active.size() * 4, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));    // (the list may change before the copy would have run)
+    }
+    f->list_changed = false;
+    return SDP_OK;
+}
+
+static int family_ensure_refs(sdp_family *f, int rows)
+{
+    if (rows < 1) rows = 1;
+    if (f->refs_rows < rows) {
+        int rc = f->refs.alloc((size_t)rows * f->P * 8);
+        if (rc) { f->refs_rows = 0; return rc; }
+        f->refs_rows = rows;
+    }
+    HIP_TRY(hipMemsetAsync(f->refs.p, 0, (size_t)rows * f->P * 8, f->stream));
+    return SDP_OK;
+}
+
+// one backup of the listed members, buf[cur] -> buf[cur ^ 1], and with rel_dp the shift of every one of them by its
+// own J[ref] (k_pick_ref + k_shift of the single problem, per member), the subtracted values in row `slot` of refs
+static int family_backup(sdp_family *f, double t_k, int rel_dp, int64_t ref_index, int slot)
+{
+    const int n = (int)f->active.size();
+    if (n < 1) return SDP_OK;
+    int rc;
+    if ((rc = family_send_list(f))) return rc;
+    SdpFamilyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.V = f->buf[f->cur].p; a.J = f->buf[f->cur ^ 1].p; a.pol = f->pol.p; a.idx = (int32_t *)f->idx.p;
+    a.axes = f->axes.p; a.wgrid = f->wgrid.p; a.proba = f->proba.p; a.prm = f->prm.p;
+    a.box_lo = f->box_lo.p; a.box_hi = f->box_hi.p; a.box_n = (const int32_t *)f->box_n.p;
+    a.members = (const int32_t *)f->members.p;
+    a.S = f->S; a.t_k = t_k;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = f->orders[k]; a.axis_off[k] = f->axis_off[k]; }
+    a.n_axes = f->n_axes; a.W = f->W; a.box_per_node = f->box_per_node; a.n_active = n;
+    // a multiple of 8 workgroups (one share per XCD, sdp_family_kernel.h): per XCD as many as it has tiles to walk,
+    // at most 8 per CU of the chip in all
+    const int64_t tile = (64 / f->lanes) * 4;
+    const int64_t tiles = (f->S + tile - 1) / tile;
+    const int parts = n >= 8 ? 1 : 8 / n;
+    int64_t per_xcd = n >= 8 ? (int64_t)((n + 7) / 8) * tiles : (tiles + parts - 1) / parts;
+    if (per_xcd > f->cus) per_xcd = f->cus;
+    if (per_xcd < 1) per_xcd = 1;
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(f->f_sweep, (unsigned)(per_xcd * 8), 1, 1, 256, 1, 1, 0, f->stream, nullptr, extra));
+    if (rel_dp) {
+        double *ref = (double *)f->refs.p + (size_t)slot * f->P;
+        unsigned bx = (unsigned)((f->S + 255) / 256);
+        if (bx > 64) bx = 64;
+        const int32_t *members = (const int32_t *)f->members.p;
+        if (f->dtype == SDP_F32) {
+            hipLaunchKernelGGL(k_family_pick_ref<float>, dim3((n + 63) / 64), dim3(64), 0, f->stream, (const float *)a.J, f->S, ref_index, members, n, ref);
+            hipLaunchKernelGGL(k_family_shift<float>, dim3(bx, n), dim3(256), 0, f->stream, (float *)a.J, f->S, members, ref);
+        } else {
+            hipLaunchKernelGGL(k_family_pick_ref<double>, dim3((n + 63) / 64), dim3(64), 0, f->stream, (const double *)a.J, f->S, ref_index, members, n, ref);
+            hipLaunchKernelGGL(k_family_shift<double>, dim3(bx, n), dim3(256), 0, f->stream, (double *)a.J, f->S, members, ref);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    for (int32_t p : f->active) f->where[(size_t)p] = f->cur ^ 1;
+    return SDP_OK;
+}
+
+static int family_check_ref(const sdp_family *f, int rel_dp, int64_t ref_index)
+{
+    if (rel_dp && (ref_index < 0 || ref_index >= f->S)) return fail(SDP_EINVAL, "reference node %lld outside the grid", (long long)ref_index);
+    return SDP_OK;
+}
+
+static int family_finish(sdp_family *f, int rel_dp, int rows, double *J_ref_out)
+{
+    HIP_TRY(hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    f->last_kernel_ms = ms;
+    if (rel_dp && J_ref_out && rows > 0) HIP_TRY(hipMemcpy(J_ref_out, f->refs.p, (size_t)rows * f->P * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_vi_sweeps(sdp_family *f, int32_t n_iter, int rel_dp, int64_t ref_index, double *J_ref_out)
+{
+    if (!f) return fail(SDP_EINVAL, "NULL family");
+    if (n_iter < 1) return fail(SDP_EINVAL, "n_iter must be at least 1");
+    int rc;
+    if ((rc = family_check_ref(f, rel_dp, ref_index))) return rc;
+    if ((rc = family_ensure_refs(f, n_iter))) return rc;
+    if ((rc = family_send_list(f))) return rc;
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int32_t k = 0; k < n_iter; ++k) {
+        if (k > 0) f->cur ^= 1;                      // J of the previous sweep becomes J_next
+        if ((rc = family_backup(f, 0.0, rel_dp, ref_index, k))) return rc;
+    }
+    return family_finish(f, rel_dp, n_iter, J_ref_out);
+}
+
+extern "C" int sdp_family_vi_sweep(sdp_family *f, double t_k, int rel_dp, int64_t ref_index, double *J_ref_out)
+{
+    if (!f) return fail(SDP_EINVAL, "NULL family");
+    int rc;
+    if ((rc = family_check_ref(f, rel_dp, ref_index))) return rc;
+    if ((rc = family_ensure_refs(f, 1))) return rc;
+    if ((rc = family_send_list(f))) return rc;
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    if ((rc = family_backup(f, t_k, rel_dp, ref_index, 0))) return rc;
+    return family_finish(f, rel_dp, 1, J_ref_out);
+}
+
+extern "C" int sdp_family_vi_until(sdp_family *f, int32_t n_max, int rel_dp, int64_t ref_index, int32_t check_every,
+                                   double tol, int32_t *n_done, double *stats, double *J_ref_out)
+{
+    if (!f || !n_done || !stats) return fail(SDP_EINVAL, "NULL argument");
+    if (n_max < 1) return fail(SDP_EINVAL, "n_max must be at least 1");
+    if (check_every < 1) return fail(SDP_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0)) return fail(SDP_EINVAL, "tol must be a number >= 0");
+    int rc;
+    if ((rc = family_check_ref(f, rel_dp, ref_index))) return rc;
+    if ((rc = family_ensure_refs(f, n_max))) return rc;
+    if ((rc = family_send_list(f))) return rc;
+    for (int p = 0; p < f->P; ++p) n_done[p] = 0;
+    std::vector<unsigned long long> keys((size_t)f->P * 3);
+    int32_t checks = 0;
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int32_t k = 0; k < n_max && !f->active.empty(); ++k) {
+        if (k > 0) f->cur ^= 1;
+        if ((rc = family_backup(f, 0.0, rel_dp, ref_index, k))) return rc;
+        for (int32_t p : f->active) n_done[p] = k + 1;
+        if ((k + 1) % check_every == 0 || k + 1 == n_max) {
+            const int n = (int)f->active.size();
+            HIP_TRY(hipMemsetAsync(f->stats.p, 0, (size_t)n * 3 * 8, f->stream));
+            unsigned bx = (unsigned)((f->S + 255) / 256);
+            if (bx > 64) bx = 64;
+            unsigned long long *acc = (unsigned long long *)f->stats.p;
+            const int32_t *members = (const int32_t *)f->members.p;
+            if (f->dtype == SDP_F32)
+                hipLaunchKernelGGL(sdp_family_diff_stats<float>, dim3(bx, n), dim3(256), 0, f->stream,
+                                   (const float *)f->buf[f->cur ^ 1].p, (const float *)f->buf[f->cur].p, f->S, members, acc);
+            else
+                hipLaunchKernelGGL(sdp_family_diff_stats<double>, dim3(bx, n), dim3(256), 0, f->stream,
+                                   (const double *)f->buf[f->cur ^ 1].p, (const double *)f->buf[f->cur].p, f->S, members, acc);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(keys.data(), f->stats.p, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(hipStreamSynchronize(f->stream));
+            std::vector<int32_t> keep;
+            for (int i = 0; i < n; ++i) {
+                const int32_t p = f->active[(size_t)i];
+                const bool nan = keys[(size_t)i * 3 + 2] != 0;
+                const double dmin = nan ? NAN : sdp_key_value(~keys[(size_t)i * 3]);
+                const double dmax = nan ? NAN : sdp_key_value(keys[(size_t)i * 3 + 1]);
+                stats[((size_t)checks * f->P + p) * 2] = dmin;
+                stats[((size_t)checks * f->P + p) * 2 + 1] = dmax;
+                if (!(dmax - dmin <= tol)) keep.push_back(p);       // NaN never converges
+            }
+            ++checks;
+            if (keep.size() != f->active.size()) { f->active.swap(keep); f->list_changed = true; }
+        }
+    }
+    return family_finish(f, rel_dp, n_max, J_ref_out);
+}
+
+// [P][S] elements of `elem_bytes` from the two buffers, every member from the one its last sweep wrote
+static int family_download(sdp_family *f, void *host, size_t elem_bytes)
+{
+    const size_t row = (size_t)f->S * elem_bytes;
+    for (int p = 0; p < f->P;) {
+        int q = p + 1;
+        while (q < f->P && f->where[(size_t)q] == f->where[(size_t)p]) ++q;      // (a run of members in one buffer: one copy)
+        HIP_TRY(hipMemcpyAsync((char *)host + (size_t)p * row, (const char *)f->buf[f->where[(size_t)p]].p + (size_t)p * row,
+                               (size_t)(q - p) * row, hipMemcpyDeviceToHost, f->stream));
+        p = q;
+    }
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_get_value(sdp_family *f, void *host_J)
+{
+    if (!f || !host_J) return fail(SDP_EINVAL, "NULL argument");
+    return family_download(f, host_J, real_size(f->dtype));
+}
+
+extern "C" int sdp_family_get_policy(sdp_family *f, void *host_pol, int32_t *host_idx)
+{
+    if (!f) return fail(SDP_EINVAL, "NULL family");
+    const size_t n = (size_t)f->P * f->S;
+    if (host_pol) HIP_TRY(hipMemcpyAsync(host_pol, f->pol.p, n * f->nu * real_size(f->dtype), hipMemcpyDeviceToHost, f->stream));
+    if (host_idx) HIP_TRY(hipMemcpyAsync(host_idx, f->idx.p, n * 4, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_last_kernel_ms(sdp_family *f, double *ms)
+{
+    if (!f || !ms) return fail(SDP_EINVAL, "NULL argument");
+    *ms = f->last_kernel_ms;
+    return SDP_OK;
+}

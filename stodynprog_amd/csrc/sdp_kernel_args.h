@@ -34,7 +34,8 @@ enum {
     SDP_META_F_SHIFT = 128, // certified filter on the shifted lattice (a perturbation that reaches x0')
     SDP_META_F_LEAD = 256,  // node-order sweep with the filter on an array reduced over w (sdp_lead_kernel.h):
                             // the code object also exports sdp_lead_reduce, launched before every sweep
-    SDP_META_F_PEER_STORES = 512   // the backup kernels store J through sdp_store_J (SdpSweepArgs.peer_J: direct exchange)
+    SDP_META_F_PEER_STORES = 512,  // the backup kernels store J through sdp_store_J (SdpSweepArgs.peer_J: direct exchange)
+    SDP_META_F_FAMILY = 1024       // a family unit (sdp_family_kernel.h): sdp_family_sweep and nothing else
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -94,6 +95,33 @@ struct SdpSweepArgs {
     int32_t n_peer;                     // 0: single GPU or another exchange -- no peer stores at all
     int32_t pad_;
     void *reserve_;                     // not used (zero): the implicit kernel arguments behind the struct keep their offsets
+};
+
+// One Bellman backup of a FAMILY of same-shaped problems (sdp_family_kernel.h, kernel `sdp_family_sweep`): the
+// backup of SdpSweepArgs with a member index in front of every array.  Members share the grid's shape, the number
+// of controls and of perturbation points and the model's structure; each has its own constants, grid ends, law
+// and box table.  A launch runs the members listed in `members`, whole.
+struct SdpFamilyArgs {
+    const void *V;         // [P][S] cost-to-go J_next of every member, C order
+    void *J;               // [P][S] output J_k (only the slices of the listed members are written)
+    void *pol;             // [P][S][nu] output optimal control VALUES (may be null)
+    int32_t *idx;          // [P][S] output flat C-order index into the member's control lattice (may be null)
+    const void *axes;      // [P][n_axes] concatenated state-grid axes of every member; axis k at axis_off[k]
+    const void *wgrid;     // [P][W] perturbation grids (null when W == 0)
+    const void *proba;     // [P][W] perturbation weights
+    const void *prm;       // [P][SDP_NPARAMS] lifted constants, row p for member p (sdp_model_cell_at)
+    const void *box_lo;    // control box lower ends: [P][nu] or [P][nu][S] (per node)
+    const void *box_hi;    // control box upper ends
+    const int32_t *box_n;  // number of control points: [P][nu] or [P][nu][S]
+    const int32_t *members;// [n_active] the members this launch runs (distinct, each < P)
+    int64_t S;             // state nodes of one member
+    double t_k;            // time index for non-stationary systems
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+    int32_t n_axes;        // sum of orders: reals per row of `axes`
+    int32_t W;             // perturbation points (0: deterministic systems)
+    int32_t box_per_node;  // 0: one box per member, 1: per-node arrays
+    int32_t n_active;      // members listed (>= 1)
 };
 
 // Batched closed-loop simulation (the user loop of the reference's examples, e.g.

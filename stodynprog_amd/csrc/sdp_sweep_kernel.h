@@ -133,7 +133,9 @@ SDP_DEV void sdp_grid_from_args(const SdpSweepArgs &a, SdpGrid<sdp_real, SDP_D> 
 template <bool H, typename Args> SDP_DEV void sdp_simulate_loop(const Args &a);
 template <bool H, typename Args> SDP_DEV void sdp_montecarlo_loop(const Args &a);
 
-#if defined(SDP_NW) && SDP_NW >= 2
+#if defined(SDP_FAMILY)
+// a family unit (sdp_family_kernel.h, which includes this file) takes the helpers above and nothing else
+#elif defined(SDP_NW) && SDP_NW >= 2
 #include "sdp_multiw_kernel.h"  // the kernels below and sdp_meta for several perturbation variables (w a vector)
 #include "sdp_trans_kernel.h"   // sdp_transitions on the flat law
 #include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy

@@ -1,0 +1,411 @@
+"""A family of same-shaped problems solved in one device call: `SolverFamily`.
+
+The reference's own studies are loops over small problems -- a range of storage capacities, of rated powers, of
+correlations -- and a grid of a few thousand nodes fills a small fraction of the GPU: a loop of solo calls pays the
+launch and call costs once per member and sweep.  A SolverFamily takes P `DPSolver` objects, each set up exactly as
+for a solo call, and runs their sweeps together: one launch of kernel `sdp_family_sweep`
+(csrc/sdp_family_kernel.h) backs up every member.
+
+The definition is the solo call: member p of every result equals, bit for bit, what `solvers[p]` returns from the
+same method with `kernel = 'generic'`.
+
+Members may differ in every real constant of dyn / cost, in the ends of the state grid, in the perturbation grid
+and weights, in control_steps and control_box.  They must agree in the grid's shape, the dtype, the number of
+controls, the `stationnary` flag, the number of perturbation points and the structure of the traced model
+(`TracedModel.structure_key`): the constants are always lifted, and the members share one code object that reads
+row p of a table of constants for member p.  NOT in the reference API.
+"""
+from __future__ import division, print_function
+import ctypes as C
+import hashlib
+
+import numpy as np
+
+from . import _native as nat
+from . import codegen
+from . import convergence as conv
+from .solver import DPSolver
+from .trace import TraceError, trace_model
+
+__all__ = ['SolverFamily']
+
+
+class _FamilyProblem(object):
+    """Owner of one sdp_family handle (include/sdp_hip.h): the members [first, last) of a family."""
+
+    def __init__(self, tabs, first, last, module, dtype, shape, nu, W):
+        self.P = last - first
+        self.dtype = np.dtype(dtype)
+        self.shape = tuple(shape)
+        self.S = int(np.prod(shape))
+        self.nu = nu
+        # host arrays the descriptor points to, cut to the members of this handle
+        keep = {k: np.ascontiguousarray(tabs[k][first:last]) for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n')
+                if tabs[k] is not None}
+        d = nat.sdp_family_desc()
+        d.dtype = nat.np_real(dtype)
+        d.d, d.nu, d.W, d.P = len(shape), nu, W, self.P
+        d.n_params = tabs['prm'].shape[1]
+        d.box_per_node = int(tabs['per_node'])
+        d.lanes_per_node = int(tabs['lanes'])
+        for k, n in enumerate(shape):
+            d.orders[k] = n
+        d.axes = keep['axes'].ctypes.data
+        if W > 0:
+            d.wgrid = keep['wgrid'].ctypes.data
+            d.proba = keep['proba'].ctypes.data
+        d.box_lo = keep['lo'].ctypes.data
+        d.box_hi = keep['hi'].ctypes.data
+        d.box_n = keep['n'].ctypes.data
+        d.module_path = module.encode()
+        h = C.c_void_p()
+        nat.check(nat.lib().sdp_family_create(C.byref(d), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            nat.lib().sdp_family_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_value(self, V):
+        V = np.ascontiguousarray(V, dtype=self.dtype)
+        assert V.size == self.P * self.S
+        nat.check(nat.lib().sdp_family_set_value(self.h, nat.ptr(V)))
+
+    def set_params(self, values):
+        values = np.ascontiguousarray(values, dtype=self.dtype)
+        assert values.shape[0] == self.P
+        nat.check(nat.lib().sdp_family_set_params(self.h, nat.ptr(values), int(values.shape[1])))
+
+    def sweep(self, t_k=0.0, rel_dp=False, ref_index=0):
+        refs = np.zeros(self.P)
+        nat.check(nat.lib().sdp_family_vi_sweep(self.h, float(t_k), int(bool(rel_dp)), int(ref_index), nat.ptr(refs)))
+        return refs
+
+    def sweeps(self, n_iter, rel_dp=False, ref_index=0):
+        refs = np.zeros((int(n_iter), self.P))
+        nat.check(nat.lib().sdp_family_vi_sweeps(self.h, int(n_iter), int(bool(rel_dp)), int(ref_index), nat.ptr(refs)))
+        return refs
+
+    def until(self, n_max, rel_dp, ref_index, check_every, tol):
+        """(sweeps done [P], [n_checks][P][2] dmin / dmax -- NaN where a member did not run the check --,
+        reference costs [n_max][P])"""
+        schedule = conv.check_schedule(int(n_max), int(check_every))
+        stats = np.full((len(schedule), self.P, 2), np.nan)
+        refs = np.zeros((int(n_max), self.P))
+        n_done = np.zeros(self.P, dtype=np.int32)
+        nat.check(nat.lib().sdp_family_vi_until(self.h, int(n_max), int(bool(rel_dp)), int(ref_index), int(check_every),
+                                                float(tol), nat.ptr(n_done), nat.ptr(stats), nat.ptr(refs)))
+        return n_done, stats, refs
+
+    def get_value(self):
+        J = np.empty((self.P,) + self.shape, dtype=self.dtype)
+        nat.check(nat.lib().sdp_family_get_value(self.h, nat.ptr(J)))
+        return J
+
+    def get_policy(self):
+        pol = np.empty((self.P,) + self.shape + (self.nu,), dtype=self.dtype)
+        idx = np.empty((self.P,) + self.shape, dtype=np.int32)
+        nat.check(nat.lib().sdp_family_get_policy(self.h, nat.ptr(pol), nat.ptr(idx)))
+        return pol, idx
+
+    def last_kernel_ms(self):
+        ms = C.c_double(0.0)
+        nat.check(nat.lib().sdp_family_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+
+def _trace_member(s, t_k=None):
+    """dyn and cost of one member, traced for one call and with EVERY real constant lifted (a family always lifts,
+    also where all members' constants are equal).  A time-dependent system whose callables need a concrete time
+    index (`data[k]`) is traced for the step t_k alone, as DPSolver._trace_now does.  A TracedModel or a TraceError."""
+    sd = s.sys
+    args = (sd.dyn, sd.cost, len(sd.state), len(sd.control), len(sd.perturb), sd.params, sd.stationnary)
+    try:
+        model = trace_model(*args)
+    except TraceError as e:
+        if sd.stationnary or t_k is None:
+            return e
+        try:
+            model = trace_model(*args, t_value=int(t_k))
+        except TraceError:
+            return e
+    model.lift_constants()
+    return model
+
+
+def _structure_message(p, model, first, where=''):
+    """why member p cannot share member 0's code object"""
+    n_p, n_0 = len(model.param_values()), len(first.param_values())
+    ops = lambda m: [n.op for n in m.live_nodes() if n.op != 'const']
+    if n_p != n_0 and ops(model) == ops(first):
+        # the trace shares equal constants (one node for h and for c where h == c): the DAG has another shape
+        few = p if n_p < n_0 else 0
+        return ('member {}{}: constants that coincide in member {} make its traced model another structure ({} distinct '
+                'constants against {}): equal values are one node of the trace.  Give the coinciding constants '
+                'different values, or solve that member alone'.format(p, where, few, min(n_p, n_0), max(n_p, n_0)))
+    return ('member {}{}: the structure of the traced dyn / cost differs from member 0\'s (another expression, another '
+            'np.interp table, or a different time dependence)'.format(p, where))
+
+
+class SolverFamily(object):
+    """P >= 1 DPSolver objects, each set up exactly as for a solo call, solved together (module docstring)."""
+
+    # members are processed in chunks of at most this many bytes of device arrays (a member larger than that runs
+    # alone); every chunk is an independent call, so no cut changes a bit
+    chunk_bytes = DPSolver.horizon_chunk_bytes
+
+    def __init__(self, solvers):
+        solvers = list(solvers)
+        if not solvers:
+            raise ValueError('a family has at least one member')
+        for p, s in enumerate(solvers):
+            if not isinstance(s, DPSolver):
+                raise TypeError('member {} is not a DPSolver'.format(p))
+        # what no family runs (checked for every member before anything else, and before a device is touched)
+        models = []
+        for p, s in enumerate(solvers):
+            if s.comm is not None:
+                raise NotImplementedError('member {} has a communicator: a family runs on one GPU'.format(p))
+            if len(s.sys.perturb) >= 2:
+                raise NotImplementedError('member {} has {} perturbation variables: a family takes one at most'.format(
+                    p, len(s.sys.perturb)))
+            if len(s.state_grid) > 4:
+                raise NotImplementedError('member {} has {} state variables: interpolation stops at 4'.format(
+                    p, len(s.state_grid)))
+            model = _trace_member(s, None if s.sys.stationnary else 0)
+            if isinstance(model, TraceError):
+                raise NotImplementedError('member {}: dyn / cost do not trace ({}): a family runs traced models only'.format(p, model))
+            models.append(model)
+        first = solvers[0]
+        self.dims = first._shape()
+        self.dtype = first.dtype
+        self.nu = len(first.sys.control)
+        self.stationnary = bool(first.sys.stationnary)
+        self.W = self._law_points(first)
+        for p, s in enumerate(solvers[1:], 1):
+            for what, mine, ref in (('dims', s._shape(), self.dims), ('dtype', s.dtype, self.dtype),
+                                    ('number of controls', len(s.sys.control), self.nu),
+                                    ('stationnary flag', bool(s.sys.stationnary), self.stationnary),
+                                    ('number of perturbation points', self._law_points(s), self.W)):
+                if mine != ref:
+                    raise ValueError('member {}: {} {} differs from member 0\'s {}'.format(p, what, mine, ref))
+            if models[p].structure_key() != models[0].structure_key():
+                raise ValueError(_structure_message(p, models[p], models[0]))
+        self.solvers = solvers
+        self.P = len(solvers)
+        self._handle = None                # (key, _FamilyProblem) of a family that runs as one chunk
+        self.last_policy_index = None
+        self.last_convergence = None
+        self.backend_info = {}
+
+    @staticmethod
+    def _law_points(s):
+        return len(s.perturb_grid[0]) if s.sys.perturb else 0
+
+    def __len__(self):
+        return self.P
+
+    # ------------------------------------------------------------------ host side
+    def _tables(self, t_k=None):
+        """Everything the device needs for one call or time step, member-major (no GPU needed): the table of
+        lifted constants, the axes, the laws, the box tables, the lane count and the generated source."""
+        dt = self.dtype
+        box_t = None if self.stationnary else t_k
+        where = '' if t_k is None else ' at step {}'.format(t_k)
+        models, plans = [], []
+        for p, s in enumerate(self.solvers):
+            s._check_supported()
+            model = _trace_member(s, t_k)
+            if isinstance(model, TraceError):
+                raise model
+            if p and model.structure_key() != models[0].structure_key():
+                raise ValueError(_structure_message(p, model, models[0], where))
+            if s._shape() != self.dims or self._law_points(s) != self.W:
+                raise ValueError('member {}: its discretisation changed since the family was made'.format(p))
+            models.append(model)
+            plans.append(s._box_plan(box_t))
+        S = int(np.prod(self.dims))
+        per_node = any(bp['per_node'] for bp in plans)
+        cols = S if per_node else 1
+        wide = lambda a, t: np.ascontiguousarray(np.broadcast_to(a, (self.nu, cols)), dtype=t)
+        tabs = dict(
+            model=models[0], per_node=per_node, lanes=max(bp['lanes'] for bp in plans),
+            prm=np.ascontiguousarray([m.param_values() for m in models], dtype=dt).reshape(self.P, -1),
+            axes=np.ascontiguousarray([np.concatenate([np.asarray(g, dtype=dt) for g in s.state_grid])
+                                       for s in self.solvers], dtype=dt),
+            wgrid=np.ascontiguousarray([s.perturb_grid[0] for s in self.solvers], dtype=dt) if self.W else None,
+            proba=np.ascontiguousarray([s.perturb_proba[0] for s in self.solvers], dtype=dt) if self.W else None,
+            lo=np.stack([wide(bp['lo'], dt) for bp in plans]),
+            hi=np.stack([wide(bp['hi'], dt) for bp in plans]),
+            n=np.stack([wide(bp['n'], np.int32) for bp in plans]),
+            time_specialized=models[0].t_value is not None)
+        tabs['source'] = codegen.family_unit(models[0], dt, tabs['lanes'])
+        return tabs
+
+    def _member_bytes(self, tabs):
+        """bytes of device arrays one member takes: two value arrays, policy, indices, box table, its rows of the
+        small tables"""
+        S = int(np.prod(self.dims))
+        rs = self.dtype.itemsize
+        cols = S if tabs['per_node'] else 1
+        return (S * rs * (2 + self.nu) + S * 4 + self.nu * cols * (2 * rs + 4)
+                + rs * (tabs['axes'].shape[1] + 2 * self.W + tabs['prm'].shape[1]) + 4 + 24)
+
+    def _chunks(self, tabs):
+        """[(first, last), ...]: members whose device arrays take at most chunk_bytes together"""
+        step = max(1, int(self.chunk_bytes) // self._member_bytes(tabs))
+        return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
+
+    def _run(self, tabs, J0, work):
+        """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims"""
+        nat.require_gpu()
+        module = nat.compile_model(tabs['source'])
+        chunks = self._chunks(tabs)
+        digest = hashlib.sha256()
+        for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
+            if tabs[k] is not None:
+                digest.update(tabs[k].tobytes())
+        key = (module, tabs['lanes'], tabs['per_node'], tabs['prm'].shape[1], digest.hexdigest(), tuple(chunks))
+        for first, last in chunks:
+            if self._handle is not None and self._handle[0] == key and len(chunks) == 1:
+                prob = self._handle[1]
+            else:
+                if self._handle is not None:
+                    self._handle[1].close()
+                    self._handle = None
+                prob = _FamilyProblem(tabs, first, last, module, self.dtype, self.dims, self.nu, self.W)
+                if len(chunks) == 1:
+                    self._handle = (key, prob)
+            try:
+                prob.set_params(tabs['prm'][first:last])
+                prob.set_value(J0[first:last])
+                work(prob, first, last)
+            finally:
+                if len(chunks) > 1:        # one chunk's arrays on the device at a time
+                    prob.close()
+        self.backend_info = dict(kernel='family', members=self.P, lanes=tabs['lanes'],
+                                 lifted_constants=int(tabs['prm'].shape[1]), chunks=len(chunks), module=module,
+                                 per_node=tabs['per_node'], time_specialized=tabs['time_specialized'])
+
+    def _start(self, J_next, rel_dp):
+        """the start of every member, [P] + dims in the family's reals, from an array of shape dims or (P,) + dims"""
+        J_next = np.asarray(J_next)
+        if J_next.shape == self.dims:
+            J_next = np.broadcast_to(J_next, (self.P,) + self.dims)
+        elif J_next.shape != (self.P,) + self.dims:
+            raise ValueError('array `J_next` should be of shape {:s} or {:s}, not {:s}'.format(
+                str(self.dims), str((self.P,) + self.dims), str(J_next.shape)))
+        if rel_dp:
+            # the cost-to-go must be a *differential* cost, zero at the reference state, for every member
+            assert np.all(J_next[(slice(None),) + self.solvers[0]._state_ref_ind] == 0.)
+        return np.ascontiguousarray(J_next, dtype=self.dtype)
+
+    def _ref_flat(self, rel_dp):
+        return self.solvers[0]._ref_flat() if rel_dp else 0
+
+    # ------------------------------------------------------------------ the solo methods, stacked
+    def value_iteration(self, J_next, rel_dp=False):
+        """one DP step of every member: `DPSolver.value_iteration` of each, stacked on a new leading axis.
+        J_next: shape dims (the same start for every member) or (P,) + dims; with rel_dp a (J, J_ref) tuple.
+        Returns (J, pol) of shapes (P,) + dims and (P,) + dims + (nu,); J is (J_diff, J_ref [P]) with rel_dp."""
+        if rel_dp:
+            J_next, _ = J_next
+        J0 = self._start(J_next, rel_dp)
+        tabs = self._tables(None)
+        out = self._empty()
+        refs = np.zeros(self.P)
+
+        def work(prob, a, b):
+            refs[a:b] = prob.sweep(0.0, rel_dp, self._ref_flat(rel_dp))
+            out[0][a:b] = prob.get_value()
+            out[1][a:b], out[2][a:b] = prob.get_policy()
+        self._run(tabs, J0, work)
+        self.last_policy_index = out[2]
+        self.last_convergence = None
+        return ((out[0], refs) if rel_dp else out[0]), out[1]
+
+    def _empty(self):
+        return (np.empty((self.P,) + self.dims, dtype=self.dtype),
+                np.empty((self.P,) + self.dims + (self.nu,), dtype=self.dtype),
+                np.empty((self.P,) + self.dims, dtype=np.int32))
+
+    def value_iterations(self, J_next, n_iter, rel_dp=False, J_ref_full=False, tol=None, check_every=1):
+        """`DPSolver.value_iterations` of every member, stacked.  With `tol` a member stops at its own first
+        checked sweep whose span is <= tol and the others go on: member p of the result equals the solo call with
+        n_iter = the sweeps it ran, and last_convergence[p] is the solo record.  With rel_dp J is (J_diff, J_ref),
+        J_ref of shape (P,), or with J_ref_full a list of P arrays (one reference cost per sweep the member ran)."""
+        assert n_iter >= 1
+        if tol is not None:
+            tol, check_every = conv.validate(tol, check_every)
+        self.last_convergence = None
+        if rel_dp:
+            J_next, _ = J_next
+        J0 = self._start(J_next, rel_dp)
+        tabs = self._tables(None)
+        out = self._empty()
+        refs = np.zeros((n_iter, self.P))
+        n_done = np.full(self.P, n_iter, dtype=np.int32)
+        schedule = conv.check_schedule(n_iter, check_every) if tol is not None else []
+        stats = np.full((len(schedule), self.P, 2), np.nan)
+
+        def work(prob, a, b):
+            ref_flat = self._ref_flat(rel_dp)
+            if tol is None:
+                refs[:, a:b] = prob.sweeps(n_iter, rel_dp, ref_flat)
+            else:
+                n_done[a:b], stats[:, a:b], refs[:, a:b] = prob.until(n_iter, rel_dp, ref_flat, check_every, tol)
+            out[0][a:b] = prob.get_value()
+            out[1][a:b], out[2][a:b] = prob.get_policy()
+        self._run(tabs, J0, work)
+        self.last_policy_index = out[2]
+        per_member = [refs[:n_done[p], p].copy() for p in range(self.P)]
+        if tol is not None:
+            records = []
+            for p in range(self.P):
+                checked = [k for k in schedule if k <= n_done[p]]
+                checks = [(k, stats[c, p, 0], stats[c, p, 1]) for c, k in enumerate(checked)]
+                records.append(DPSolver._sweep_record(tol, check_every, int(n_done[p]), checks, per_member[p], rel_dp))
+            self.last_convergence = records
+        if rel_dp:
+            return (out[0], per_member if J_ref_full else np.array([r[-1] for r in per_member])), out[1]
+        return out[0], out[1]
+
+    def bellman_recursion(self, t_fin, J_fin, t_ini=0):
+        """`DPSolver.bellman_recursion` of every member, stacked: (J, pol) of shapes (P, t_fin - t_ini) + dims and
+        (P, t_fin - t_ini) + dims + (nu,).  The time index is stepped here, one family launch per step; a model that
+        looks data up as data[k] is traced per member and step, and step k runs with the constants of that step."""
+        assert t_ini == 0       # t_ini > 0 not tested (as in the reference)
+        T = t_fin - t_ini
+        J = np.zeros((self.P, T) + self.dims)
+        pol = np.zeros((self.P, T) + self.dims + (self.nu,))
+        J_fin = self._start(J_fin, False)
+        idx = np.empty((self.P,) + self.dims, dtype=np.int32)
+        for t_k in range(t_ini, t_fin)[::-1]:
+            k = t_k - t_ini
+            J_next = J_fin if t_k == t_fin - 1 else J[:, k + 1]
+            tabs = self._tables(t_k)
+
+            def work(prob, a, b):
+                prob.sweep(t_k, False, 0)
+                J[a:b, k] = prob.get_value()
+                pol[a:b, k], idx[a:b] = prob.get_policy()
+            self._run(tabs, np.ascontiguousarray(J_next, dtype=self.dtype), work)
+        self.last_policy_index = idx
+        self.last_convergence = None
+        return J, pol
+
+    def last_kernel_ms(self):
+        """HIP-event time of the launches of the last sweep call of a family that runs as one chunk (None otherwise)"""
+        return self._handle[1].last_kernel_ms() if self._handle is not None else None
+
+    def close(self):
+        if self._handle is not None:
+            self._handle[1].close()
+            self._handle = None
