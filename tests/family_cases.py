@@ -17,6 +17,22 @@ chunks          storage_ar1 with P = 5 and chunk_bytes such that it runs as 2 + 
 tol             inventory, P = 3, rel_dp, tol = 1e-6, check_every = 3, n_iter = 200, with constants at which the
                 members need different numbers of sweeps (18, 21, 18 by oracle/vi_numpy.py; those of `inventory` all
                 need 18) and none reaches n_iter.
+
+The cases above are compared with solo 'generic' calls on the device.  Those below (`Case(..., oracle=True)`) reach the
+three ways the kernel maps listed members to XCDs and the second trip of its walk, and are compared with
+oracle/vi_numpy.py alone (`oracle_sweeps`); no solo unit is built for them.  Their members are `line(...)`: 41 controls,
+so 64 lanes and a tile of 4 nodes; member p of every line family is the same problem with the same start whatever P.
+
+line P=..       P in MAPPING_P, 9 nodes (3 tiles, the last ragged): 1..3 members on an XCD (P >= 8), one XCD a member
+                and idle XCDs (5..7), 8 / P XCDs a member, each a part of its tiles (P < 5).
+line P=65       a second block of k_family_pick_ref (64 members a block).
+line strided    P = 17, 515 nodes (129 tiles, the last ragged), 8- and 4-byte reals: 2 * 129 units on the XCDs with two
+                members and 3 * 129 on XCD 0 exceed the cus workgroups an XCD gets (`launch`), so they walk again.
+shrink          16 inventory members, rel_dp, tol = 1e-6, check_every = 1: by the oracle the list runs
+                16 -> 13 -> 6 -> 4 -> 0 (`list_sizes`), through all three mappings, non-contiguous from the first drop.
+chunks P>=8     line P=17 with chunk_bytes such that it runs as 9 + 8.
+line long       P = 2 on 64 * 256 + 129 nodes: k_family_shift and sdp_family_diff_stats launch at most 64 workgroups of 256
+                nodes a member, so the last 129 nodes are a second trip; and each of a member's 4 XCDs walks 1033 tiles.
 """
 import numpy as np
 
@@ -122,9 +138,33 @@ def pv_sized(E_rated, scale, T=6, dt=0.5, loss=0.05):
     return make
 
 
+def line(decay, effort, target, n_x, dtype=np.float64):
+    """one state, one control on 41 lattice points (64 lanes), three lifted constants"""
+    def make():
+        sysd = SysDescription((1, 1, 1), name='line')
+        sysd.dyn = lambda x, u, w: (decay * x + u + w,)
+        sysd.cost = lambda x, u, w: (x - target) * (x - target) + effort * u * u
+        sysd.control_box = lambda x: ((-1., 1.),)
+        sysd.perturb_laws = [NormalLaw(0, 0.1)]
+        s = DPSolver(sysd, dtype=dtype)
+        s.discretize_state(-2, 2, n_x)
+        s.discretize_perturb(-0.3, 0.3, 3)
+        s.control_steps = (0.05,)
+        return s
+    return make
+
+
+def line_members(P, n_x, dtype=np.float64):
+    """member p is the same problem in every line family (no two of its constants coincide up to p = 65)"""
+    return [line(0.5 + 0.005 * p, 1.11 + 0.05 * p, -0.43 + 0.03 * p, n_x, dtype) for p in range(P)]
+
+
 class Case(object):
-    def __init__(self, name, members, horizon=None, dtype=np.float64):
+    """oracle: compared with oracle/vi_numpy.py alone, so unit_sources() emits no solo unit for it"""
+
+    def __init__(self, name, members, horizon=None, dtype=np.float64, oracle=False):
         self.name, self.members, self.horizon, self.dtype = name, list(members), horizon, np.dtype(dtype)
+        self.oracle = oracle
 
     def solvers(self):
         return [make() for make in self.members]
@@ -156,6 +196,25 @@ HORIZON = [
 CHUNKS = Case('chunks', [storage_ar1(*a) for a in AR1_FIVE])
 CASES = STATIONARY + HORIZON + [CHUNKS]
 
+# the cases compared with the oracle
+MAPPING_P = (2, 4, 6, 7, 8, 9, 16, 17)
+LINE_NX, STRIDED_NX = 9, 515
+MAPPING = [Case('line P={}'.format(P), line_members(P, LINE_NX), oracle=True) for P in MAPPING_P]
+MANY = Case('line P=65', line_members(65, LINE_NX), oracle=True)
+STRIDED = [Case('line strided f64', line_members(17, STRIDED_NX), oracle=True),
+           Case('line strided f32', line_members(17, STRIDED_NX, np.float32), dtype=np.float32, oracle=True)]
+CHUNKS_17 = MAPPING[-1]
+LONG_NX = 64 * 256 + 129
+LONG = Case('line long', line_members(2, LONG_NX), oracle=True)
+SHRINK = dict(members=[inventory(*a) for a in (
+    (0.5, 3, 1), (2.0, 3, 1.5), (0.7, 2, 1.5), (0.3, 4, 1.25), (1.5, 2.5, 0.75), (0.25, 5, 2), (3.0, 4, 1.5), (0.6, 6, 1.75),
+    (1.25, 3.5, 0.8), (0.9, 2.2, 1.1), (4.0, 5, 2.5), (0.1, 3, 1.2), (6.0, 8, 2.5), (0.05, 9, 4), (8.0, 9.5, 0.4),
+    (0.02, 1.5, 0.9))], tol=1e-6, check_every=1, n_iter=200)
+SHRINK_SWEEPS = [17, 19, 18, 16, 17, 17, 19, 17, 17, 18, 19, 16, 19, 17, 17, 16]      # by the oracle (test_family_plan.py)
+SHRINK_SIZES = [16, 13, 6, 4, 0]
+SHRINK_CASE = Case('shrink', SHRINK['members'], oracle=True)
+ORACLE_CASES = MAPPING + [MANY] + STRIDED + [SHRINK_CASE, LONG]
+
 
 def start(case, per_member=True):
     """a start array that differs from member to member (or one of shape dims), in the case's reals"""
@@ -166,6 +225,58 @@ def start(case, per_member=True):
     return rng.uniform(0., 2., size=shape).astype(case.dtype)
 
 
+def line_start(case):
+    """(P,) + dims in the case's reals: member p's start depends on p alone, so a line member has one oracle result
+    whatever family it is in"""
+    dims = case.members[0]()._shape()
+    return np.stack([np.random.default_rng(1000 + p).uniform(0., 2., size=dims)
+                     for p in range(len(case.members))]).astype(case.dtype)
+
+
+def launch(S, lanes, n_active, cus):
+    """the host's grid of one family backup, restated (family_backup in csrc/sdp_hip.hip, the head of
+    csrc/sdp_family_kernel.h): tiles per member, XCDs per member, workgroups per XCD, and the units every XCD walks"""
+    tile = (64 // lanes) * 4
+    tiles = -(-S // tile)
+    parts = 1 if n_active >= 8 else 8 // n_active
+    per_part = -(-tiles // parts)
+    per_xcd = max(1, min(-(-n_active // 8) * tiles if n_active >= 8 else per_part, cus))
+    units = []
+    for xcd in range(8):
+        first = xcd // parts
+        mine = (n_active - first + 7) // 8 if first < n_active else 0
+        units.append(mine * per_part)
+    return dict(tiles=tiles, parts=parts, per_xcd=per_xcd, units=units)
+
+
+def list_sizes(sweeps, n_iter):
+    """the distinct lengths of the list of members still running, from the sweeps each member needs"""
+    sizes = [sum(1 for n in sweeps if n > k) for k in range(n_iter + 1)]
+    return [n for i, n in enumerate(sizes) if i == 0 or n != sizes[i - 1]]
+
+
+def oracle_sweeps(make, J0, n_iter, rel_dp=False, tol=None, check_every=1):
+    """oracle/vi_numpy.py's value_iteration_real of one member, iterated: per sweep (J, J_ref or None, pol, idx), and
+    with `tol` the checks [(k, dmin, dmax)] of stodynprog_amd/convergence.py's rule, stopping where it says so"""
+    from oracle import vi_numpy
+    from stodynprog_amd import convergence as conv
+    s = make()
+    spec = vi_numpy.Spec.from_solver(s)
+    J = np.asarray(J0, dtype=s.dtype)
+    out, checks = [], []
+    for k in range(1, n_iter + 1):
+        J_k, pol, idx, _ = vi_numpy.value_iteration_real(spec, (J, 0.) if rel_dp else J, s.dtype, rel_dp)
+        J_k, ref = J_k if rel_dp else (J_k, None)
+        out.append((J_k, ref, pol, idx))
+        if tol is not None and conv.is_check(k, n_iter, check_every):
+            dmin, dmax = conv.diff_stats(J_k, J, s.dtype)
+            checks.append((k, dmin, dmax))
+            if conv.converged(dmin, dmax, tol):
+                break
+        J = J_k
+    return out, checks
+
+
 def chunk_bytes_for(fam, members):
     """a chunk_bytes at which `members` members fit in a chunk and one more does not"""
     per_member = fam._member_bytes(fam._tables())
@@ -174,15 +285,15 @@ def chunk_bytes_for(fam, members):
 
 def unit_sources():
     """the generated source of every family unit the GPU tests run (for the build: they travel compiled), and of
-    the solo 'generic' units they are compared with"""
+    the solo 'generic' units they are compared with (none for the cases compared with the oracle)"""
     from stodynprog_amd import SolverFamily
     out = []
-    for case in CASES + [Case('tol', TOL['members'])]:
+    for case in CASES + [Case('tol', TOL['members'])] + ORACLE_CASES:
         fam = SolverFamily(case.solvers())
         steps = [None] if case.horizon is None else range(case.horizon)
         for t_k in steps:
             out.append(fam._tables(t_k)['source'])
-            for s in fam.solvers:
+            for s in [] if case.oracle else fam.solvers:
                 s.kernel = 'generic'
                 out.append(s._kernel_plan(None if s.sys.stationnary else t_k, s._trace_now(t_k))['source'])
     return out

@@ -16,9 +16,13 @@ like tests/multi_perturb.py; not a test file): models and policies whose transit
   untraceable    the storage model behind a callable the tracer refuses: entries made on the host (from_coo); its
                  traced twin is `storage_ar1`
 
+  long_line      (`long_line(cus)`, not in CASES) one state on cus * 8 * 256 + 129 nodes, a two-point law and steps of a
+                 few nodes: past the launch caps of sdp_transitions, of the stream kernels of the CSR build, of k_push,
+                 of k_push_group<16> once every row is listed, and (8-byte reals) of push_until's k_diff_stats
+
 Policies are smooth functions of the state between bounds given per case, off every lattice: what a user may hand
-to eval_policy.  Every grid is small: the kernels take no other path on a large one (one lane per (node, vertex), a
-grid-stride loop) except where an index overflows, which the size cap excludes."""
+to eval_policy.  The grids of CASES are small: every workgroup of theirs makes one trip through its grid-stride loop;
+`long_line` is the case whose workgroups make a second one."""
 import numpy as np
 
 from stodynprog_amd import SysDescription, DPSolver, models
@@ -160,6 +164,42 @@ def _untraceable():
     return solver
 
 
+def long_line_nodes(cus, per_cu=8):
+    return cus * per_cu * 256 + 129
+
+
+def long_line(cus, per_cu=8):
+    """the Case on long_line_nodes(cus, per_cu) nodes of [0, 1]: x + u + w with |u| <= 1.5 and w = -2.5 or 3.25 node
+    spacings, so rows are short (the lane path) and a vector that starts near the end of the grid stays there for a
+    few pushes.  per_cu = 16: past the caps of the direct kernel's eval_policy and of k_shift (tests/test_gpu_policy_forms.py)"""
+    S = long_line_nodes(cus, per_cu)
+    h = 1.0 / (S - 1)
+
+    def make():
+        s = SysDescription((1, 1, 1), name='long_line')
+        s.dyn = lambda x, u, w: ((x + u) + w,)
+        s.cost = lambda x, u, w: (x - 0.5) * (x - 0.5) + u * w
+        s.control_box = lambda x: ((-1., 1.),)
+        solver = DPSolver(s)
+        solver.discretize_state(0, 1, S)
+        solver.perturb_grid = [np.array([-2.5 * h, 3.25 * h])]
+        solver.perturb_proba = [np.array([0.375, 0.625])]
+        solver.control_steps = (0.5,)
+        return solver
+    return Case('long_line', make, [(-1.5 * h, 1.5 * h)])
+
+
+def long_line_caps(S, nnz, row_lengths, cus, itemsize):
+    """the launches of csrc/sdp_hip.hip a long_line operator goes through, restated: name -> (workgroups wanted for
+    one trip, the cap).  row_lengths: entries per row of P^T."""
+    short = int((row_lengths < 8).sum())
+    listed = int(((row_lengths >= 1) & (row_lengths < 256)).sum())         # set_long_rows(1): the rows of k_push_group<16>
+    vec = 16 // itemsize
+    return {'sdp_transitions': (-(-S * 2 // 256), cus * 8), 'k_iota, k_trans_gather, k_trans_count': (-(-nnz // 256), cus * 8),
+            'k_push': (-(-S // 256) if short else 0, cus * 8), 'k_push_group<16>': (-(-listed // 16), cus * 64),
+            'k_diff_stats': (-(-(S // vec) // 256), cus * 4)}
+
+
 CASES = [
     Case('inventory', lambda: models.inventory()[1], [(0., 10.)]),
     Case('storage_ar1', lambda: models.storage_ar1(n_E=13, n_P=9, n_w=5)[1], [(-4., 4.), (0., 0.)]),
@@ -192,6 +232,8 @@ def unit_sources():
             for kernel in (None, 'generic'):
                 s = case.solver(dt, kernel)
                 out += [plan_of(s, t)['source'] for t in case.times]
+        # long_line as an MI355X's 256 CUs size it (the source does not depend on the number of nodes)
+        out += [plan_of(long_line(256).solver(dt, kernel))['source'] for kernel in (None, 'generic')]
     return list(dict.fromkeys(out))
 
 

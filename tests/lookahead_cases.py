@@ -329,6 +329,48 @@ def start_states(case, solver, B, seed=5):
     return x0
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# batches past the launch caps of sdp_lookahead and sdp_simulate_lookahead (csrc/sdp_hip.hip, restated)
+
+def cap_batch(lanes, cus):
+    """the smallest batch shape past both caps: cus * 8 workgroups of (64 / lanes) * 4 states, and a ragged tile more"""
+    return cus * 8 * (64 // lanes) * 4 + 33
+
+
+def lookahead_grid(B, lanes, cus):
+    """sdp_problem_lookahead launches sweep_blocks(p, B) workgroups: (tiles, workgroups)"""
+    tile = (64 // lanes) * 4
+    tiles = -(-B // tile)
+    return tiles, max(8, -(-min(cus * 8, tiles) // 8) * 8)
+
+
+def lookahead_later_trips(B, lanes, cus):
+    """the rows of a batch that kernel sdp_lookahead reaches after a workgroup's first tile: XCD x walks the x-th
+    contiguous eighth of the tiles with a stride of workgroups / 8"""
+    tile = (64 // lanes) * 4
+    tiles, blocks = lookahead_grid(B, lanes, cus)
+    per_xcd, stride = -(-tiles // 8), blocks // 8
+    rows = []
+    for xcd in range(8):
+        for t in range(xcd * per_xcd + stride, min((xcd + 1) * per_xcd, tiles)):
+            rows += range(t * tile, min((t + 1) * tile, B))
+    return np.array(rows, dtype=np.int64)
+
+
+def simulate_grid(B, lanes, cus):
+    """sdp_problem_simulate_lookahead: (tiles, workgroups); workgroup b takes the tiles b, b + workgroups, .."""
+    tiles = -(-B // ((64 // lanes) * 4))
+    return tiles, min(tiles, cus * 8)
+
+
+def repeated_rows(B, distinct, seed=11):
+    """which of `distinct` inputs every row of a batch of B carries, drawn at random: the definition is a function of a
+    row's own inputs, so its answer on the distinct inputs, gathered, is its answer on the whole batch"""
+    pick = np.random.default_rng(seed).integers(0, distinct, size=B)
+    pick[:distinct] = np.arange(distinct)
+    return pick
+
+
 def unit_source(solver, t_k=None):
     """the generated source of the solver's lookahead unit (no GPU)"""
     from stodynprog_amd import codegen

@@ -95,12 +95,13 @@ def _one_control_per_lane(dtype):
     return _finish(s, dtype, (0, 2, 6), [LAW_3B, LAW_2B], (1.0,))
 
 
-def _full_wave(dtype):
+def _full_wave(dtype, n_x=9):
+    """(n_x: tests/test_gpu_multi_perturb.py also runs it on a grid past the sweep's launch cap; the unit is the same)"""
     s = SysDescription((1, 1, 2), name='full_wave')
     s.dyn = lambda x, u, w1, w2: ((x + u) - w1 + 0.25 * u * w2,)
     s.cost = lambda x, u, w1, w2: (x * x + 0.5 * u * u) + (w2 * u + w1 * x)
     s.control_box = lambda x: ((-1., 1.),)
-    return _finish(s, dtype, (-2, 2, 9), [LAW_3B, LAW_2B], (0.05,))
+    return _finish(s, dtype, (-2, 2, n_x), [LAW_3B, LAW_2B], (0.05,))
 
 
 def _degenerate_callables(second):

@@ -316,3 +316,127 @@ def test_members_of_the_tol_case_need_different_numbers_of_sweeps():
     print('sweeps to tol by the oracle:', counts)
     assert len(set(counts)) > 1 and max(counts) < t['n_iter'], counts
     assert counts[0] == counts[2]                                     # (two identical members)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the cases compared with the oracle (family_cases.ORACLE_CASES): what their table claims
+
+PLANNED = [fc.MAPPING[0], fc.MAPPING[-1], fc.MANY] + fc.STRIDED + [fc.SHRINK_CASE]
+
+
+@pytest.mark.parametrize('case', PLANNED, ids=repr)
+def test_oracle_cases_compile_and_carry_their_members_rows(case, tmp_path):
+    test_unit_compiles_without_scratch_spills_or_lds(case, tmp_path)
+    test_row_p_of_every_table_is_member_p(case)
+
+
+def test_shapes_the_oracle_cases_are_for():
+    units = fc.unit_sources()
+    line_units = {}
+    for case in fc.ORACLE_CASES:
+        fam = SolverFamily(case.solvers())
+        tabs = fam._tables()
+        assert tabs['source'] in units, case                          # the build compiles it ahead
+        if case is fc.SHRINK_CASE:
+            continue
+        S = int(np.prod(fam.dims))
+        # 41 controls: 64 lanes, a tile of 4 nodes; three lifted constants, no two of a member the same
+        assert [int(s._box_table(None)[2].prod()) for s in fam.solvers] == [41] * fam.P
+        assert tabs['lanes'] == 64 and not tabs['per_node'] and tabs['prm'].shape == (fam.P, 3)
+        assert all(len(set(row)) == 3 for row in tabs['prm'].tolist())
+        grid = fc.launch(S, 64, fam.P, 256)
+        assert S % 4 and grid['tiles'] == {fc.LINE_NX: 3, fc.STRIDED_NX: 129, fc.LONG_NX: 4129}[S]      # the last tile is ragged
+        line_units.setdefault(case.dtype, set()).add(tabs['source'])
+    assert {dt: len(u) for dt, u in line_units.items()} == {np.dtype(np.float64): 1, np.dtype(np.float32): 1}
+    # no solo unit for them: every unit of the line model is a family unit
+    for s in (fc.MAPPING[0].solvers()[0], fc.STRIDED[1].solvers()[0]):
+        s.kernel = 'generic'
+        assert s._kernel_plan()['source'] not in units
+    # the mappings: members per XCD at P >= 8, idle XCDs at 5..7, parts of a member's tiles below 5
+    units_of = {P: fc.launch(fc.LINE_NX, 64, P, 256) for P in fc.MAPPING_P + (65,)}
+    assert [units_of[P]['parts'] for P in fc.MAPPING_P] == [4, 2, 1, 1, 1, 1, 1, 1]
+    assert units_of[2]['units'] == [1] * 8 and units_of[4]['units'] == [2] * 8
+    assert units_of[6]['units'] == [3] * 6 + [0] * 2 and units_of[7]['units'] == [3] * 7 + [0]
+    assert units_of[8]['units'] == [3] * 8 and units_of[9]['units'] == [6] + [3] * 7
+    assert units_of[16]['units'] == [6] * 8 and units_of[17]['units'] == [9] + [6] * 7
+    assert units_of[65]['units'] == [27] + [24] * 7
+    assert all(g['per_xcd'] == max(g['units']) for g in units_of.values())       # one trip each
+    # the strided case on 256 CUs: 258 units on the XCDs with two members, 387 on XCD 0, 256 workgroups an XCD
+    grid = fc.launch(fc.STRIDED_NX, 64, 17, 256)
+    assert grid == dict(tiles=129, parts=1, per_xcd=256, units=[387] + [258] * 7)
+    # the long case: four XCDs a member, 1033 tiles each behind 256 workgroups; 65 workgroups of 256 nodes against 64
+    grid = fc.launch(fc.LONG_NX, 64, 2, 256)
+    assert grid == dict(tiles=4129, parts=4, per_xcd=256, units=[1033] * 8) and -(-fc.LONG_NX // 256) == 65
+    # chunks at P >= 8
+    fam = SolverFamily(fc.CHUNKS_17.solvers())
+    fam.chunk_bytes = fc.chunk_bytes_for(fam, 9)
+    assert fam._chunks(fam._tables()) == [(0, 9), (9, 17)]
+
+
+def test_the_host_grid_formula_is_the_one_restated():
+    """family_cases.launch restates family_backup (csrc/sdp_hip.hip); the lines it restates are still there"""
+    with open(os.path.join(codegen.CSRC, 'sdp_hip.hip')) as f:
+        library = f.read()
+    for line in ('const int64_t tile = (64 / f->lanes) * 4;', 'const int parts = n >= 8 ? 1 : 8 / n;',
+                 'int64_t per_xcd = n >= 8 ? (int64_t)((n + 7) / 8) * tiles : (tiles + parts - 1) / parts;',
+                 'if (per_xcd > f->cus) per_xcd = f->cus;'):
+        assert line in library, line
+
+
+def test_the_list_of_the_shrink_case_runs_through_every_mapping():
+    t = fc.SHRINK
+    counts = [len(fc.oracle_sweeps(make, np.zeros(10), t['n_iter'], True, t['tol'], t['check_every'])[0])
+              for make in t['members']]
+    print('sweeps to tol by the oracle:', counts)
+    assert counts == fc.SHRINK_SWEEPS and max(counts) < t['n_iter']
+    sizes = fc.list_sizes(counts, t['n_iter'])
+    assert sizes == fc.SHRINK_SIZES == [16, 13, 6, 4, 0]               # >= 8, >= 8, 5..7, < 5
+    # non-contiguous from the first drop on
+    for k in sorted(set(counts))[:-1]:
+        left = [p for p, n in enumerate(counts) if n > k]
+        assert left != list(range(left[0], left[0] + len(left))), (k, left)
+
+
+def _walk(S, lanes, n_active, cus, stride_factor=1):
+    """the (position in the list, tile) pairs kernel sdp_family_sweep visits, from its index arithmetic restated
+    (csrc/sdp_family_kernel.h) on the grid `fc.launch` gives; stride_factor = 2 is a walk with a wrong stride"""
+    grid = fc.launch(S, lanes, n_active, cus)
+    tiles, parts = grid['tiles'], grid['parts']
+    per_part = -(-tiles // parts)
+    seen = []
+    for block in range(grid['per_xcd'] * 8):
+        xcd = block & 7
+        first, part = xcd // parts, xcd % parts
+        mine = (n_active - first + 7) // 8 if first < n_active else 0
+        for unit in range(block >> 3, mine * per_part, grid['per_xcd'] * stride_factor):
+            tile = part * per_part + unit % per_part
+            if tile < tiles:
+                seen.append((first + 8 * (unit // per_part), tile))
+    return seen
+
+
+def test_the_restated_walk_visits_every_tile_of_every_listed_member_once():
+    """for every list length and grid of the oracle cases -- so the arithmetic the GPU tests restate is the kernel's
+    as long as the kernel's is right -- and a doubled stride misses tiles only where a case is past the cap: the cases
+    that name a second trip are the ones that would notice"""
+    shapes = [(fc.LINE_NX, P) for P in fc.MAPPING_P + (65,)] + [(fc.STRIDED_NX, 17), (fc.LONG_NX, 2)]
+    shapes += [(10, n) for n in fc.SHRINK_SIZES[:-1]]
+    for S, n in shapes:
+        lanes = 16 if S == 10 else 64
+        tiles = fc.launch(S, lanes, n, 256)['tiles']
+        want = sorted((i, t) for i in range(n) for t in range(tiles))
+        assert sorted(_walk(S, lanes, n, 256)) == want, (S, n)
+        missed = set(want) - set(_walk(S, lanes, n, 256, stride_factor=2))
+        assert bool(missed) == (S in (fc.STRIDED_NX, fc.LONG_NX)), (S, n)
+    # the strided case: the second and third member of every XCD lose tiles to the wrong stride (units 256 .. 511), and
+    # the GPU test compares all 17 x 515 nodes
+    all_tiles = {(i, t) for i in range(17) for t in range(129)}
+    assert {i for i, _ in all_tiles - set(_walk(fc.STRIDED_NX, 64, 17, 256, 2))} == set(range(8, 17))
+    with open(os.path.join(codegen.CSRC, 'sdp_family_kernel.h')) as f:
+        kernel = f.read()
+    for line in ('const int parts = a.n_active >= 8 ? 1 : 8 / max(a.n_active, 1);', 'const int first = xcd / parts;',
+                 'const int part = xcd % parts;', 'const int mine = first < a.n_active ? (a.n_active - first + 7) / 8 : 0;',
+                 'const int64_t per_part = (tiles + parts - 1) / parts;', 'const int64_t stride = gridDim.x >> 3;',
+                 'const int64_t tile = (int64_t)part * per_part + unit % per_part;',
+                 'const int64_t p = members[first + 8 * (int)(unit / per_part)];'):
+        assert line in kernel, line

@@ -111,3 +111,25 @@ def test_a_policy_of_the_wrong_shape_is_refused():
             s.transition_operator(bad)
         with pytest.raises(ValueError):
             forward.entries(s, bad)
+
+
+@pytest.mark.parametrize('dtkey', sorted(fc.DTYPES))
+def test_long_line_is_past_the_launch_caps_of_256_compute_units(dtkey):
+    """what tests/test_gpu_forward.py asserts with the chip's own count, on the MI355X's: every launch of the build and
+    of a push makes a second trip, push_until's statistics with 8-byte reals; and the unit travels with the build"""
+    dt = np.dtype(fc.DTYPES[dtkey])
+    case = fc.long_line(256)
+    s = case.solver(dt.type)
+    plan = fc.plan_of(s)
+    assert plan['source'] in fc.unit_sources()
+    assert plan['source'] == fc.plan_of(fc.long_line(64).solver(dt.type))['source']      # (whatever the chip)
+    e = forward.entries(s, case.policy(s))
+    assert (e.S, e.W, e.V) == (524417, 2, 2) and len(e.val) == 4 * e.S
+    indptr, _, _ = forward.csr(e.S, e.tgt, e.src, e.val)
+    lengths = np.diff(indptr)
+    assert 3 <= lengths.min() and lengths.max() < 256 and (lengths < 8).sum() > e.S - 8
+    caps = fc.long_line_caps(e.S, len(e.val), lengths, 256, dt.itemsize)
+    assert caps['sdp_transitions'] == (4098, 2048) and caps['k_iota, k_trans_gather, k_trans_count'] == (8195, 2048)
+    assert caps['k_push'] == (2049, 2048) and caps['k_push_group<16>'] == (32777, 16384)
+    assert caps['k_diff_stats'] == ((1025, 1024) if dt.itemsize == 8 else (513, 1024))
+    assert forward.operator_bytes(len(e.val), e.S, dt.itemsize) < 64 << 20

@@ -248,3 +248,79 @@ def test_from_coo_refuses_indices_outside_the_grid(gpu):
     assert lib.sdp_transop_from_coo(0, 5, 2, gpu.ptr(t), gpu.ptr(s_), gpu.ptr(val), C.byref(h)) == -1       # SDP_EINVAL
     assert b'entry 1: target 7' in lib.sdp_last_error() and not h.value
     assert lib.sdp_transop_push(None, None, 1) == -1
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# past the launch caps: forward_cases.long_line, sized from the chip's compute units.  The whole grid is compared
+# (the definition takes well under a second at this size): every entry, every row pointer, the mean cost; the pushes
+# and the stationary iteration against forward.py's sequential sums over those verified entries
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('dtkey', sorted(fc.DTYPES))
+def test_operator_and_pushes_past_the_launch_caps(gpu, dtkey):
+    dt = np.dtype(fc.DTYPES[dtkey])
+    cus = gpu.device_info(0)['compute_units']
+    case = fc.long_line(cus)
+    s = case.solver(dt.type)
+    pol = case.policy(s)
+    e = forward.entries(s, pol)
+    csr = forward.csr(e.S, e.tgt, e.src, e.val)
+    lengths = np.diff(csr[0])
+    assert e.S == cus * 8 * 256 + 129 and e.W == 2 and e.V == 2
+    caps = fc.long_line_caps(e.S, len(e.val), lengths, cus, dt.itemsize)
+    print(caps)
+    for name, (wanted, cap) in caps.items():
+        # (k_diff_stats reads 16 bytes a lane: with 4-byte reals its cap is cus * 4096 nodes, and this grid is below it)
+        if name != 'k_diff_stats' or dt.itemsize == 8:
+            assert wanted > cap, (name, wanted, cap)
+    assert lengths.max() < 256                               # (no row of k_push_group<64>)
+    second = cus * 8 * 256                                   # the first row of k_push's second trip
+    tail = np.zeros(e.S, dtype=dt)
+    tail[e.S - 60] = 1.0                                     # what it becomes stays in the rows of the second trips
+    vectors = {'random': np.random.default_rng(5).standard_normal(e.S).astype(dt), 'tail': tail}
+    op = s.transition_operator(pol)
+    try:
+        assert op.path == 'device'
+        _assert_operator(op, e, csr, 'long_line ' + dtkey)
+        assert fc.same(op.mean_cost.ravel(), e.mean_cost)
+        want = {(name, n): forward.push(csr, mu, n) for name, mu in vectors.items() for n in (1, 2)}
+        assert np.flatnonzero(want['tail', 2]).min() >= second and np.count_nonzero(want['random', 2][second:]) > 100
+        for long_from in (None, 1):                          # as built (rows of 8 entries on a group); every row on a group
+            if long_from is not None:
+                op.set_long_rows(long_from)
+            for (name, n), w in want.items():
+                assert fc.same(op.push(vectors[name], n), w), (name, n, long_from)
+        op.set_long_rows(8)
+        for kw in (dict(tol=0.0, n_max=2, check_every=1), dict(tol=0.3, n_max=3, check_every=1)):
+            w = forward.stationary(csr, e.mean_cost, mu0=tail, **kw)
+            got = op.stationary(mu0=tail, **kw)
+            assert w.delta > 0 and got.delta == w.delta, (kw, got.delta, w.delta)      # the largest change is in the tail
+            assert got.n_done == w.n_done and got.converged == w.converged and fc.same(got.mu.ravel(), w.mu), kw
+    finally:
+        op.close()
+
+
+def test_from_coo_wide_rows_past_the_launch_cap(gpu):
+    """k_push_group<64>, one wave a row of 256 entries or more, capped at cus * 64 workgroups of 4 waves: cus * 256 + 129
+    rows of exactly 256 entries in a shuffled emission order.  4-byte reals: tgt, src and val take 12 bytes an entry,
+    201 MB on 256 CUs; with 8-byte reals they would take 268 MB, over the 256 MiB a test here may use, so that
+    instantiation is not reached."""
+    dt = np.float32
+    cus = gpu.device_info(0)['compute_units']
+    S = cus * 256 + 129
+    n = S * 256
+    assert -(-S // 4) > cus * 64 and n * 12 < 256 << 20                 # past the cap of k_push_group<64>; the arrays' size
+    rng = np.random.default_rng(64)
+    tgt = rng.permutation(np.repeat(np.arange(S, dtype=np.int32), 256))
+    src = rng.integers(0, S, size=n, dtype=np.int32)
+    val = rng.standard_normal(n, dtype=dt)
+    mu = rng.standard_normal(S, dtype=dt)
+    want = np.zeros(S, dtype=dt)
+    np.add.at(want, tgt, val * mu[src])                                  # per row in emission order: the stable sort's
+    op = TransitionOperator.from_coo((S,), tgt, src, val)
+    try:
+        indptr, indices, data = op.tocsr()
+        assert np.array_equal(indptr, np.arange(S + 1, dtype=np.int64) * 256)
+        assert fc.same(op.push(mu), want)                               # (the order within a row decides the roundings)
+        assert np.count_nonzero(want[cus * 256:]) == 129                # (the rows of the second trip)
+    finally:
+        op.close()

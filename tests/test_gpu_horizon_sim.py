@@ -270,3 +270,32 @@ def test_equal_slices_give_the_stationary_call(gpu):
             assert np.array_equal(a.n_outside, b.n_outside) and np.array_equal(a.occupancy, b.occupancy)
         finally:
             _close(s)
+
+
+@pytest.mark.timeout(600)
+def test_monte_carlo_past_the_launch_cap(gpu):
+    """sdp_problem_montecarlo_h caps the grid at cus * per_cu workgroups of 256 trajectories, per_cu <= 8 from the
+    kernel's occupancy: cus * 8 * 256 + 333 trajectories are past it whatever the occupancy.  Every trajectory's sums
+    against the oracle chained on the replayed draws (the twin of test_gpu_montecarlo.test_batch_past_the_grid_cap)"""
+    cus = int(nat.device_info(0)['compute_units'])
+    cap = cus * 8 * 256
+    B, T = cap + 333, 3
+    assert -(-B // 256) > cus * 8
+    s = hc.storage()
+    spec = hs.spec_of(s)
+    rng = np.random.default_rng(12)
+    pol = hs.policies(s, 'smooth', T)
+    x0 = _starts(s, B, rng)
+    try:
+        res = _quiet(s.monte_carlo, pol, x0, T, seed=17, n_burn=1, occupancy=True, traj_offset=40)
+        assert res.path == 'device' and s.backend_info['horizon_path'] == 'device'
+        _, w = s.monte_carlo_draws(17, B, T, traj_offset=40)
+        x, _, g = hs.simulate_indexed(spec, pol, x0, w, T, 0, s.dtype)
+        _same_mc(res, _reduce(s, x, g, 1, False), 'B = {}'.format(B))
+        # the occupancy: every counted state once, and the second trip's own against the oracle's
+        assert res.occupancy.dtype == np.int64 and int(res.occupancy.sum()) == B * (T - 1)
+        first = _quiet(s.monte_carlo, pol, x0[:cap], T, seed=17, n_burn=1, occupancy=True, traj_offset=40)
+        assert np.array_equal(res.occupancy - first.occupancy, _reduce(s, x[:, cap:], g[:, cap:], 1, True)[3])
+        assert len(np.unique(res.cost_sum[cap:])) > 300                  # (the trajectories of the second trip differ)
+    finally:
+        _close(s)

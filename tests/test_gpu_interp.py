@@ -161,3 +161,22 @@ def test_power_of_two_spans_multiply_by_the_reciprocal_bit_exactly(gpu):
                 out = multilinear_interpolation(smin, smax, orders, values, s)
                 ref = c_oracle.mlinterp(smin, smax, orders, values, s)
             assert np.array_equal(out, ref, equal_nan=True), (dt, lo, span)
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_more_points_than_the_launch_cap(gpu, dtype):
+    """launch_mlinterp caps the grid at cus * 16 workgroups of 256 points: 129 points more than that, so the last
+    points are reached on a second trip; every point against the C oracle"""
+    cus = gpu.device_info(0)['compute_units']
+    n = cus * 16 * 256 + 129
+    assert -(-n // 256) > cus * 16
+    rng = np.random.default_rng(7)
+    orders = np.array([50, 51], dtype=np.int64)
+    smin = rng.uniform(-1, 0, 2).astype(dtype)
+    smax = (smin + rng.uniform(1, 2, 2)).astype(dtype)
+    values = rng.standard_normal((2, int(np.prod(orders)))).astype(dtype)
+    s = np.vstack([rng.uniform(smin[k] - 0.2, smax[k] + 0.2, n) for k in range(2)]).astype(dtype)
+    out = multilinear_interpolation(smin, smax, orders, values, np.ascontiguousarray(s))
+    ref = c_oracle.mlinterp(smin, smax, orders, values, s)
+    assert out.dtype == ref.dtype and np.array_equal(out, ref)
+    assert len(np.unique(out[:, cus * 16 * 256:])) > 200                 # (the points of the second trip)

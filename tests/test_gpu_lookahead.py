@@ -199,3 +199,84 @@ def test_cutting_a_time_indexed_cost_to_go_changes_no_bit(name):
             assert same(a, b), (name, steps, what)
     with pytest.raises(ValueError):
         s.simulate_lookahead(J_all, x0, w, n_steps=T, t0=3)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# batches past the launch caps: the rows a workgroup reaches after its first tile.  The whole batch against the numpy
+# definition (stodynprog_amd/lookahead.py), the later trips also against the oracle; a chip on which the shape is not
+# past the cap fails the assertion on the grid
+
+DISTINCT = 2039
+
+
+def _cus():
+    from stodynprog_amd import _native as nat
+    return nat.device_info(0)['compute_units']
+
+
+def test_lookahead_past_the_grid_cap_with_64_lanes():
+    from stodynprog_amd import lookahead as la
+    case = lc.BY_NAME['lanes 64']
+    s = case.solver()
+    cus = _cus()
+    B = cus * 8 * 4 + 33
+    assert B == lc.cap_batch(64, cus)
+    tiles, blocks = lc.lookahead_grid(B, 64, cus)
+    later = lc.lookahead_later_trips(B, 64, cus)
+    assert tiles > blocks == cus * 8 and len(later) >= 7 * 4, (tiles, blocks)       # every XCD but the last walks again
+    J_next = lc.cost_to_go(s)
+    X = lc.start_states(case, s, B)                                       # (every row another state)
+    got = s.lookahead(J_next, X)
+    assert s.backend_info['lookahead_path'] == 'device' and s.backend_info['lookahead_box'] == 'device'
+    check(got, la.lookahead(s, J_next, X), 'the definition, every row')
+    assert len(np.unique(got[2])) > 8
+    rows = np.concatenate([later, np.arange(B - 40, B)])
+    check(tuple(a[rows] for a in got), lc.oracle_lookahead(s, lc.spec_of(case, s), J_next, X[rows]), 'the oracle, later trips')
+
+
+def test_lookahead_past_the_grid_cap_with_8_lanes():
+    from stodynprog_amd import lookahead as la
+    case = lc.BY_NAME['lanes 8']
+    s = case.solver()
+    cus = _cus()
+    B = cus * 8 * 32 + 33
+    assert B == lc.cap_batch(8, cus)
+    tiles, blocks = lc.lookahead_grid(B, 8, cus)
+    later = lc.lookahead_later_trips(B, 8, cus)
+    assert tiles > blocks == cus * 8 and len(later) >= 32, (tiles, blocks)
+    J_next = lc.cost_to_go(s)
+    pick = lc.repeated_rows(B, DISTINCT)
+    base = lc.start_states(case, s, DISTINCT)
+    X = base[pick]
+    got = s.lookahead(J_next, X)
+    assert s.backend_info['lookahead_path'] == 'device' and s.backend_info['lookahead_box'] == 'device'
+    check(got, tuple(a[pick] for a in la.lookahead(s, J_next, base)), 'the definition, every row')
+    assert len(np.unique(got[2])) > 1
+    rows = np.concatenate([later, np.arange(B - 40, B)])
+    check(tuple(a[rows] for a in got), lc.oracle_lookahead(s, lc.spec_of(case, s), J_next, X[rows]), 'the oracle, later trips')
+
+
+def test_closed_loop_past_the_grid_cap_with_8_lanes():
+    from stodynprog_amd import lookahead as la
+    case = lc.BY_NAME['lanes 8']
+    s = case.solver()
+    cus = _cus()
+    T = 3
+    B = cus * 8 * 32 + 33
+    tiles, blocks = lc.simulate_grid(B, 8, cus)
+    assert tiles > blocks == cus * 8, (tiles, blocks)                     # the tiles from `blocks` on: a second trip
+    tail = blocks * 32 - 7
+    J_next = lc.cost_to_go(s)
+    pick = lc.repeated_rows(B, DISTINCT)
+    base = lc.start_states(case, s, DISTINCT)
+    w_base, _ = lc.draws(s, T, DISTINCT)
+    x0, w = base[pick], np.ascontiguousarray(w_base[:, pick])
+    got = s.simulate_lookahead(J_next, x0, w, n_steps=T)
+    assert s.backend_info['lookahead_path'] == 'device'
+    want = la.simulate_lookahead(s, J_next, base, w_base[:, None, :], T)
+    for a, b, what in zip(got, want, 'xugq'):
+        assert a.dtype == s.dtype and same(a, b[:, pick]), ('the definition', what)
+    oracle = lc.oracle_closed_loop(s, lc.spec_of(case, s), J_next, x0[tail:], w[:, tail:], T)
+    for a, b, what in zip(got, oracle, 'xugq'):
+        assert same(a[:, tail:], b), ('the chained oracle, second trip', what)
+    assert len(np.unique(got[0][-1])) > DISTINCT // 2                     # (the trajectories do differ)

@@ -443,3 +443,30 @@ def test_untraceable_model_runs_the_same_definition(gpu):
         assert np.array_equal(host.n_outside, dev.n_outside) and np.array_equal(host.occupancy, dev.occupancy)
     finally:
         _close(ref)
+
+
+def test_a_sweep_past_the_grid_cap(gpu):
+    """`full_wave` (64 lanes, 4 nodes a workgroup) on cus * 8 * 4 + 129 nodes: sweep_blocks caps the grid at cus * 8
+    workgroups, XCD x walks the x-th eighth of the tiles with a stride of cus, so seven XCDs walk twice.  The nodes of
+    the later trips, the last 129 and a sample against the oracle on the flat law"""
+    import lookahead_cases as lc                 # (the walk of sdp_lookahead is this kernel's: lookahead_later_trips)
+    cus = gpu.device_info(0)['compute_units']
+    n_x = cus * 8 * 4 + 129
+    tiles, blocks = lc.lookahead_grid(n_x, 64, cus)
+    later = lc.lookahead_later_trips(n_x, 64, cus)
+    assert tiles > blocks == cus * 8 and len(later) >= 7 * 4, (tiles, blocks)
+    solver = mp._full_wave(np.float64, n_x)
+    V = np.random.default_rng(21).standard_normal(n_x)
+    nodes = np.unique(np.concatenate([later, np.arange(n_x - 129, n_x), np.random.default_rng(22).choice(n_x, 300, replace=False)]))
+    try:
+        J, pol = _quiet(solver.value_iteration, V, report_time=False)
+        info = solver.backend_info
+        assert info['kernel'] == 'generic' and info['perturb_vars'] == 2 and info['lanes_per_node'] == 64
+        with np.errstate(all='ignore'):
+            Jo, polo, idxo, _ = vi_numpy.value_iteration(mp.flat_spec(solver), V, nodes=nodes)
+        _same(J[nodes], Jo, 'J')
+        _same(pol[nodes], polo, 'policy values')
+        _same(solver.last_policy_index[nodes], idxo.astype(np.int32), 'policy index')
+        assert len(np.unique(idxo)) > 8
+    finally:
+        _close(solver)

@@ -171,3 +171,54 @@ def test_policy_iteration_matches_the_direct_kernel(gpu, family):
                 assert np.array_equal(x, y), (family, rel_dp, 'J')
     finally:
         _close(s, gen)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the direct kernel's eval_policy, k_shift and k_diff_stats past their launch caps
+
+def past_the_caps_start(S, dtype):
+    """a standard-normal start, zero at the reference node, with two spikes among the last 129 nodes: the extremes of
+    J_2 - J_1 then lie where only the last trip of k_diff_stats' loop reads"""
+    V = np.random.default_rng(3).standard_normal(S)
+    V[S // 2] = 0.
+    V[S - 50], V[S - 90] = 1e3, -1e3
+    return V.astype(dtype)
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32], ids=['f64', 'f32'])
+def test_direct_kernel_evaluates_a_policy_past_its_launch_caps(gpu, dtype):
+    """one state on cus * 16 * 256 + 129 nodes (forward_cases.long_line), kernel = 'generic', rel_dp, two sweeps with a
+    tolerance nobody meets: both sweeps and their reference costs against the oracle on every node, the statistics
+    against convergence.diff_stats of the downloaded arrays"""
+    import forward_cases as fwd
+    from stodynprog_amd import convergence as conv
+    dt = np.dtype(dtype)
+    cus = gpu.device_info(0)['compute_units']
+    case = fwd.long_line(cus, 16)
+    s = case.solver(dtype, 'generic')
+    S = s._shape()[0]
+    last = S - 129                                                        # the first node of every kernel's last trip
+    vec = 16 // dt.itemsize
+    assert S == cus * 16 * 256 + 129 and s._state_ref_ind == (S // 2,)
+    assert -(-S // 256) > cus * 16 and last == cus * 16 * 256                              # sdp_evalpol and k_shift: 256 nodes a workgroup
+    assert -(-(S // vec) // 256) > cus * 4 and last % (cus * 4 * 256 * vec) == 0           # k_diff_stats: 16 bytes a lane
+    pol = case.policy(s)
+    V = past_the_caps_start(S, dtype)
+    spec = vi_numpy.Spec.from_solver(s)
+    with np.errstate(all='ignore'):
+        J1o, ref1o = vi_numpy.eval_policy(spec, pol, 1, True, V, True, dtype=dtype)
+        J2o, ref2o = vi_numpy.eval_policy(spec, pol, 2, True, V, True, dtype=dtype)
+    d = J2o.astype(float) - J1o.astype(float)
+    assert min(d.argmax(), d.argmin()) >= last
+    try:
+        J1, ref1 = _quiet(s.eval_policy, pol, 1, True, V, report_time=False, J_ref_full=True)
+        assert s.backend_info['kernel'] == 'generic'
+        J2, ref2 = _quiet(s.eval_policy, pol, 2, True, V, report_time=False, J_ref_full=True, tol=0.0, check_every=1)
+        rec = s.last_convergence
+        assert J1.dtype == dt and np.array_equal(J1, J1o) and np.array_equal(np.atleast_1d(ref1), ref1o)
+        assert J2.dtype == dt and np.array_equal(J2, J2o) and np.array_equal(np.atleast_1d(ref2), ref2o)
+        assert rec.n_iter == 2 and rec.checked == [1, 2] and not rec.converged
+        assert (rec.dmin[0], rec.dmax[0]) == conv.diff_stats(J1, V, dt)
+        assert (rec.dmin[1], rec.dmax[1]) == conv.diff_stats(J2, J1, dt)
+    finally:
+        _close(s)

@@ -175,3 +175,25 @@ def test_staged_minimal_axes(gpu):
         return sysd, s
     a, b = _both(make)
     _same(a, b)
+
+
+def test_staged_kernel_past_its_launch_cap(gpu):
+    """launch_sweep gives the staged kernel at most cus * 4 workgroups, which stride over the tiles of 8 x 8 x 8 nodes:
+    the coupled model on the smallest cube with more tiles than that (ragged: 3 nodes short of whole tiles), against
+    the direct kernel on every node and against the numpy oracle on sampled nodes"""
+    from oracle import vi_numpy
+    from stodynprog_amd import _native as nat
+    cus = nat.device_info(0)['compute_units']
+    m = 1
+    while m ** 3 <= cus * 4:
+        m += 1
+    N = 8 * m - 3
+    a, b = _both(lambda: models.synthetic3d_coupled(N=N), V0=models.synthetic3d_V0(models.synthetic3d_coupled(N=N)[1].state_grid))
+    assert b[3].backend_info['staged']['tile'] == (8, 8, 8) and -(-N // 8) ** 3 > cus * 4
+    _same(a, b)
+    s = b[3]
+    V0 = models.synthetic3d_V0(s.state_grid)
+    nodes = np.sort(np.random.default_rng(1).choice(V0.size, 400, replace=False))
+    Jo, polo, idxo, _ = vi_numpy.value_iteration(vi_numpy.Spec.from_solver(s), V0, nodes=nodes)
+    assert np.array_equal(b[0].ravel()[nodes], Jo) and np.array_equal(b[2].ravel()[nodes], idxo)
+    assert np.array_equal(b[1].reshape(-1, 1)[nodes], polo)

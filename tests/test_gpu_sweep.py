@@ -1353,3 +1353,40 @@ def test_host_array_path_again_and_again_in_the_state_the_suite_left(gpu, monkey
         return models.synthetic3d(N=144)
     for k in range(24):
         _host_path_pair(ar1 if k % 3 else f64, monkeypatch)
+
+
+def test_tabulated_mode_past_its_launch_caps(gpu):
+    """sdp_tab_backup runs k_tab_cells on at most cus * 16 workgroups of 256 lattice cells and k_tab_reduce on at most
+    cus * 8 workgroups of 4 nodes: an untraceable one-state model on cus * 8 * 4 + 129 nodes with 51 controls and 3
+    perturbation points (one call: fewer cells than _backup_tabulated's chunk) is past both.  The nodes whose cells or
+    whose wave come on a second trip, and a sample, against the numpy oracle"""
+    from stodynprog_amd.models import NormalLaw
+    cus = gpu.device_info(0)['compute_units']
+    n_x = cus * 8 * 4 + 129
+    cells = 51 * 3
+    assert -(-n_x * cells // 256) > cus * 16 and -(-n_x // 4) > cus * 8 and n_x * cells < 4_000_000
+    sysd = SysDescription((1, 1, 1), name='untraceable line')
+
+    def dyn(x, u, w):
+        shape = np.shape(u)                         # needs a concrete array
+        return (0.6 * x + np.asarray(u).reshape(shape) + w,)
+    sysd.dyn = dyn
+    sysd.cost = lambda x, u, w: (x + 0.4) * (x + 0.4) + 1.3 * u * u
+    sysd.control_box = lambda x: ((-1., 1.),)
+    sysd.perturb_laws = [NormalLaw(0, 0.1)]
+    solver = DPSolver(sysd)
+    solver.discretize_state(-2, 2, n_x)
+    solver.discretize_perturb(-0.3, 0.3, 3)
+    solver.control_steps = (0.04,)
+    assert isinstance(solver._traced(), TraceError)
+    assert solver.control_grids((0.,), None)[1] == (51,)
+    V = np.random.default_rng(4).standard_normal(n_x)
+    J, u = solver.value_iteration(V, report_time=False)
+    assert solver.backend_info['mode'] == 'tabulated'
+    first = cus * 16 * 256 // cells                                  # the node of the first cell of k_tab_cells' second trip
+    assert first < cus * 8 * 4 < n_x
+    nodes = np.unique(np.concatenate([np.arange(first, n_x, 5), np.arange(cus * 8 * 4, n_x),
+                                      np.random.default_rng(5).choice(n_x, 200, replace=False)]))
+    Jo, po, io, _ = vi_numpy.value_iteration(vi_numpy.Spec.from_solver(solver), V, nodes=nodes)
+    assert np.array_equal(J[nodes], Jo) and np.array_equal(u[nodes], po) and np.array_equal(solver.last_policy_index[nodes], io)
+    assert len(np.unique(io)) > 8
