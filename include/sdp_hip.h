@@ -473,6 +473,40 @@ int sdp_family_get_policy(sdp_family *f, void *host_pol, int32_t *host_idx);
 /* HIP-event duration of the launches of the last sweep call (all its sweeps), milliseconds. */
 int sdp_family_last_kernel_ms(sdp_family *f, double *ms);
 
+/*
+ * Policy evaluation of a family (csrc/sdp_family_policy_kernel.h).  The family's EVALUATION unit
+ * (codegen.family_policy_unit: kernels sdp_family_evalpol and sdp_family_evalpol_resident) is loaded beside the
+ * sweep unit; its sdp_meta is checked.  Member p of every result has the bits of sdp_problem_eval_policy /
+ * sdp_problem_eval_policy_until on problem p alone; a time-dependent system is evaluated at time index 0.
+ */
+int sdp_family_load_policy_unit(sdp_family *f, const char *module_path);
+/* The prescribed policy of every member, [P][S][nu] reals in C order (its buffer is allocated at the first call). */
+int sdp_family_set_policy(sdp_family *f, const void *host_pol);
+/* The policy the last sweep wrote becomes the prescribed one without a copy: the two buffers swap. */
+int sdp_family_take_policy(sdp_family *f);
+/* same[P]: 1 where the policy of the last sweep equals the prescribed one value by value (a NaN equals nothing).
+ * One launch, P words read back. */
+int sdp_family_compare_policy(sdp_family *f, int32_t *same);
+/* The members the launches that follow run: n distinct indices.  sdp_family_set_value lists all of them again. */
+int sdp_family_set_members(sdp_family *f, const int32_t *members, int32_t n);
+/* The two forms of an evaluation: a launch per step, any grid size; or all steps of a member in one workgroup with
+ * its values in LDS (a member of more nodes than the unit's two LDS buffers hold is refused with SDP_EINVAL). */
+#define SDP_FAMILY_EVAL_STEPS 0
+#define SDP_FAMILY_EVAL_RESIDENT 1
+/* n_iter steps of the listed members from the values set, under the prescribed policy.  rel_dp: the relative
+ * algorithm, the reference cost of every step in J_ref_out [n_iter][P]. */
+int sdp_family_eval_policy(sdp_family *f, int32_t n_iter, int rel_dp, int64_t ref_index, int32_t form,
+                           double *J_ref_out);
+/*
+ * At most n_max steps with the check of sdp_problem_eval_policy_until per member (the statistics of the shifted
+ * sequence), in the shape of sdp_family_vi_until: n_done[P], stats [n_checks][P][2], J_ref_out [n_max][P]; only
+ * the entries of listed members are written.  Steps form: one reduction launch and 24 bytes a listed member read
+ * back per checked step, converged members leave the list.  Resident form: the checks run inside the kernel and
+ * everything is read back once at the end.
+ */
+int sdp_family_eval_policy_until(sdp_family *f, int32_t n_max, int rel_dp, int64_t ref_index, int32_t check_every,
+                                 double tol, int32_t form, int32_t *n_done, double *stats, double *J_ref_out);
+
 /* ---- tabulated backup (models that cannot be traced into device code) ------- */
 /*
  * Replaces the numeric part of DPSolver._value_at_state_vect

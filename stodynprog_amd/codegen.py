@@ -773,6 +773,38 @@ def family_unit(model, dtype, lanes):
     return '\n'.join(head)
 
 
+# the resident evaluation kernel of a family (csrc/sdp_family_policy_kernel.h: SDP_FPOL_THREADS, SDP_FPOL_LDS_BYTES,
+# SDP_FPOL_RED_BYTES): its workgroup, its LDS budget -- the whole LDS of a CU -- and what of it the reduction takes
+FAMILY_RESIDENT_THREADS = 1024
+FAMILY_RESIDENT_LDS_BYTES = 160 * 1024
+FAMILY_RESIDENT_REDUCTION_BYTES = 512
+
+
+def family_resident_nodes(dtype):
+    """the fit rule of kernel sdp_family_evalpol_resident: a member is resident when two buffers of S reals, plus
+    what the reduction needs, fit the LDS budget the kernel is built for.  The largest such S."""
+    return (FAMILY_RESIDENT_LDS_BYTES - FAMILY_RESIDENT_REDUCTION_BYTES) // (2 * np.dtype(dtype).itemsize)
+
+
+def family_policy_unit(model, dtype):
+    """The generated source of a family EVALUATION unit (csrc/sdp_family_policy_kernel.h, kernels
+    `sdp_family_evalpol` and `sdp_family_evalpol_resident`): the direct prologue of a model with lifted constants,
+    marked SDP_FAMILY and SDP_FAMILY_POLICY, and the evaluation header in the place of sdp_sweep_kernel.h.  A
+    fixed-policy backup has no control lattice, so there is one unit per model structure and real type (the lane
+    count the prologue prints is 1 and nothing reads it)."""
+    if model.param_index is None:
+        raise ValueError('a family unit takes a model with lifted constants (TracedModel.lift_constants)')
+    if model.n_perturb >= 2:
+        raise NotImplementedError('a family unit takes one perturbation variable at most')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, 1, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
+    head.insert(at + 1, '#define SDP_FAMILY_POLICY 1   // .. and the two evaluation kernels in the place of sdp_family_sweep')
+    head += ['#include "sdp_family_policy_kernel.h"    // brings in sdp_family_kernel.h', '']
+    return '\n'.join(head)
+
+
 def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False, lookahead=None):
     """The generated source of one model code object.  `family`: what the unit is to hold beside the direct node-order
     kernels of csrc/sdp_sweep_kernel.h --
@@ -1472,6 +1504,9 @@ def source_key(source):
             h.update(f.read())
     if '#define SDP_FAMILY ' in source:
         with open(os.path.join(CSRC, 'sdp_family_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_FAMILY_POLICY ' in source:
+        with open(os.path.join(CSRC, 'sdp_family_policy_kernel.h'), 'rb') as f:
             h.update(f.read())
     h.update(source.encode())
     h.update(' '.join(HIPCC_FLAGS[:-1]).encode())

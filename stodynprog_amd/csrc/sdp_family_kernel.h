@@ -116,6 +116,8 @@ SDP_DEV sdp_real sdp_family_expected_cost(const SdpFamilyArgs &a, const SdpMembe
 #endif
 }
 
+#if !defined(SDP_FAMILY_POLICY)
+// (an evaluation unit, sdp_family_policy_kernel.h, takes SdpMember and the helpers above and brings its own kernels)
 extern "C" __global__ void __launch_bounds__(256) sdp_family_sweep(SdpFamilyArgs a)
 {
     constexpr int L = SDP_LANES;
@@ -185,3 +187,4 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
     SDP_META_MAGIC, (int32_t)sizeof(sdp_real), SDP_D, SDP_NU, SDP_HAS_W, 0, 0, 1,
     SDP_META_F_FAMILY, 0, 0, 256, 0, 0, 0, 0};
 }
+#endif  // SDP_FAMILY_POLICY

@@ -3715,19 +3715,21 @@ __global__ void __launch_bounds__(256) k_family_shift(real *__restrict__ J, int6
         Jp[i] = Jp[i] - r;
 }
 
-// k_diff_stats per listed member (no shift): the three key words of member members[y] at acc[3 y ..]
+// k_diff_stats per listed member: the three key words of member members[y] at acc[3 y ..].  ra / rb >= 0: J / V of
+// every member is read shifted by its own node ra / rb, each rounded once (the policy evaluation's raw buffers)
 template <typename real>
 __global__ void __launch_bounds__(256) sdp_family_diff_stats(const real *__restrict__ J, const real *__restrict__ V, int64_t S,
-                                                             const int32_t *__restrict__ members,
+                                                             const int32_t *__restrict__ members, int64_t ra, int64_t rb,
                                                              unsigned long long *__restrict__ acc)
 {
     const int64_t p = members[blockIdx.y];
     const real *__restrict__ Jp = J + p * S, *__restrict__ Vp = V + p * S;
+    const real ja = ra >= 0 ? Jp[ra] : real(0), vb = rb >= 0 ? Vp[rb] : real(0);
     real mn = real(INFINITY), mx = real(-INFINITY);
     int nan = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < S; i += stride)
-        stat_node(Jp[i], Vp[i], mn, mx, nan);
+        stat_node(ra >= 0 ? Jp[i] - ja : Jp[i], rb >= 0 ? Vp[i] - vb : Vp[i], mn, mx, nan);
     for (int off = warpSize / 2; off > 0; off >>= 1) {
         const real omn = __shfl_xor(mn, off), omx = __shfl_xor(mx, off);
         mn = omn < mn ? omn : mn;
@@ -3760,6 +3762,16 @@ struct sdp_family {
     int32_t axis_off[SDP_MAXD] = {0, 0, 0, 0};
     int32_t n_axes = 0;
     DevBuf axes, wgrid, proba, prm, box_lo, box_hi, box_n, buf[2], pol, idx, members, refs, stats;
+    // policy evaluation (sdp_family_load_policy_unit): the prescribed policy [P][S][nu] -- allocated at the first
+    // sdp_family_set_policy / sdp_family_take_policy --, the members that leave the list at a check, the flags of
+    // sdp_family_compare_policy, what the resident kernel reports
+    DevBuf pol_in, leavers, flags, res_done, res_stats;
+    bool has_policy = false;
+    size_t res_stats_rows = 0;
+    hipModule_t pmod = nullptr;
+    hipFunction_t f_evalpol = nullptr, f_resident = nullptr;
+    int res_threads = 0;
+    int64_t res_nodes = 0;
     int cur = 0;                           // buf[cur] is read (V), buf[cur ^ 1] written (J)
     std::vector<int32_t> active;           // the members the next launch runs
     std::vector<int> where;                // [P] the buffer that holds the member's latest values
@@ -3775,6 +3787,7 @@ struct sdp_family {
     ~sdp_family()
     {
         if (mod) (void)hipModuleUnload(mod);
+        if (pmod) (void)hipModuleUnload(pmod);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -4056,10 +4069,10 @@ extern "C" int sdp_family_vi_until(sdp_family *f, int32_t n_max, int rel_dp, int
             const int32_t *members = (const int32_t *)f->members.p;
             if (f->dtype == SDP_F32)
                 hipLaunchKernelGGL(sdp_family_diff_stats<float>, dim3(bx, n), dim3(256), 0, f->stream,
-                                   (const float *)f->buf[f->cur ^ 1].p, (const float *)f->buf[f->cur].p, f->S, members, acc);
+                                   (const float *)f->buf[f->cur ^ 1].p, (const float *)f->buf[f->cur].p, f->S, members, (int64_t)-1, (int64_t)-1, acc);
             else
                 hipLaunchKernelGGL(sdp_family_diff_stats<double>, dim3(bx, n), dim3(256), 0, f->stream,
-                                   (const double *)f->buf[f->cur ^ 1].p, (const double *)f->buf[f->cur].p, f->S, members, acc);
+                                   (const double *)f->buf[f->cur ^ 1].p, (const double *)f->buf[f->cur].p, f->S, members, (int64_t)-1, (int64_t)-1, acc);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(keys.data(), f->stats.p, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, f->stream));
             HIP_TRY(hipStreamSynchronize(f->stream));
@@ -4075,6 +4088,355 @@ extern "C" int sdp_family_vi_until(sdp_family *f, int32_t n_max, int rel_dp, int
             }
             ++checks;
             if (keep.size() != f->active.size()) { f->active.swap(keep); f->list_changed = true; }
+        }
+    }
+    return family_finish(f, rel_dp, n_max, J_ref_out);
+}
+
+// ---------------------------------------------------------------------------
+// policy evaluation of a family (kernels sdp_family_evalpol and sdp_family_evalpol_resident of an evaluation unit,
+// csrc/sdp_family_policy_kernel.h).  The loops are those of sdp_problem_eval_policy and iterate_until(evalpol) per
+// member: step k > 0 of the relative algorithm reads V - V[ref] and records J_ref[k - 1], only a member's last step
+// is followed by the explicit shift, and the statistics are those of the shifted sequence.
+// ---------------------------------------------------------------------------
+// flags[p] = 1 where the policies a and b of member p differ in a value (`!(x == y)`: a NaN differs from everything)
+template <typename real>
+__global__ void __launch_bounds__(256) k_family_policy_differs(const real *__restrict__ a, const real *__restrict__ b, int64_t n,
+                                                               int32_t *__restrict__ flags)
+{
+    const int64_t p = blockIdx.y;
+    const real *__restrict__ ap = a + p * n, *__restrict__ bp = b + p * n;
+    bool differs = false;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        differs |= !(ap[i] == bp[i]);
+    if (differs) flags[p] = 1;             // (every lane that stores stores the same word)
+}
+
+extern "C" int sdp_family_load_policy_unit(sdp_family *f, const char *module_path)
+{
+    if (!f || !module_path) return fail(SDP_EINVAL, "NULL argument");
+    if (f->pmod) { (void)hipModuleUnload(f->pmod); f->pmod = nullptr; f->f_evalpol = f->f_resident = nullptr; }
+    const size_t rs = real_size(f->dtype);
+    hipError_t e = hipModuleLoad(&f->pmod, module_path);
+    if (e != hipSuccess) { f->pmod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", module_path, hipGetErrorString(e)); }
+    int32_t m[SDP_META_WORDS] = {0};
+    hipDeviceptr_t mptr = nullptr;
+    size_t mbytes = 0;
+    const char *why = nullptr;
+    if (hipModuleGetGlobal(&mptr, &mbytes, f->pmod, "sdp_meta") != hipSuccess || mbytes != sizeof(m)) {
+        (void)hipGetLastError();
+        why = "it does not declare `sdp_meta`";
+    } else {
+        HIP_TRY(hipMemcpyDtoH(m, mptr, sizeof(m)));
+        if (m[SDP_META_MAGIC_AT] != SDP_META_MAGIC) why = "bad magic";
+        else if (!(m[SDP_META_FLAGS] & SDP_META_F_FAMILY_POLICY)) why = "not a family evaluation unit";
+        else if (m[SDP_META_REAL_BYTES] != (int)rs) why = "built for other reals";
+        else if (m[SDP_META_D] != f->d) why = "built for another number of state variables";
+        else if (m[SDP_META_NU] != f->nu) why = "built for another number of controls";
+        else if ((m[SDP_META_HAS_W] != 0) != (f->W > 0)) why = "built with / without a perturbation, unlike the family";
+        else if (m[SDP_META_THREADS] < 64 || m[SDP_META_THREADS] > 1024 || m[SDP_META_COL_ROWS] < 1
+                 || (size_t)m[SDP_META_COL_ROWS] * 2 * rs > (size_t)160 * 1024) why = "bad resident geometry";
+    }
+    hipDeviceptr_t pptr = nullptr;
+    size_t pbytes = 0;
+    if (!why) {
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->pmod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs) why = "another number of lifted constants";
+    }
+    if (!why && hipModuleGetFunction(&f->f_evalpol, f->pmod, "sdp_family_evalpol") != hipSuccess) why = "no sdp_family_evalpol kernel";
+    if (!why && hipModuleGetFunction(&f->f_resident, f->pmod, "sdp_family_evalpol_resident") != hipSuccess) why = "no sdp_family_evalpol_resident kernel";
+    if (why) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(f->pmod);
+        f->pmod = nullptr; f->f_evalpol = f->f_resident = nullptr;
+        return fail(SDP_EMODULE, "code object %s was not built for this family's evaluation: %s", module_path, why);
+    }
+    f->res_threads = m[SDP_META_THREADS];
+    f->res_nodes = m[SDP_META_COL_ROWS];
+    return SDP_OK;
+}
+
+static int family_ensure_pol_in(sdp_family *f)
+{
+    if (f->pol_in.p) return SDP_OK;
+    const size_t bytes = (size_t)f->P * f->S * f->nu * real_size(f->dtype);
+    int rc;
+    if ((rc = f->pol_in.alloc(bytes))) return rc;
+    HIP_TRY(hipMemset(f->pol_in.p, 0, bytes));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_set_policy(sdp_family *f, const void *host_pol)
+{
+    if (!f || !host_pol) return fail(SDP_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = family_ensure_pol_in(f))) return rc;
+    HIP_TRY(hipMemcpyAsync(f->pol_in.p, host_pol, (size_t)f->P * f->S * f->nu * real_size(f->dtype), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    f->has_policy = true;
+    return SDP_OK;
+}
+
+// the policy the last sweep wrote becomes the prescribed one, and the other buffer the next sweep's output: no copy
+extern "C" int sdp_family_take_policy(sdp_family *f)
+{
+    if (!f) return fail(SDP_EINVAL, "NULL family");
+    int rc;
+    if ((rc = family_ensure_pol_in(f))) return rc;
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    std::swap(f->pol.p, f->pol_in.p);
+    f->has_policy = true;
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_set_members(sdp_family *f, const int32_t *members, int32_t n)
+{
+    if (!f || !members) return fail(SDP_EINVAL, "NULL argument");
+    if (n < 1 || n > f->P) return fail(SDP_EINVAL, "%d members listed: a family of %d lists 1..%d", (int)n, f->P, f->P);
+    std::vector<char> seen((size_t)f->P, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (members[i] < 0 || members[i] >= f->P || seen[(size_t)members[i]])
+            return fail(SDP_EINVAL, "listed member %d (position %d) is outside 0..%d or listed twice", (int)members[i], (int)i, f->P - 1);
+        seen[(size_t)members[i]] = 1;
+    }
+    f->active.assign(members, members + n);
+    f->list_changed = true;
+    return SDP_OK;
+}
+
+// 1 where the policy of the last sweep equals the prescribed one, value by value
+extern "C" int sdp_family_compare_policy(sdp_family *f, int32_t *same)
+{
+    if (!f || !same) return fail(SDP_EINVAL, "NULL argument");
+    if (!f->has_policy || !f->pol_in.p) return fail(SDP_EINVAL, "no policy set (sdp_family_set_policy)");
+    int rc;
+    if (!f->flags.p && (rc = f->flags.alloc((size_t)f->P * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(f->flags.p, 0, (size_t)f->P * 4, f->stream));
+    const int64_t n = f->S * f->nu;
+    unsigned bx = (unsigned)((n + 255) / 256);
+    if (bx > 64) bx = 64;
+    if (f->dtype == SDP_F32)
+        hipLaunchKernelGGL(k_family_policy_differs<float>, dim3(bx, (unsigned)f->P), dim3(256), 0, f->stream,
+                           (const float *)f->pol.p, (const float *)f->pol_in.p, n, (int32_t *)f->flags.p);
+    else
+        hipLaunchKernelGGL(k_family_policy_differs<double>, dim3(bx, (unsigned)f->P), dim3(256), 0, f->stream,
+                           (const double *)f->pol.p, (const double *)f->pol_in.p, n, (int32_t *)f->flags.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(same, f->flags.p, (size_t)f->P * 4, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    for (int p = 0; p < f->P; ++p) same[p] = !same[p];
+    return SDP_OK;
+}
+
+static int family_eval_check(const sdp_family *f, int form)
+{
+    if (!f->f_evalpol || !f->f_resident) return fail(SDP_EINVAL, "no evaluation unit loaded (sdp_family_load_policy_unit)");
+    if (!f->has_policy || !f->pol_in.p) return fail(SDP_EINVAL, "no policy set (sdp_family_set_policy)");
+    if (form != SDP_FAMILY_EVAL_STEPS && form != SDP_FAMILY_EVAL_RESIDENT) return fail(SDP_EINVAL, "evaluation form %d: 0 (steps) or 1 (resident)", form);
+    // the fit rule: two buffers of S reals beside what the reduction needs, in the LDS budget the kernel was built for
+    if (form == SDP_FAMILY_EVAL_RESIDENT && f->S > f->res_nodes)
+        return fail(SDP_EINVAL, "the resident form holds two buffers of at most %lld reals (%lld bytes): a member of %lld nodes needs %lld bytes",
+                    (long long)f->res_nodes, (long long)(f->res_nodes * 2 * (int64_t)real_size(f->dtype)), (long long)f->S,
+                    (long long)(f->S * 2 * (int64_t)real_size(f->dtype)));
+    return SDP_OK;
+}
+
+static void family_eval_args(const sdp_family *f, SdpFamilyEvalArgs &e, int64_t ref_index)
+{
+    memset(&e, 0, sizeof(e));
+    SdpFamilyArgs &a = e.f;
+    a.V = f->buf[f->cur].p; a.J = f->buf[f->cur ^ 1].p; a.pol = f->pol_in.p;
+    a.axes = f->axes.p; a.wgrid = f->wgrid.p; a.proba = f->proba.p; a.prm = f->prm.p;
+    a.members = (const int32_t *)f->members.p;
+    a.S = f->S; a.t_k = 0.0;                         // a time-dependent system is evaluated at time index 0
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = f->orders[k]; a.axis_off[k] = f->axis_off[k]; }
+    a.n_axes = f->n_axes; a.W = f->W; a.n_active = (int)f->active.size();
+    e.ref_index = ref_index; e.refs = (double *)f->refs.p; e.P = f->P;
+}
+
+// one step of the listed members, buf[cur] -> buf[cur ^ 1] (raw values); fused: the relative shift of the step before
+static int family_evalpol_step(sdp_family *f, bool fused, int64_t ref_index, int slot)
+{
+    const int n = (int)f->active.size();
+    if (n < 1) return SDP_OK;
+    int rc;
+    if ((rc = family_send_list(f))) return rc;
+    SdpFamilyEvalArgs e;
+    family_eval_args(f, e, ref_index);
+    e.shift = fused ? 1 : 0;
+    e.slot = slot;
+    // a multiple of 8 workgroups, as family_backup, with the evaluation's tile of 256 nodes (a workgroup)
+    const int64_t tiles = (f->S + 255) / 256;
+    const int parts = n >= 8 ? 1 : 8 / n;
+    int64_t per_xcd = n >= 8 ? (int64_t)((n + 7) / 8) * tiles : (tiles + parts - 1) / parts;
+    if (per_xcd > f->cus) per_xcd = f->cus;
+    if (per_xcd < 1) per_xcd = 1;
+    size_t size = sizeof(e);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &e, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(f->f_evalpol, (unsigned)(per_xcd * 8), 1, 1, 256, 1, 1, 0, f->stream, nullptr, extra));
+    for (int32_t p : f->active) f->where[(size_t)p] = f->cur ^ 1;
+    return SDP_OK;
+}
+
+// the explicit shift after a member's last step: `n` members listed in `list` (device), their raw values in `J`
+static int family_last_shift(sdp_family *f, const int32_t *list, int n, void *J, int64_t ref_index, int slot)
+{
+    if (n < 1) return SDP_OK;
+    double *ref = (double *)f->refs.p + (size_t)slot * f->P;
+    unsigned bx = (unsigned)((f->S + 255) / 256);
+    if (bx > 64) bx = 64;
+    if (f->dtype == SDP_F32) {
+        hipLaunchKernelGGL(k_family_pick_ref<float>, dim3((n + 63) / 64), dim3(64), 0, f->stream, (const float *)J, f->S, ref_index, list, n, ref);
+        hipLaunchKernelGGL(k_family_shift<float>, dim3(bx, n), dim3(256), 0, f->stream, (float *)J, f->S, list, ref);
+    } else {
+        hipLaunchKernelGGL(k_family_pick_ref<double>, dim3((n + 63) / 64), dim3(64), 0, f->stream, (const double *)J, f->S, ref_index, list, n, ref);
+        hipLaunchKernelGGL(k_family_shift<double>, dim3(bx, n), dim3(256), 0, f->stream, (double *)J, f->S, list, ref);
+    }
+    HIP_TRY(hipGetLastError());
+    return SDP_OK;
+}
+
+// all steps of the listed members in one launch, buf[cur] -> buf[cur ^ 1] (final values); check_every 0: no check
+static int family_resident(sdp_family *f, int32_t n_iter, int rel_dp, int64_t ref_index, int32_t check_every, double tol,
+                           size_t n_checks)
+{
+    const int n = (int)f->active.size();
+    if (n < 1) return SDP_OK;
+    int rc;
+    if ((rc = family_send_list(f))) return rc;
+    if (f->S > f->res_nodes) return fail(SDP_EINVAL, "a member of %lld nodes is not resident (%lld at most)", (long long)f->S, (long long)f->res_nodes);
+    if (!f->res_done.p && (rc = f->res_done.alloc((size_t)f->P * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(f->res_done.p, 0, (size_t)f->P * 4, f->stream));
+    if (n_checks > 0) {
+        if (f->res_stats_rows < n_checks) {
+            if ((rc = f->res_stats.alloc(n_checks * f->P * 16))) { f->res_stats_rows = 0; return rc; }
+            f->res_stats_rows = n_checks;
+        }
+        HIP_TRY(hipMemsetAsync(f->res_stats.p, 0xff, n_checks * f->P * 16, f->stream));      // (NaN: a check that did not run)
+    }
+    SdpFamilyEvalArgs e;
+    family_eval_args(f, e, ref_index);
+    e.rel_dp = rel_dp ? 1 : 0; e.n_iter = n_iter; e.check_every = check_every; e.tol = tol;
+    e.n_done = (int32_t *)f->res_done.p;
+    e.stats = n_checks > 0 ? (double *)f->res_stats.p : nullptr;
+    // one workgroup a member and, with the whole LDS of a CU each, one workgroup a CU: the grid strides over the list
+    int blocks = n;
+    if (blocks > f->cus) blocks = f->cus;
+    size_t size = sizeof(e);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &e, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(f->f_resident, (unsigned)blocks, 1, 1, (unsigned)f->res_threads, 1, 1, 0, f->stream, nullptr, extra));
+    for (int32_t p : f->active) f->where[(size_t)p] = f->cur ^ 1;
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_eval_policy(sdp_family *f, int32_t n_iter, int rel_dp, int64_t ref_index, int32_t form, double *J_ref_out)
+{
+    if (!f) return fail(SDP_EINVAL, "NULL family");
+    if (n_iter < 0) return fail(SDP_EINVAL, "negative iteration count");
+    int rc;
+    if ((rc = family_eval_check(f, form))) return rc;
+    if ((rc = family_check_ref(f, rel_dp, ref_index))) return rc;
+    f->last_kernel_ms = 0;
+    if (n_iter == 0) return SDP_OK;                  // the result is the starting value
+    if ((rc = family_ensure_refs(f, n_iter))) return rc;
+    if ((rc = family_send_list(f))) return rc;
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    if (form == SDP_FAMILY_EVAL_RESIDENT) {
+        if ((rc = family_resident(f, n_iter, rel_dp, ref_index, 0, 0.0, 0))) return rc;
+    } else {
+        for (int32_t k = 0; k < n_iter; ++k) {
+            if (k > 0) f->cur ^= 1;
+            if ((rc = family_evalpol_step(f, rel_dp && k > 0, ref_index, k - 1))) return rc;
+        }
+        if (rel_dp && (rc = family_last_shift(f, (const int32_t *)f->members.p, (int)f->active.size(), f->buf[f->cur ^ 1].p, ref_index, n_iter - 1))) return rc;
+    }
+    return family_finish(f, rel_dp, n_iter, J_ref_out);
+}
+
+extern "C" int sdp_family_eval_policy_until(sdp_family *f, int32_t n_max, int rel_dp, int64_t ref_index, int32_t check_every,
+                                            double tol, int32_t form, int32_t *n_done, double *stats, double *J_ref_out)
+{
+    if (!f || !n_done || !stats) return fail(SDP_EINVAL, "NULL argument");
+    if (n_max < 1) return fail(SDP_EINVAL, "n_max must be at least 1");
+    if (check_every < 1) return fail(SDP_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0)) return fail(SDP_EINVAL, "tol must be a number >= 0");
+    int rc;
+    if ((rc = family_eval_check(f, form))) return rc;
+    if ((rc = family_check_ref(f, rel_dp, ref_index))) return rc;
+    if ((rc = family_ensure_refs(f, n_max))) return rc;
+    if ((rc = family_send_list(f))) return rc;
+    for (int p = 0; p < f->P; ++p) n_done[p] = 0;
+    const size_t P = (size_t)f->P;
+    if (form == SDP_FAMILY_EVAL_RESIDENT) {
+        const size_t n_checks = (size_t)(n_max / check_every + (n_max % check_every ? 1 : 0));
+        const std::vector<int32_t> listed = f->active;
+        HIP_TRY(hipEventRecord(f->ev0, f->stream));
+        if ((rc = family_resident(f, n_max, rel_dp, ref_index, check_every, tol, n_checks))) return rc;
+        if ((rc = family_finish(f, rel_dp, n_max, J_ref_out))) return rc;
+        // everything is read back once, at the end
+        std::vector<int32_t> done(P);
+        std::vector<double> st(n_checks * P * 2);
+        HIP_TRY(hipMemcpy(done.data(), f->res_done.p, P * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st.data(), f->res_stats.p, st.size() * 8, hipMemcpyDeviceToHost));
+        for (int32_t p : listed) {
+            n_done[p] = done[(size_t)p];
+            for (size_t c = 0; c < n_checks; ++c) {
+                stats[(c * P + p) * 2] = st[(c * P + p) * 2];
+                stats[(c * P + p) * 2 + 1] = st[(c * P + p) * 2 + 1];
+            }
+        }
+        return SDP_OK;
+    }
+    std::vector<unsigned long long> keys(P * 3);
+    if (!f->leavers.p && (rc = f->leavers.alloc(P * 4))) return rc;
+    int32_t checks = 0;
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int32_t k = 0; k < n_max && !f->active.empty(); ++k) {
+        if (k > 0) f->cur ^= 1;
+        if ((rc = family_evalpol_step(f, rel_dp && k > 0, ref_index, k - 1))) return rc;
+        for (int32_t p : f->active) n_done[p] = k + 1;
+        if ((k + 1) % check_every == 0 || k + 1 == n_max) {
+            // one reduction launch over the listed members and 24 bytes a member back: the statistics of the shifted
+            // sequence, from the raw buffers
+            const int n = (int)f->active.size();
+            HIP_TRY(hipMemsetAsync(f->stats.p, 0, (size_t)n * 3 * 8, f->stream));
+            unsigned bx = (unsigned)((f->S + 255) / 256);
+            if (bx > 64) bx = 64;
+            unsigned long long *acc = (unsigned long long *)f->stats.p;
+            const int32_t *members = (const int32_t *)f->members.p;
+            const int64_t ra = rel_dp ? ref_index : -1, rb = rel_dp && k > 0 ? ref_index : -1;
+            if (f->dtype == SDP_F32)
+                hipLaunchKernelGGL(sdp_family_diff_stats<float>, dim3(bx, n), dim3(256), 0, f->stream,
+                                   (const float *)f->buf[f->cur ^ 1].p, (const float *)f->buf[f->cur].p, f->S, members, ra, rb, acc);
+            else
+                hipLaunchKernelGGL(sdp_family_diff_stats<double>, dim3(bx, n), dim3(256), 0, f->stream,
+                                   (const double *)f->buf[f->cur ^ 1].p, (const double *)f->buf[f->cur].p, f->S, members, ra, rb, acc);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(keys.data(), f->stats.p, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, f->stream));
+            HIP_TRY(hipStreamSynchronize(f->stream));
+            std::vector<int32_t> keep, leave;
+            for (int i = 0; i < n; ++i) {
+                const int32_t p = f->active[(size_t)i];
+                const bool nan = keys[(size_t)i * 3 + 2] != 0;
+                const double dmin = nan ? NAN : sdp_key_value(~keys[(size_t)i * 3]);
+                const double dmax = nan ? NAN : sdp_key_value(keys[(size_t)i * 3 + 1]);
+                stats[((size_t)checks * P + p) * 2] = dmin;
+                stats[((size_t)checks * P + p) * 2 + 1] = dmax;
+                if (!(dmax - dmin <= tol) && k + 1 < n_max) keep.push_back(p);       // NaN never converges
+                else leave.push_back(p);
+            }
+            ++checks;
+            if (!leave.empty()) {
+                // a member that stops here takes its explicit shift now: its raw values stay in the buffer of this step
+                if (rel_dp) {
+                    HIP_TRY(hipMemcpyAsync(f->leavers.p, leave.data(), leave.size() * 4, hipMemcpyHostToDevice, f->stream));
+                    HIP_TRY(hipStreamSynchronize(f->stream));
+                    if ((rc = family_last_shift(f, (const int32_t *)f->leavers.p, (int)leave.size(), f->buf[f->cur ^ 1].p, ref_index, k))) return rc;
+                }
+                f->active.swap(keep);
+                f->list_changed = true;
+            }
         }
     }
     return family_finish(f, rel_dp, n_max, J_ref_out);

@@ -35,7 +35,10 @@ enum {
     SDP_META_F_LEAD = 256,  // node-order sweep with the filter on an array reduced over w (sdp_lead_kernel.h):
                             // the code object also exports sdp_lead_reduce, launched before every sweep
     SDP_META_F_PEER_STORES = 512,  // the backup kernels store J through sdp_store_J (SdpSweepArgs.peer_J: direct exchange)
-    SDP_META_F_FAMILY = 1024       // a family unit (sdp_family_kernel.h): sdp_family_sweep and nothing else
+    SDP_META_F_FAMILY = 1024,      // a family unit (sdp_family_kernel.h): sdp_family_sweep and nothing else
+    SDP_META_F_FAMILY_POLICY = 2048    // a family evaluation unit (sdp_family_policy_kernel.h): sdp_family_evalpol and
+                            // sdp_family_evalpol_resident; SDP_META_THREADS is the resident kernel's workgroup size and
+                            // SDP_META_COL_ROWS the nodes of a member its two LDS buffers hold
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -122,6 +125,31 @@ struct SdpFamilyArgs {
     int32_t W;             // perturbation points (0: deterministic systems)
     int32_t box_per_node;  // 0: one box per member, 1: per-node arrays
     int32_t n_active;      // members listed (>= 1)
+};
+
+// Fixed-policy backups of a family (sdp_family_policy_kernel.h).  `f` is the block of the sweep with `f.pol` the
+// PRESCRIBED policy [P][S][nu] (read, not written) and the box arrays and `f.idx` unused (null).
+// Kernel `sdp_family_evalpol` runs one step of the listed members, f.V -> f.J: with `shift` every vertex of member p
+// is read as V - V[p][ref_index] (the relative shift of the previous step, SdpLerp<.., SHIFT>) and that value is
+// stored in refs[slot][p].
+// Kernel `sdp_family_evalpol_resident` runs ALL steps of a listed member in one workgroup, the values in LDS: it
+// starts from f.V, writes the result (shifted once more with rel_dp) to f.J, the reference cost of step k to
+// refs[k][p], the steps run to n_done[p] and, with check_every > 0, dmin / dmax of every check the member ran to
+// stats[check][p][0..1] (it stops at the first check with dmax - dmin <= tol; a NaN never converges).
+struct SdpFamilyEvalArgs {
+    SdpFamilyArgs f;
+    int64_t ref_index;     // node of the relative shift (only read with shift / rel_dp)
+    double *refs;          // [rows][P] reference costs (may be null without shift / rel_dp)
+    int32_t P;             // members of the family: the row length of refs, n_done and stats
+    int32_t shift;         // evalpol: 1 = read V - V[ref_index] and store V[ref_index] to refs[slot]
+    int32_t slot;
+    // ---- resident kernel only ----
+    int32_t rel_dp;
+    int32_t n_iter;        // steps (at most, with a check)
+    int32_t check_every;   // 0: no check; else after steps c, 2c, .. and after step n_iter
+    double tol;
+    int32_t *n_done;       // [P]
+    double *stats;         // [checks][P][2] (null without a check)
 };
 
 // Batched closed-loop simulation (the user loop of the reference's examples, e.g.

@@ -6,6 +6,10 @@ launch and call costs once per member and sweep.  A SolverFamily takes P `DPSolv
 for a solo call, and runs their sweeps together: one launch of kernel `sdp_family_sweep`
 (csrc/sdp_family_kernel.h) backs up every member.
 
+`eval_policy` and `policy_iteration` evaluate the members' policies together as well (csrc/sdp_family_policy_kernel.h):
+one launch of `sdp_family_evalpol` per step, or all steps of a member in one workgroup with its values in LDS
+(`sdp_family_evalpol_resident`); the improvement of policy iteration is the family sweep.
+
 The definition is the solo call: member p of every result equals, bit for bit, what `solvers[p]` returns from the
 same method with `kernel = 'generic'`.
 
@@ -102,6 +106,45 @@ class _FamilyProblem(object):
         n_done = np.zeros(self.P, dtype=np.int32)
         nat.check(nat.lib().sdp_family_vi_until(self.h, int(n_max), int(bool(rel_dp)), int(ref_index), int(check_every),
                                                 float(tol), nat.ptr(n_done), nat.ptr(stats), nat.ptr(refs)))
+        return n_done, stats, refs
+
+    # ---- policy evaluation (csrc/sdp_family_policy_kernel.h)
+    def load_policy_unit(self, module):
+        nat.check(nat.lib().sdp_family_load_policy_unit(self.h, module.encode()))
+
+    def set_policy(self, pol):
+        pol = np.ascontiguousarray(pol, dtype=self.dtype)
+        assert pol.size == self.P * self.S * self.nu
+        nat.check(nat.lib().sdp_family_set_policy(self.h, nat.ptr(pol)))
+
+    def take_policy(self):
+        nat.check(nat.lib().sdp_family_take_policy(self.h))
+
+    def compare_policy(self):
+        """[P] bool: the policy of the last sweep equals the prescribed one, value by value"""
+        same = np.zeros(self.P, dtype=np.int32)
+        nat.check(nat.lib().sdp_family_compare_policy(self.h, nat.ptr(same)))
+        return same != 0
+
+    def set_members(self, members):
+        members = np.ascontiguousarray(members, dtype=np.int32)
+        nat.check(nat.lib().sdp_family_set_members(self.h, nat.ptr(members), int(members.size)))
+
+    def eval_policy(self, n_iter, rel_dp, ref_index, resident):
+        refs = np.zeros((max(int(n_iter), 1), self.P))
+        nat.check(nat.lib().sdp_family_eval_policy(self.h, int(n_iter), int(bool(rel_dp)), int(ref_index),
+                                                   int(bool(resident)), nat.ptr(refs)))
+        return refs[:int(n_iter)]
+
+    def eval_policy_until(self, n_max, rel_dp, ref_index, check_every, tol, resident):
+        """as `until`, for the members listed (the entries of the others stay 0 / NaN)"""
+        schedule = conv.check_schedule(int(n_max), int(check_every))
+        stats = np.full((len(schedule), self.P, 2), np.nan)
+        refs = np.zeros((int(n_max), self.P))
+        n_done = np.zeros(self.P, dtype=np.int32)
+        nat.check(nat.lib().sdp_family_eval_policy_until(self.h, int(n_max), int(bool(rel_dp)), int(ref_index),
+                                                         int(check_every), float(tol), int(bool(resident)),
+                                                         nat.ptr(n_done), nat.ptr(stats), nat.ptr(refs)))
         return n_done, stats, refs
 
     def get_value(self):
@@ -258,16 +301,25 @@ class SolverFamily(object):
         return (S * rs * (2 + self.nu) + S * 4 + self.nu * cols * (2 * rs + 4)
                 + rs * (tabs['axes'].shape[1] + 2 * self.W + tabs['prm'].shape[1]) + 4 + 24)
 
-    def _chunks(self, tabs):
-        """[(first, last), ...]: members whose device arrays take at most chunk_bytes together"""
-        step = max(1, int(self.chunk_bytes) // self._member_bytes(tabs))
+    def _policy_bytes(self):
+        """what a member takes on top of _member_bytes in eval_policy and policy_iteration: the prescribed policy
+        (allocated at the first evaluation), its flag of the policy compare and its word of the resident kernel"""
+        return int(np.prod(self.dims)) * self.nu * self.dtype.itemsize + 8
+
+    def _chunks(self, tabs, extra=0):
+        """[(first, last), ...]: members whose device arrays take at most chunk_bytes together (`extra`: bytes a
+        member takes beside _member_bytes in this call)"""
+        step = max(1, int(self.chunk_bytes) // (self._member_bytes(tabs) + extra))
         return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
 
-    def _run(self, tabs, J0, work):
-        """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims"""
+    def _run(self, tabs, J0, work, evaluation=False):
+        """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims.  evaluation: the
+        call evaluates policies, so every handle also loads the family's evaluation unit and the chunks leave room
+        for the prescribed policy"""
         nat.require_gpu()
         module = nat.compile_model(tabs['source'])
-        chunks = self._chunks(tabs)
+        policy_module = nat.compile_model(codegen.family_policy_unit(tabs['model'], self.dtype)) if evaluation else None
+        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else 0)
         digest = hashlib.sha256()
         for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
             if tabs[k] is not None:
@@ -284,6 +336,9 @@ class SolverFamily(object):
                 if len(chunks) == 1:
                     self._handle = (key, prob)
             try:
+                if evaluation and getattr(prob, 'policy_module', None) != policy_module:
+                    prob.load_policy_unit(policy_module)
+                    prob.policy_module = policy_module
                 prob.set_params(tabs['prm'][first:last])
                 prob.set_value(J0[first:last])
                 work(prob, first, last)
@@ -294,14 +349,14 @@ class SolverFamily(object):
                                  lifted_constants=int(tabs['prm'].shape[1]), chunks=len(chunks), module=module,
                                  per_node=tabs['per_node'], time_specialized=tabs['time_specialized'])
 
-    def _start(self, J_next, rel_dp):
+    def _start(self, J_next, rel_dp, name='J_next'):
         """the start of every member, [P] + dims in the family's reals, from an array of shape dims or (P,) + dims"""
         J_next = np.asarray(J_next)
         if J_next.shape == self.dims:
             J_next = np.broadcast_to(J_next, (self.P,) + self.dims)
         elif J_next.shape != (self.P,) + self.dims:
-            raise ValueError('array `J_next` should be of shape {:s} or {:s}, not {:s}'.format(
-                str(self.dims), str((self.P,) + self.dims), str(J_next.shape)))
+            raise ValueError('array `{:s}` should be of shape {:s} or {:s}, not {:s}'.format(
+                name, str(self.dims), str((self.P,) + self.dims), str(J_next.shape)))
         if rel_dp:
             # the cost-to-go must be a *differential* cost, zero at the reference state, for every member
             assert np.all(J_next[(slice(None),) + self.solvers[0]._state_ref_ind] == 0.)
@@ -400,6 +455,170 @@ class SolverFamily(object):
         self.last_policy_index = idx
         self.last_convergence = None
         return J, pol
+
+    # ------------------------------------------------------------------ policy evaluation and iteration
+    # the form of an evaluation (csrc/sdp_family_policy_kernel.h): 'steps' is a launch per step (kernel
+    # sdp_family_evalpol, any grid size); 'resident' runs all steps of a member in one workgroup with its values in
+    # LDS (sdp_family_evalpol_resident), for a member that fits there (codegen.family_resident_nodes).  'auto' takes the
+    # resident form for n_iter >= 2 steps of a member of at most one node per thread of the resident workgroup, the
+    # steps form otherwise: as measured, a member of 651 nodes is 1.3 to 1.8 times faster resident at
+    # every family size, one of 2501 nodes -- three trips of the workgroup a step, on one CU -- is not
+    evaluation = 'auto'
+
+    def _evaluation_form(self, n_iter):
+        """'steps' or 'resident' for a call of n_iter steps, by `self.evaluation` and the fit rule
+        (codegen.family_resident_nodes)"""
+        if self.evaluation not in ('auto', 'steps', 'resident'):
+            raise ValueError("evaluation should be 'auto', 'steps' or 'resident', not {!r}".format(self.evaluation))
+        S, rs = int(np.prod(self.dims)), self.dtype.itemsize
+        fits = S <= codegen.family_resident_nodes(self.dtype)
+        if self.evaluation == 'resident' and not fits:
+            raise ValueError('the resident evaluation holds two value buffers of a member in {} bytes of LDS: a member of '
+                             '{} nodes needs {} bytes'.format(
+                                 codegen.FAMILY_RESIDENT_LDS_BYTES - codegen.FAMILY_RESIDENT_REDUCTION_BYTES, S, 2 * S * rs))
+        if self.evaluation == 'auto':
+            return 'resident' if fits and S <= codegen.FAMILY_RESIDENT_THREADS and n_iter >= 2 else 'steps'
+        return self.evaluation
+
+    def _policy(self, pol, name='pol'):
+        """the policy of every member, [P] + dims + (nu,) in the family's reals, from an array of shape
+        dims + (nu,) (every member's policy) or (P,) + dims + (nu,)"""
+        pol = np.asarray(pol)
+        one, each = self.dims + (self.nu,), (self.P,) + self.dims + (self.nu,)
+        if pol.shape == one and one != each:
+            pol = np.broadcast_to(pol, each)
+        elif pol.shape != each:
+            raise ValueError('array `{:s}` should be of shape {:s} or {:s}, not {:s}'.format(name, str(one), str(each), str(pol.shape)))
+        return np.ascontiguousarray(pol, dtype=self.dtype)
+
+    def _evaluate(self, prob, n_iter, rel_dp, tol, check_every, form):
+        """the evaluation of the members listed in `prob`, from the values set: (steps run [P], statistics
+        [n_checks][P][2] or None, reference costs [n_iter][P])"""
+        ref_flat = self._ref_flat(rel_dp)
+        if tol is None:
+            refs = prob.eval_policy(n_iter, rel_dp, ref_flat, form == 'resident')
+            return np.full(prob.P, n_iter, dtype=np.int32), None, refs
+        return prob.eval_policy_until(n_iter, rel_dp, ref_flat, check_every, tol, form == 'resident')
+
+    def _records(self, members, n_done, stats, refs, n_iter, rel_dp, tol, check_every):
+        """the solo SweepConvergence of every member of `members` (positions in the arrays of one chunk)"""
+        schedule = conv.check_schedule(n_iter, check_every)
+        out = []
+        for p in members:
+            checked = [k for k in schedule if k <= n_done[p]]
+            checks = [(k, stats[c, p, 0], stats[c, p, 1]) for c, k in enumerate(checked)]
+            out.append(DPSolver._sweep_record(tol, check_every, int(n_done[p]), checks, refs[:n_done[p], p].copy(), rel_dp))
+        return out
+
+    def _evaluation_info(self, form):
+        S, rs = int(np.prod(self.dims)), self.dtype.itemsize
+        self.backend_info['evaluation'] = form
+        self.backend_info['evaluation_lds_bytes'] = (2 * S * rs + codegen.FAMILY_RESIDENT_REDUCTION_BYTES
+                                                     if form == 'resident' else 0)
+
+    def _check_evaluation(self, n_iter, rel_dp, tol, check_every, what):
+        if tol is not None:
+            tol, check_every = conv.validate(tol, check_every)
+            if n_iter < 1:
+                raise ValueError('{} with tol needs n_iter >= 1, not {!r}'.format(what, n_iter))
+        if n_iter < (1 if rel_dp else 0):
+            raise ValueError('{} needs n_iter >= {}, not {!r}'.format(what, 1 if rel_dp else 0, n_iter))
+        return tol, check_every
+
+    def eval_policy(self, pol, n_iter, rel_dp=False, J_zero=None, J_ref_full=False, tol=None, check_every=1):
+        """`DPSolver.eval_policy` of every member, stacked, without its progress lines.  pol: shape dims + (nu,)
+        (every member's policy) or (P,) + dims + (nu,); J_zero: dims or (P,) + dims, zeros by default.  Returns
+        J_pol of shape (P,) + dims, or with rel_dp (J_pol, J_ref), J_ref of shape (P,) or with J_ref_full a list of
+        P arrays (one reference cost per step the member ran).  With `tol` a member stops at its own first checked
+        step whose span is <= tol: member p equals the solo call with n_iter = the steps it ran, and
+        last_convergence[p] is the solo record.  A time-dependent system is evaluated at time index 0."""
+        tol, check_every = self._check_evaluation(n_iter, rel_dp, tol, check_every, 'eval_policy')
+        self.last_convergence = None
+        pol = self._policy(pol)
+        J0 = self._start(np.zeros(self.dims) if J_zero is None else J_zero, False, 'J_zero')
+        form = self._evaluation_form(n_iter)
+        tabs = self._tables(None if self.stationnary else 0)
+        J = np.empty((self.P,) + self.dims, dtype=self.dtype)
+        per_member, records = [None] * self.P, [None] * self.P
+
+        def work(prob, a, b):
+            prob.set_policy(pol[a:b])
+            n_done, stats, refs = self._evaluate(prob, n_iter, rel_dp, tol, check_every, form)
+            J[a:b] = prob.get_value()
+            for p in range(b - a):
+                per_member[a + p] = refs[:n_done[p], p].copy()
+            if tol is not None:
+                records[a:b] = self._records(range(b - a), n_done, stats, refs, n_iter, rel_dp, tol, check_every)
+        self._run(tabs, J0, work, evaluation=True)
+        self._evaluation_info(form)
+        if tol is not None:
+            self.last_convergence = records
+        if rel_dp:
+            return J, (per_member if J_ref_full else np.array([r[-1] for r in per_member]))
+        return J
+
+    def policy_iteration(self, pol_init, n_val, n_pol=1, rel_dp=False, tol=None, check_every=1):
+        """`DPSolver.policy_iteration` of every member, stacked, without its progress lines: (J_pol, pol) of shapes
+        (P,) + dims and (P,) + dims + (nu,); J_pol is (J_diff, J_ref) with rel_dp, J_ref of shape (P,).  With `tol`
+        every evaluation stops per member as in `eval_policy`, a member whose improvement step returns exactly the
+        policy it was given is stable and leaves the list of members still running, and last_convergence[p] is the
+        solo PolicyIterationConvergence.  The improvement is a family sweep; the policy it writes becomes the next
+        evaluation's input on the device (the two buffers swap), and `same policy` is decided there."""
+        tol, check_every = self._check_evaluation(n_val, rel_dp, tol, check_every, 'policy_iteration')
+        self.last_convergence = None
+        pol0 = self._policy(pol_init, 'pol_init')
+        form = self._evaluation_form(n_val)
+        tabs = self._tables(None if self.stationnary else 0)
+        ref_flat = self._ref_flat(rel_dp)
+        J = np.zeros((self.P,) + self.dims, dtype=self.dtype)
+        pol = pol0.copy()
+        idx = np.zeros((self.P,) + self.dims, dtype=np.int32)
+        J_ref = np.zeros(self.P)
+        evaluations = [[] for _ in range(self.P)]
+        n_improvements, stable = np.zeros(self.P, dtype=int), np.zeros(self.P, dtype=bool)
+        zeros = np.zeros((self.P,) + self.dims, dtype=self.dtype)
+
+        def work(prob, a, b):
+            def evaluate(members):
+                """the members listed (positions in the chunk) from zeros, under the prescribed policy"""
+                prob.set_value(zeros[a:b])
+                prob.set_members(members)
+                n_done, stats, refs = self._evaluate(prob, n_val, rel_dp, tol, check_every, form)
+                J[a + members] = prob.get_value()[members]
+                if rel_dp:
+                    J_ref[a + members] = [refs[n_done[p] - 1, p] for p in members]
+                if tol is not None:
+                    for p, rec in zip(members, self._records(members, n_done, stats, refs, n_val, rel_dp, tol, check_every)):
+                        evaluations[a + p].append(rec)
+            prob.set_policy(pol0[a:b])
+            active = np.arange(b - a)
+            evaluate(active)
+            for k in range(n_pol):
+                # the improvement: one family sweep of the members still running, from their evaluations
+                prob.set_value(J[a:b])
+                prob.set_members(active)
+                prob.sweep(0.0, rel_dp, ref_flat)
+                n_improvements[a + active] += 1
+                same = prob.compare_policy()[active] if tol is not None else np.zeros(active.size, dtype=bool)
+                last = k == n_pol - 1
+                if same.any() or last:
+                    # a member that ends here returns this sweep's policy (a stable one: equal to the one it was given)
+                    pol_new, idx_new = prob.get_policy()
+                    ends = active if last else active[same]
+                    pol[a + ends], idx[a + ends] = pol_new[ends], idx_new[ends]
+                stable[a + active[same]] = True          # (J is already the evaluation of this policy)
+                active = active[~same]
+                if active.size == 0:
+                    break
+                prob.take_policy()
+                evaluate(active)
+        self._run(tabs, zeros, work, evaluation=True)
+        self._evaluation_info(form)
+        self.last_policy_index = idx
+        if tol is not None:
+            self.last_convergence = [conv.PolicyIterationConvergence(evaluations[p], int(n_improvements[p]), bool(stable[p]))
+                                     for p in range(self.P)]
+        return ((J, J_ref) if rel_dp else J), pol
 
     def last_kernel_ms(self):
         """HIP-event time of the launches of the last sweep call of a family that runs as one chunk (None otherwise)"""
