@@ -507,6 +507,29 @@ int sdp_family_eval_policy(sdp_family *f, int32_t n_iter, int rel_dp, int64_t re
 int sdp_family_eval_policy_until(sdp_family *f, int32_t n_max, int rel_dp, int64_t ref_index, int32_t check_every,
                                  double tol, int32_t form, int32_t *n_done, double *stats, double *J_ref_out);
 
+/*
+ * Monte Carlo policy evaluation of a family (csrc/sdp_family_mc_kernel.h).  The family's MONTE CARLO unit
+ * (codegen.family_mc_unit: kernel sdp_family_montecarlo) is loaded beside the sweep unit; its sdp_meta is checked.
+ */
+int sdp_family_load_mc_unit(sdp_family *f, const char *module_path);
+/*
+ * sdp_problem_montecarlo of every member of the handle, together: B trajectories with the ids traj_offset ..
+ * traj_offset + B - 1 and T steps per member, member p under its policy host_pol[p] ([P][nu][S] reals), from
+ * its start states host_x0[p] ([P][d][B]), with its seed host_seeds[p] and its law (host_cum [P][n_law] float64
+ * running sums, host_law_grid [P][n_law] reals; every law has n_law points, 1..4096, the draw table of one member
+ * at most 65536 bytes), the constants of sdp_family_set_params.  The sums are zeroed, one launch runs at most
+ * steps_per_launch steps (clamped to 2^30) of all members, the state stays on the device in between, and everything
+ * is read back once: host_cost_sum [P][B] reals, host_n_outside [P][B], host_x_final [P][d][B] reals,
+ * host_occupancy [P][S] or NULL.  Member p of every result has the bits of sdp_problem_montecarlo on problem p
+ * alone.  sdp_family_last_kernel_ms covers the call.  SDP_EINVAL for a NULL pointer, a negative size, n_burn
+ * outside [0, T], steps_per_launch < 1, a deterministic family, a law that does not fit, or no unit loaded.
+ */
+int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_t B, int64_t T, int64_t n_burn,
+                          const uint64_t *host_seeds, uint64_t traj_offset, const void *host_x0,
+                          const double *host_cum, int32_t n_law, const void *host_law_grid, double t0,
+                          int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                          void *host_x_final, uint64_t *host_occupancy);
+
 /* ---- tabulated backup (models that cannot be traced into device code) ------- */
 /*
  * Replaces the numeric part of DPSolver._value_at_state_vect

@@ -148,6 +148,9 @@ def _declare(lib):
         'sdp_family_set_members': (C.c_int, [vp, vp, i32]),
         'sdp_family_eval_policy': (C.c_int, [vp, i32, C.c_int, i64, i32, vp]),
         'sdp_family_eval_policy_until': (C.c_int, [vp, i32, C.c_int, i64, i32, dbl, i32, vp, vp, vp]),
+        'sdp_family_load_mc_unit': (C.c_int, [vp, C.c_char_p]),
+        'sdp_family_montecarlo': (C.c_int, [vp, vp, i64, i64, i64, vp, C.c_uint64, vp, vp, i32, vp, dbl, i64, vp, vp,
+                                            vp, vp]),
         'sdp_transop_create': (C.c_int, [vp, vp, dbl, P(vp)]),
         'sdp_transop_from_coo': (C.c_int, [C.c_int, i64, i64, vp, vp, vp, P(vp)]),
         'sdp_transop_destroy': (C.c_int, [vp]),

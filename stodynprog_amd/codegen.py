@@ -805,6 +805,25 @@ def family_policy_unit(model, dtype):
     return '\n'.join(head)
 
 
+def family_mc_unit(model, dtype):
+    """The generated source of a family MONTE CARLO unit (csrc/sdp_family_mc_kernel.h, kernel
+    `sdp_family_montecarlo`): the direct prologue of a model with lifted constants, marked SDP_FAMILY and
+    SDP_FAMILY_MC, and the Monte Carlo header in the place of sdp_sweep_kernel.h.  A closed loop has no control
+    lattice, so there is one unit per model structure and real type (the lane count the prologue prints is 1 and
+    nothing reads it)."""
+    if model.param_index is None:
+        raise ValueError('a family unit takes a model with lifted constants (TracedModel.lift_constants)')
+    if model.n_perturb != 1:
+        raise NotImplementedError('a family Monte Carlo unit draws one perturbation variable')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, 1, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
+    head.insert(at + 1, '#define SDP_FAMILY_MC 1       // .. and sdp_family_montecarlo in the place of sdp_family_sweep')
+    head += ['#include "sdp_family_mc_kernel.h"    // brings in sdp_family_kernel.h and the draw helpers of sdp_mc_kernel.h', '']
+    return '\n'.join(head)
+
+
 def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False, lookahead=None):
     """The generated source of one model code object.  `family`: what the unit is to hold beside the direct node-order
     kernels of csrc/sdp_sweep_kernel.h --
@@ -1507,6 +1526,9 @@ def source_key(source):
             h.update(f.read())
     if '#define SDP_FAMILY_POLICY ' in source:
         with open(os.path.join(CSRC, 'sdp_family_policy_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_FAMILY_MC ' in source:
+        with open(os.path.join(CSRC, 'sdp_family_mc_kernel.h'), 'rb') as f:
             h.update(f.read())
     h.update(source.encode())
     h.update(' '.join(HIPCC_FLAGS[:-1]).encode())

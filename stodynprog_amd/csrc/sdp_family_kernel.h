@@ -116,8 +116,9 @@ SDP_DEV sdp_real sdp_family_expected_cost(const SdpFamilyArgs &a, const SdpMembe
 #endif
 }
 
-#if !defined(SDP_FAMILY_POLICY)
-// (an evaluation unit, sdp_family_policy_kernel.h, takes SdpMember and the helpers above and brings its own kernels)
+#if !defined(SDP_FAMILY_POLICY) && !defined(SDP_FAMILY_MC)
+// (an evaluation unit, sdp_family_policy_kernel.h, takes SdpMember and the helpers above and brings its own kernels; so
+// does a Monte Carlo unit, sdp_family_mc_kernel.h)
 extern "C" __global__ void __launch_bounds__(256) sdp_family_sweep(SdpFamilyArgs a)
 {
     constexpr int L = SDP_LANES;

@@ -3772,6 +3772,9 @@ struct sdp_family {
     hipFunction_t f_evalpol = nullptr, f_resident = nullptr;
     int res_threads = 0;
     int64_t res_nodes = 0;
+    // Monte Carlo evaluation (sdp_family_load_mc_unit): the unit and its kernel; the arrays of a run live for the call
+    hipModule_t mcmod = nullptr;
+    hipFunction_t f_montecarlo = nullptr;
     int cur = 0;                           // buf[cur] is read (V), buf[cur ^ 1] written (J)
     std::vector<int32_t> active;           // the members the next launch runs
     std::vector<int> where;                // [P] the buffer that holds the member's latest values
@@ -3788,6 +3791,7 @@ struct sdp_family {
     {
         if (mod) (void)hipModuleUnload(mod);
         if (pmod) (void)hipModuleUnload(pmod);
+        if (mcmod) (void)hipModuleUnload(mcmod);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -4440,6 +4444,134 @@ extern "C" int sdp_family_eval_policy_until(sdp_family *f, int32_t n_max, int re
         }
     }
     return family_finish(f, rel_dp, n_max, J_ref_out);
+}
+
+// ---------------------------------------------------------------------------
+// Monte Carlo policy evaluation of a family (csrc/sdp_family_mc_kernel.h): sdp_problem_montecarlo of every member in
+// one launch per cut of the steps.  The unit is loaded beside the sweep unit; the arrays of a run live for the call.
+// ---------------------------------------------------------------------------
+extern "C" int sdp_family_load_mc_unit(sdp_family *f, const char *module_path)
+{
+    if (!f || !module_path) return fail(SDP_EINVAL, "NULL argument");
+    if (f->mcmod) { (void)hipModuleUnload(f->mcmod); f->mcmod = nullptr; f->f_montecarlo = nullptr; }
+    const size_t rs = real_size(f->dtype);
+    hipError_t e = hipModuleLoad(&f->mcmod, module_path);
+    if (e != hipSuccess) { f->mcmod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", module_path, hipGetErrorString(e)); }
+    int32_t m[SDP_META_WORDS] = {0};
+    hipDeviceptr_t mptr = nullptr;
+    size_t mbytes = 0;
+    const char *why = nullptr;
+    if (hipModuleGetGlobal(&mptr, &mbytes, f->mcmod, "sdp_meta") != hipSuccess || mbytes != sizeof(m)) {
+        (void)hipGetLastError();
+        why = "it does not declare `sdp_meta`";
+    } else {
+        HIP_TRY(hipMemcpyDtoH(m, mptr, sizeof(m)));
+        if (m[SDP_META_MAGIC_AT] != SDP_META_MAGIC) why = "bad magic";
+        else if (!(m[SDP_META_FLAGS] & SDP_META_F_FAMILY_MC)) why = "not a family Monte Carlo unit";
+        else if (m[SDP_META_THREADS] != 256) why = "built for another workgroup size";
+        else if (m[SDP_META_REAL_BYTES] != (int)rs) why = "built for other reals";
+        else if (m[SDP_META_D] != f->d) why = "built for another number of state variables";
+        else if (m[SDP_META_NU] != f->nu) why = "built for another number of controls";
+        else if (!m[SDP_META_HAS_W] || f->W <= 0) why = "a deterministic system has nothing to draw";
+    }
+    hipDeviceptr_t pptr = nullptr;
+    size_t pbytes = 0;
+    if (!why) {
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->mcmod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs) why = "another number of lifted constants";
+    }
+    if (!why && hipModuleGetFunction(&f->f_montecarlo, f->mcmod, "sdp_family_montecarlo") != hipSuccess) why = "no sdp_family_montecarlo kernel";
+    if (why) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(f->mcmod);
+        f->mcmod = nullptr; f->f_montecarlo = nullptr;
+        return fail(SDP_EMODULE, "code object %s was not built for this family's Monte Carlo evaluation: %s", module_path, why);
+    }
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_t B, int64_t T, int64_t n_burn,
+                                     const uint64_t *host_seeds, uint64_t traj_offset, const void *host_x0,
+                                     const double *host_cum, int32_t n_law, const void *host_law_grid, double t0,
+                                     int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                                     void *host_x_final, uint64_t *host_occupancy)
+{
+    if (!f || !host_pol || !host_seeds || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (f->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    if (!f->f_montecarlo) return fail(SDP_EINVAL, "no Monte Carlo unit loaded (sdp_family_load_mc_unit)");
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    // (the draw table of one member in LDS: the cumulative sums, then the values)
+    const size_t lds_bytes = (size_t)(n_law - 1) * 8 + (size_t)n_law * rs;
+    if (lds_bytes > 65536)
+        return fail(SDP_EINVAL, "a law of %d points needs %zu bytes of LDS: at most 65536", (int)n_law, lds_bytes);
+    DevBuf dpol, dx, dacc, dout, dcum, dlaw, dseed, docc;
+    int rc;
+    if ((rc = upload(dpol, host_pol, P * (size_t)f->nu * f->S * rs))) return rc;          // [P][nu][S]
+    if ((rc = upload(dx, host_x0, P * (size_t)f->d * B * rs))) return rc;                 // [P][d][B]
+    if ((rc = upload(dcum, host_cum, P * (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, P * (size_t)n_law * rs))) return rc;
+    if ((rc = upload(dseed, host_seeds, P * 8))) return rc;
+    if ((rc = dacc.alloc(P * (size_t)B * rs))) return rc;
+    if ((rc = dout.alloc(P * (size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, P * (size_t)B * rs, f->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, P * (size_t)B * 8, f->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc(P * (size_t)f->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, P * (size_t)f->S * 8, f->stream));
+    }
+    SdpFamilyMcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.axes = f->axes.p; a.prm = f->prm.p; a.cum = (const double *)dcum.p; a.law_grid = dlaw.p;
+    a.seed = (const uint64_t *)dseed.p; a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.S = f->S; a.traj_offset = traj_offset; a.n_burn = n_burn; a.t0 = t0;
+    a.n_law = n_law; a.n_axes = f->n_axes; a.P = f->P;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = f->orders[k]; a.axis_off[k] = f->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    // a tile of 256 trajectories of one member is a workgroup.  A multiple of 8 workgroups (one share per XCD,
+    // sdp_family_mc_kernel.h): per XCD as many as it has tiles to walk, in all at most the workgroups that are resident
+    // at once (the kernel's registers and the draw table decide how many a CU holds, 8 at most), the rest in the stride loop
+    const int threads = 256;
+    const unsigned lds = (unsigned)lds_bytes;
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f->f_montecarlo, threads, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 8) per_cu = 8;
+    const int64_t tiles = (B + threads - 1) / threads;
+    const int parts = f->P >= 8 ? 1 : 8 / f->P;
+    int64_t per_xcd = f->P >= 8 ? (int64_t)((f->P + 7) / 8) * tiles : (tiles + parts - 1) / parts;
+    const int64_t cap = (int64_t)f->cus * per_cu / 8;
+    if (per_xcd > cap) per_xcd = cap;
+    if (per_xcd < 1) per_xcd = 1;
+    HIP_TRY(hipStreamSynchronize(f->stream));        // lifted constants set on the family's stream
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int64_t k = 0; k < T; k += steps_per_launch) {
+        a.step_begin = k;
+        a.step_end = (T - k < steps_per_launch) ? T : k + steps_per_launch;
+        HIP_TRY(hipModuleLaunchKernel(f->f_montecarlo, (unsigned)(per_xcd * 8), 1, 1, threads, 1, 1, lds, f->stream, nullptr, extra));
+    }
+    HIP_TRY(hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    f->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, P * (size_t)f->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
 }
 
 // [P][S] elements of `elem_bytes` from the two buffers, every member from the one its last sweep wrote

@@ -36,9 +36,11 @@ enum {
                             // the code object also exports sdp_lead_reduce, launched before every sweep
     SDP_META_F_PEER_STORES = 512,  // the backup kernels store J through sdp_store_J (SdpSweepArgs.peer_J: direct exchange)
     SDP_META_F_FAMILY = 1024,      // a family unit (sdp_family_kernel.h): sdp_family_sweep and nothing else
-    SDP_META_F_FAMILY_POLICY = 2048    // a family evaluation unit (sdp_family_policy_kernel.h): sdp_family_evalpol and
+    SDP_META_F_FAMILY_POLICY = 2048,   // a family evaluation unit (sdp_family_policy_kernel.h): sdp_family_evalpol and
                             // sdp_family_evalpol_resident; SDP_META_THREADS is the resident kernel's workgroup size and
                             // SDP_META_COL_ROWS the nodes of a member its two LDS buffers hold
+    SDP_META_F_FAMILY_MC = 4096        // a family Monte Carlo unit (sdp_family_mc_kernel.h): sdp_family_montecarlo and nothing
+                            // else; SDP_META_THREADS is its workgroup size, the trajectories of a tile
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -150,6 +152,36 @@ struct SdpFamilyEvalArgs {
     double tol;
     int32_t *n_done;       // [P]
     double *stats;         // [checks][P][2] (null without a check)
+};
+
+// Monte Carlo policy evaluation of a family (sdp_family_mc_kernel.h, kernel `sdp_family_montecarlo`): SdpMcArgs with
+// a member index in front of every array.  Every member runs the same B trajectory ids over the same steps, each
+// with its own policy, constants, grid ends, seed and law (all laws have n_law points).  A launch runs the steps
+// [step_begin, step_end) of all P members and leaves the states and the sums in the buffers.
+struct SdpFamilyMcArgs {
+    const void *pol;       // [P][nu][S] policies (control VALUES on the state grid), control axis first
+    const void *axes;      // [P][n_axes] concatenated state-grid axes of every member; axis k at axis_off[k]
+    const void *prm;       // [P][SDP_NPARAMS] lifted constants, row p for member p (sdp_model_cell_at)
+    const double *cum;     // [P][n_law] float64 running sums of the laws' probabilities (the last entry is not read)
+    const void *law_grid;  // [P][n_law] perturbation values (reals)
+    const uint64_t *seed;  // [P] Philox keys
+    void *x;               // [P][d][B] states: x at step_begin in, x at step_end out
+    void *acc;             // [P][B] running cost sums (reals)
+    long long *n_outside;  // [P][B] steps k >= n_burn whose x_k lies outside the member's state grid or is NaN
+    unsigned long long *occupancy;   // [P][S] visits of the node nearest to x_k, k >= n_burn (null: not counted)
+    int64_t B;             // trajectories of one member
+    int64_t S;             // state nodes of one member
+    uint64_t traj_offset;  // id of row 0 (Philox counter words 0 and 1 hold traj_offset + row)
+    int64_t step_begin;    // absolute step index (Philox counter words 2 and 3) of this launch's first step
+    int64_t step_end;      // one past its last step
+    int64_t n_burn;        // steps before this one advance the state only
+    double t0;             // time index of step 0 (non-stationary systems)
+    int32_t n_law;         // points of every law (>= 1)
+    int32_t n_axes;        // sum of orders: reals per row of `axes`
+    int32_t P;             // members (>= 1): all of them run
+    int32_t pad_;
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
 };
 
 // Batched closed-loop simulation (the user loop of the reference's examples, e.g.

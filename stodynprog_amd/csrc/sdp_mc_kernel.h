@@ -86,7 +86,10 @@ SDP_DEV void sdp_mc_visit(unsigned long long *occ, int node, bool count)
 #endif
 }
 
+#if !defined(SDP_MC_HELPERS_ONLY)
+// (a family Monte Carlo unit, sdp_family_mc_kernel.h, takes the draw helpers above and brings its own kernel)
 extern "C" __global__ void __launch_bounds__(SDP_MC_THREADS) sdp_montecarlo(SdpMcArgs a)
 {
     sdp_montecarlo_loop<false>(a);     // (sdp_horizon_kernel.h)
 }
+#endif

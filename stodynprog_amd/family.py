@@ -10,8 +10,12 @@ for a solo call, and runs their sweeps together: one launch of kernel `sdp_famil
 one launch of `sdp_family_evalpol` per step, or all steps of a member in one workgroup with its values in LDS
 (`sdp_family_evalpol_resident`); the improvement of policy iteration is the family sweep.
 
+`monte_carlo` scores the members' policies in closed loop together (csrc/sdp_family_mc_kernel.h): one launch of
+`sdp_family_montecarlo` per cut of the steps runs every member's trajectories, a tile of 256 of one member a workgroup;
+with one seed the members see the same draws (common random numbers, `FamilyMonteCarloResult.paired`).
+
 The definition is the solo call: member p of every result equals, bit for bit, what `solvers[p]` returns from the
-same method with `kernel = 'generic'`.
+same method with `kernel = 'generic'` (`monte_carlo`: on its device path, whatever its kernel).
 
 Members may differ in every real constant of dyn / cost, in the ends of the state grid, in the perturbation grid
 and weights, in control_steps and control_box.  They must agree in the grid's shape, the dtype, the number of
@@ -28,6 +32,7 @@ import numpy as np
 from . import _native as nat
 from . import codegen
 from . import convergence as conv
+from . import montecarlo as mc
 from .solver import DPSolver
 from .trace import TraceError, trace_model
 
@@ -146,6 +151,26 @@ class _FamilyProblem(object):
                                                          int(check_every), float(tol), int(bool(resident)),
                                                          nat.ptr(n_done), nat.ptr(stats), nat.ptr(refs)))
         return n_done, stats, refs
+
+    # ---- Monte Carlo evaluation (csrc/sdp_family_mc_kernel.h)
+    def load_mc_unit(self, module):
+        nat.check(nat.lib().sdp_family_load_mc_unit(self.h, module.encode()))
+
+    def montecarlo(self, pol, x0, n_steps, n_burn, seeds, traj_offset, cum, law_grid, t0, steps_per_launch, occupancy):
+        """pol [P][nu][S], x0 [P][d][B], cum / law_grid [P][n_law], seeds [P]: (cost_sum [P][B], n_outside [P][B],
+        x_final [P][d][B], occupancy [P][S] uint64 or None)"""
+        d, B = x0.shape[1], x0.shape[2]
+        assert pol.shape == (self.P, self.nu, self.S) and x0.shape[0] == self.P and cum.shape == law_grid.shape
+        assert all(a.flags.c_contiguous for a in (pol, x0, cum, law_grid, seeds))
+        cost_sum = np.empty((self.P, B), dtype=self.dtype)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, d, B), dtype=self.dtype)
+        occ = np.empty((self.P, self.S), dtype=np.uint64) if occupancy else None
+        nat.check(nat.lib().sdp_family_montecarlo(
+            self.h, nat.ptr(pol), B, int(n_steps), int(n_burn), nat.ptr(seeds), int(traj_offset), nat.ptr(x0),
+            nat.ptr(cum), int(cum.shape[1]), nat.ptr(law_grid), float(t0), int(steps_per_launch), nat.ptr(cost_sum),
+            nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
+        return cost_sum, n_out, x_final, occ
 
     def get_value(self):
         J = np.empty((self.P,) + self.shape, dtype=self.dtype)
@@ -312,14 +337,17 @@ class SolverFamily(object):
         step = max(1, int(self.chunk_bytes) // (self._member_bytes(tabs) + extra))
         return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
 
-    def _run(self, tabs, J0, work, evaluation=False):
+    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None):
         """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims.  evaluation: the
         call evaluates policies, so every handle also loads the family's evaluation unit and the chunks leave room
-        for the prescribed policy"""
+        for the prescribed policy.  mc_bytes: the call is a Monte Carlo run whose arrays take that many bytes a
+        member beside the handle's, so every handle also loads the family's Monte Carlo unit (J0 is None then: the
+        values of a handle that is reused stay what they were)"""
         nat.require_gpu()
         module = nat.compile_model(tabs['source'])
         policy_module = nat.compile_model(codegen.family_policy_unit(tabs['model'], self.dtype)) if evaluation else None
-        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else 0)
+        mc_module = nat.compile_model(codegen.family_mc_unit(tabs['model'], self.dtype)) if mc_bytes is not None else None
+        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else int(mc_bytes or 0))
         digest = hashlib.sha256()
         for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
             if tabs[k] is not None:
@@ -339,8 +367,12 @@ class SolverFamily(object):
                 if evaluation and getattr(prob, 'policy_module', None) != policy_module:
                     prob.load_policy_unit(policy_module)
                     prob.policy_module = policy_module
+                if mc_module is not None and getattr(prob, 'mc_module', None) != mc_module:
+                    prob.load_mc_unit(mc_module)
+                    prob.mc_module = mc_module
                 prob.set_params(tabs['prm'][first:last])
-                prob.set_value(J0[first:last])
+                if J0 is not None:
+                    prob.set_value(J0[first:last])
                 work(prob, first, last)
             finally:
                 if len(chunks) > 1:        # one chunk's arrays on the device at a time
@@ -620,8 +652,142 @@ class SolverFamily(object):
                                      for p in range(self.P)]
         return ((J, J_ref) if rel_dp else J), pol
 
+    # ------------------------------------------------------------------ Monte Carlo evaluation
+    # a run is cut into launches of at most this many steps, as the solo call's; the state stays on the device
+    steps_per_launch = DPSolver.steps_per_launch
+
+    def _mc_seeds(self, seed):
+        """the seed of every member: one integer for all of them (common random numbers) or a sequence of P"""
+        if np.ndim(seed) == 0:
+            return [mc.check_seed(seed)] * self.P
+        seeds = list(seed)
+        if len(seeds) != self.P:
+            raise ValueError('seed: one integer or a sequence of {} (one per member), not {} values'.format(self.P, len(seeds)))
+        return [mc.check_seed(s) for s in seeds]
+
+    def _mc_laws(self, law):
+        """[(grid, proba)] of every member in float64, checked as the solo call checks its law: None (each member's
+        own), one (grid, proba) for all members, or a sequence of P of them.  All have the same number of points."""
+        for p, s in enumerate(self.solvers):
+            if self._law_points(s) == 0:
+                raise NotImplementedError('member {}: a deterministic system has nothing to draw: use simulate(pol, x0, '
+                                          'n_steps=...)'.format(p))
+        if law is None:
+            each = [None] * self.P
+        else:
+            try:
+                shared = len(law) == 2 and np.ndim(law[0][0]) == 0      # (grid, proba): its first entry is a number
+            except (TypeError, IndexError):
+                raise ValueError('law must be (grid, proba), or a sequence of {} of them'.format(self.P))
+            each = [law] * self.P if shared else list(law)
+            if len(each) != self.P:
+                raise ValueError('law: one (grid, proba) or a sequence of {} (one per member), not {}'.format(self.P, len(each)))
+        laws = [s._mc_law(lw) for s, lw in zip(self.solvers, each)]
+        n = len(laws[0][1])
+        rs = self.dtype.itemsize
+        for p, (grid, proba) in enumerate(laws):
+            if len(proba) != n:
+                raise ValueError('member {}: a law of {} points, member 0\'s has {}: the laws of a family have the same '
+                                 'number of points'.format(p, len(proba), n))
+        if (n - 1) * 8 + n * rs > 65536:
+            raise ValueError('a law of {} points needs a draw table of {} bytes: at most 65536'.format(n, (n - 1) * 8 + n * rs))
+        return laws
+
+    def monte_carlo_draws(self, seed, n_traj, n_steps, law=None, traj_offset=0):
+        """`DPSolver.monte_carlo_draws` of every member, stacked (numpy alone): (indices, w) of shapes
+        (P, n_steps, n_traj).  seed and law as in `monte_carlo`."""
+        seeds = self._mc_seeds(seed)
+        laws = self._mc_laws(law)
+        out = [s.monte_carlo_draws(seeds[p], n_traj, n_steps, law=laws[p], traj_offset=traj_offset)
+               for p, s in enumerate(self.solvers)]
+        return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+
+    def _mc_member_bytes(self, B, n_law, occupancy):
+        """bytes of device arrays one member takes in a Monte Carlo run beside _member_bytes (the value, index and
+        box arrays of the handle are allocated with it, so they count): its policy, states and sums, the outside
+        counts, the occupancy, its rows of the draw tables and its seed"""
+        S, d, rs = int(np.prod(self.dims)), len(self.dims), self.dtype.itemsize
+        return (self.nu * S + (d + 1) * B) * rs + 8 * B + (8 * S if occupancy else 0) + n_law * (8 + rs) + 8
+
+    def monte_carlo(self, pol, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False, traj_offset=0, t0=0):
+        """`DPSolver.monte_carlo` of every member in one device call per cut of the steps (kernel
+        sdp_family_montecarlo, csrc/sdp_family_mc_kernel.h): a `montecarlo.FamilyMonteCarloResult`, member p of
+        every field equal, bit for bit, to what `solvers[p].monte_carlo` returns on its device path.
+
+        pol   : (P,) + dims + (nu,), what `policy_iteration` or `value_iteration` returns (or dims + (nu,): every
+                member's policy)
+        x0    : (d,) with n_traj given, (B, d) shared by all members, or (P, B, d)
+        seed  : one integer -- every member then sees the same uniform draws (common random numbers: compare two
+                members with `res.paired(p, q)`) -- or a sequence of P integers
+        law   : None (each member's own law), one (grid, proba) for all members, or a sequence of P of them; all
+                with the same number of points
+        n_burn, occupancy, traj_offset, t0: as in the solo call.
+        Not built: time-indexed policies, models that look data up as data[k], deterministic members."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        laws = self._mc_laws(law)
+        pol = np.asarray(pol)
+        one = self.dims + (self.nu,)
+        if pol.ndim > len(one) + 1 and pol.shape[-len(one):] == one:
+            raise NotImplementedError('pol of shape {}: a time-indexed policy (a leading axis beside the members\') is not '
+                                      'built for families'.format(pol.shape))
+        pol = self._policy(pol)
+        x0 = np.asarray(x0, dtype=float)
+        shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
+        if x0.ndim == 1:
+            if x0.shape != (d,):
+                raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
+            if n_traj is None:
+                raise ValueError('give n_traj with a single start state')
+            if int(n_traj) < 1:
+                raise ValueError('n_traj must be at least 1')
+            x0 = np.broadcast_to(x0, (int(n_traj), d))
+        elif x0.ndim not in (2, 3) or x0.shape[-1] != d or (x0.ndim == 3 and x0.shape[0] != self.P):
+            raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
+        elif n_traj is not None and int(n_traj) != x0.shape[-2]:
+            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[-2]))
+        B = x0.shape[-2]
+        if x0.ndim == 2:
+            x0 = np.broadcast_to(x0, (self.P, B, d))
+        n_steps, n_burn = int(n_steps), int(n_burn)
+        if n_steps < 1 or not 0 <= n_burn < n_steps:
+            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
+        seeds = self._mc_seeds(seed)
+        DPSolver._mc_ids(B, traj_offset)
+        spl = int(self.steps_per_launch)
+        if spl < 1:
+            raise ValueError('steps_per_launch must be at least 1')
+        tabs = self._tables(None if self.stationnary else 0)
+        if tabs['time_specialized']:
+            raise NotImplementedError('the members\' model looks data up at a concrete time index (data[k]): a table of '
+                                      'constants per step is not built for families')
+        # ---- member-major device arrays
+        dt = self.dtype
+        S, n_law = int(np.prod(self.dims)), len(laws[0][1])
+        pol_d = np.ascontiguousarray(np.moveaxis(pol, -1, 1), dtype=dt).reshape(self.P, self.nu, S)       # [P][nu][S]
+        x0_d = np.ascontiguousarray(np.moveaxis(x0, -1, 1), dtype=dt)                                     # [P][d][B]
+        cum = np.ascontiguousarray([mc.cumulative(proba) for _, proba in laws])                           # [P][n_law]
+        law_d = np.ascontiguousarray([grid for grid, _ in laws], dtype=dt)
+        seeds_d = np.array(seeds, dtype=np.uint64)
+        cost_sum = np.empty((self.P, B), dtype=dt)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, B, d), dtype=dt)
+        occ = np.empty((self.P,) + self.dims, dtype=np.int64) if occupancy else None
+
+        def work(prob, a, b):
+            c, n, xf, o = prob.montecarlo(pol_d[a:b], x0_d[a:b], n_steps, n_burn, seeds_d[a:b], traj_offset, cum[a:b],
+                                          law_d[a:b], t0, spl, occupancy)
+            cost_sum[a:b], n_out[a:b], x_final[a:b] = c, n, np.moveaxis(xf, 1, 2)
+            if occupancy:
+                occ[a:b] = o.astype(np.int64).reshape((b - a,) + self.dims)
+        self._run(tabs, None, work, mc_bytes=self._mc_member_bytes(B, n_law, occupancy))
+        self.backend_info['monte_carlo'] = dict(members=self.P, n_traj=B, chunks=self.backend_info['chunks'],
+                                                launches=self.backend_info['chunks'] * (-(-n_steps // min(spl, 1 << 30))))
+        return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
+
     def last_kernel_ms(self):
-        """HIP-event time of the launches of the last sweep call of a family that runs as one chunk (None otherwise)"""
+        """HIP-event time of the launches of the last sweep, evaluation or Monte Carlo call of a family that runs as one
+        chunk (None otherwise)"""
         return self._handle[1].last_kernel_ms() if self._handle is not None else None
 
     def close(self):

@@ -144,6 +144,52 @@ class MonteCarloResult(object):
                                       self.seed, int(self.n_outside.sum()))
 
 
+class FamilyMonteCarloResult(object):
+    """What `SolverFamily.monte_carlo` returns: the fields of `MonteCarloResult` stacked on a leading member axis.
+
+    cost_sum (P, B), cost_mean (P, B), n_outside (P, B), x_final (P, B, d), occupancy (P,) + state dims or None,
+    mean (P,), stderr (P,); `seeds` holds the seed of every member.  len(res) == P and res[p] is the
+    `MonteCarloResult` of member p: its mean and stderr are those of the solo call, bit for bit.
+    Members that ran with one seed and the same trajectory ids saw the same uniform draws (common random numbers):
+    `paired(p, q)` is the mean and the standard error of their per-trajectory difference.
+    """
+
+    def __init__(self, cost_sum, n_outside, x_final, occupancy, n_steps, n_burn, seeds, traj_offset, t0, path):
+        self.cost_sum, self.n_outside, self.x_final, self.occupancy = cost_sum, n_outside, x_final, occupancy
+        self.n_steps, self.n_burn, self.traj_offset, self.t0 = n_steps, n_burn, traj_offset, t0
+        self.seeds = tuple(int(s) for s in seeds)
+        self.n_members, self.n_traj = cost_sum.shape
+        if len(self.seeds) != self.n_members:
+            raise ValueError('{} seeds for {} members'.format(len(self.seeds), self.n_members))
+        self.path = path
+        self._members = [MonteCarloResult(cost_sum[p], n_outside[p], x_final[p],
+                                          None if occupancy is None else occupancy[p], n_steps, n_burn, self.seeds[p],
+                                          traj_offset, t0, path) for p in range(self.n_members)]
+        self.cost_mean = cost_sum.astype(np.float64) / float(n_steps - n_burn)
+        self.mean = np.array([m.mean for m in self._members], dtype=np.float64)
+        self.stderr = np.array([m.stderr for m in self._members], dtype=np.float64)
+
+    def __len__(self):
+        return self.n_members
+
+    def __getitem__(self, p):
+        return self._members[p]
+
+    def paired(self, p, q):
+        """(mean, stderr) of cost_mean[p] - cost_mean[q] over the batch, float64, ddof=1 (stderr NaN for B = 1).
+        Only members that ran with the same seed are paired."""
+        if self.seeds[p] != self.seeds[q]:
+            raise ValueError('members {} and {} ran with different seeds ({} and {}): their trajectories are not '
+                             'paired'.format(p, q, self.seeds[p], self.seeds[q]))
+        diff = self.cost_mean[p] - self.cost_mean[q]
+        stderr = float(diff.std(ddof=1) / np.sqrt(self.n_traj)) if self.n_traj > 1 else float('nan')
+        return float(diff.mean()), stderr
+
+    def __repr__(self):
+        return 'FamilyMonteCarloResult({} members, n_traj={}, n_steps={}, n_burn={}, mean={})'.format(
+            self.n_members, self.n_traj, self.n_steps, self.n_burn, np.array2string(self.mean, precision=6))
+
+
 def nearest_nodes(x, state_grid, dtype):
     """Per axis, the grid node the occupancy counts for states x (..., d): the cell and weight of the
     policy lookup (multilinear_cython.pyx:75-81, in the problem's reals), node = cell + (lam >= 0.5),
