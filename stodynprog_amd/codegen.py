@@ -38,10 +38,12 @@ MAX_PERTURB = 4          # perturbation variables of a generated unit (perturb.M
 DEBUG_INT_MACROS = ('SDP_COL_MIN_WAVES', 'SDP_COL_BATCH', 'SDP_COL_UNROLL_U', 'SDP_COL_UNROLL_W',
                     'SDP_COL_A_GROUP', 'SDP_COL_FILTER_UNROLL', 'SDP_COL_FILTER_TOP2', 'SDP_COL_FILTER_RUNROLL',
                     'SDP_COL_A_WIDE_LOADS', 'SDP_COLU_WIDE_LOADS', 'SDP_COLU_A_GROUP',
-                    'SDP_COL_TAIL_HOLD', 'SDP_SHORT_GROUP', 'SDP_BNB_CHUNK')
+                    'SDP_COL_TAIL_HOLD', 'SDP_SHORT_GROUP', 'SDP_BNB_CHUNK', 'SDP_BNB_LEAN')
 # (SDP_COL_LEAN2 = 0 keeps the resident-chunk kernel on the first pass of section 3.1c: an A/B switch of short_pass_source)
 # (SDP_COL_WRES is a planning switch: it sizes the LDS image -- column_config)
 # (SDP_BNB_UNIFORM = 0 keeps the branch and bound on the bound stage that locates every block end per node: an A/B switch)
+# (SDP_BNB_LEAN = 0 keeps the branch and bound's bookkeeping of before round 9 -- the 64-bit block mask, the per-control
+#  selects of the evaluation: an A/B switch that nothing plans, copied into the unit only when a caller sets it)
 # every name a `debug` dict may carry (a typo must not pass silently)
 DEBUG_NAMES = frozenset(DEBUG_INT_MACROS + (
     'SDP_STAMP', 'SDP_NO_POW2', 'SDP_EXTRA_DEFINES', 'SDP_COL_FILTER_SCALE', 'SDP_LEAD_FILTER_SCALE',

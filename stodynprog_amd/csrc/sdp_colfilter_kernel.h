@@ -1029,6 +1029,9 @@ SDP_DEV void sdp_wide2_pass1(const sdp_real *ad, const sdp_real *utab, const Sdp
 #ifndef SDP_BNB_CHUNK
 #define SDP_BNB_CHUNK (sizeof(SDP_REAL) == 8 ? 4 : 2)      // blocks whose bounds are evaluated together (registers: 8-byte values throughout)
 #endif
+#ifndef SDP_BNB_LEAN
+#define SDP_BNB_LEAN 1                                     // 0: the bookkeeping of sdp_short_bnb before round 9, for A/B runs (see there)
+#endif
 // ---------------------------------------------------------------------------
 // The short first pass as a certified BRANCH AND BOUND over blocks of controls (round 5).
 // A node's filter value is F'(c) = hp_c + L(p_c): hp_c = +-h_c psum from the control table, L the piecewise-linear
@@ -1074,6 +1077,17 @@ SDP_DEV void sdp_wide2_pass1(const sdp_real *ad, const sdp_real *utab, const Sdp
 // - 1 absorbs the roundings of that difference: argued in sdp_col_phase_u, asserted by tests/test_uniform_bound_exact.py);
 // any further row that the clamped extra reads (row k_b - 1 where two ends share a cell) only lowers the bound.  A NaN or an infinity in a row the bound reads keeps
 // the block as before.
+// BOOKKEEPING (SDP_BNB_LEAN, round 9; 0 keeps the earlier form for A/B runs).  Which blocks a lane asks for, and which
+// controls it inserts, is the same set either way -- only how it is written down differs, so that the vector stream holds
+// little beside the arithmetic:
+//  * `need` has 32 bits where the blocks fit; a block's bit is set on its comparison alone, and the two conditions that
+//    do not depend on the bound -- the guess's own block always stays, no block past the lattice -- are applied once,
+//    after the bound stage;
+//  * `extra` = 0 and 1 (wave-uniform; every lattice whose blocks span less than three rows) are straight-line code;
+//  * a trip of the evaluation runs under `if (need)`: the lanes with nothing left are masked out of it instead of
+//    inserting the largest finite number for every control (inserting a block twice would NOT be harmless: the second
+//    smallest value would become the smallest), and where every lane's lattice is whole blocks the trip carries no
+//    clamp and no test of the control's index.  A control past the end is never inserted, as before.
 template <int AXIS, bool WIDE, typename INSERT>
 SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpColFilter &f, const SdpLeadAxis &l,
                            sdp_real X, sdp_real k_rows, int c_lo, int n, int mask, double slack, int guess, INSERT &insert,
@@ -1120,9 +1134,15 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
     sdp_real glam;
     cell(SDP_LEAN2_LEAD(X, ga), gq, glam);
     const double gA0 = row(gq), gA1 = row(gq + 1), gB = brow(gq);
-    unsigned long long need = 0ull;
     double thresh = 0.0;
     constexpr int CB = NB < SDP_BNB_CHUNK ? NB : SDP_BNB_CHUNK;
+    constexpr bool LEAN = SDP_BNB_LEAN != 0;
+    // (the lean form sets the bits of a whole chunk, its blocks past the lattice included: they must fit too)
+    typedef typename std::conditional<LEAN && (NB + CB - 1) / CB * CB <= 32, unsigned, unsigned long long>::type need_t;
+    constexpr bool FITS = (NB + CB - 1) / CB * CB <= (int)(8 * sizeof(need_t));
+    constexpr need_t ONE = 1;
+    need_t need = 0;
+    auto lowest = [](need_t v) -> int { return sizeof(need_t) == 4 ? __ffs((int)v) : __ffsll((long long)v); };
 #if SDP_BNB_UNIFORM_ON
     {
         const char *Ar = (const char *)(A + row_u);        // this lane's row of the (padded) reduced table
@@ -1151,19 +1171,29 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
             for (int j = 0; j <= CB; ++j) P[j] = fma(P[j], Aq1[j] - Aq[j], Aq[j]);       // (P: now L at the end)
 #pragma unroll
             for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(sdp_vmin(P[j], P[j + 1]), sdp_vmin(Aq1[j], Aq[j + 1]));
-            for (int k = 0; k < extra; ++k) {
+            if (LEAN && extra >= 1) {                      // (uniform: the first of them straight-line -- the only one on the benchmark lattice)
+                double more[CB];
+#pragma unroll
+                for (int j = 0; j < CB; ++j) more[j] = at(min(ko[j] + 16, ko[j + 1] - 8));
+#pragma unroll
+                for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(m[j], more[j]);
+            }
+            for (int k = LEAN ? 1 : 0; k < extra; ++k) {
                 double more[CB];
 #pragma unroll
                 for (int j = 0; j < CB; ++j) more[j] = at(min(ko[j] + 16 + 8 * k, ko[j + 1] - 8));
 #pragma unroll
                 for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(m[j], more[j]);
             }
+            unsigned nib = 0u;                             // (lean: the chunk's bits, shifted into place once)
 #pragma unroll
             for (int j = 0; j < CB; ++j) {
                 const double lbv = hp[j] + m[j];
                 // pruned only on a comparison that HOLDS (a NaN anywhere keeps the block); the guess's own block always stays
-                if ((!(lbv > thresh) || b0 + j == g / BS) && b0 + j < n_blocks) need |= 1ull << (b0 + j);
+                if (LEAN) { if (!(lbv > thresh) && (FITS || b0 + j < n_blocks)) nib |= 1u << j; }
+                else if ((!(lbv > thresh) || b0 + j == g / BS) && b0 + j < n_blocks) need |= ONE << (b0 + j);
             }
+            if (LEAN) need |= (need_t)nib << b0;
         }
     }
 #else
@@ -1204,7 +1234,18 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
         }
 #pragma unroll
         for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(sdp_vmin(P[j], P[j + 1]), sdp_vmin(Aq1[j], Aq[j + 1]));
-        for (int k = 0; k < extra; ++k) {                  // (one more row per block on the benchmark lattice)
+        if (LEAN && extra >= 1) {                          // (uniform: the first of them straight-line)
+            double more[CB];
+#pragma unroll
+            for (int j = 0; j < CB; ++j) more[j] = row(max(min(q[j] + 2, q[j + 1] - 1), 0));
+#pragma unroll
+            for (int j = 0; j < CB; ++j) m[j] = sdp_vmin(m[j], more[j]);
+            if (SHIFT) {
+#pragma unroll
+                for (int j = 0; j < CB; ++j) bm[j] = sdp_vmax(bm[j], brow(max(min(q[j] + 2, q[j + 1] - 1), 0)));
+            }
+        }
+        for (int k = LEAN ? 1 : 0; k < extra; ++k) {                  // (one more row per block on the benchmark lattice)
             double more[CB];
 #pragma unroll
             for (int j = 0; j < CB; ++j) more[j] = row(max(min(q[j] + 2 + k, q[j + 1] - 1), 0));
@@ -1215,26 +1256,91 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
                 for (int j = 0; j < CB; ++j) bm[j] = sdp_vmax(bm[j], brow(max(min(q[j] + 2 + k, q[j + 1] - 1), 0)));
             }
         }
+        unsigned nib = 0u;                                 // (lean: the chunk's bits, shifted into place once)
 #pragma unroll
         for (int j = 0; j < CB; ++j) {
             if (q[j + 1] - q[j] - 2 > extra) m[j] = -(double)INFINITY;      // (never seen; a count too small must not cost a row)
             const double lbv = SHIFT ? fma(-BSCALE, bm[j], hp[j] + m[j]) : hp[j] + m[j];
             // pruned only on a comparison that HOLDS (a NaN anywhere keeps the block); the guess's own block always stays
-            if ((!(lbv > thresh) || b0 + j == g / BS) && b0 + j < n_blocks) need |= 1ull << (b0 + j);
+            if (LEAN) { if (!(lbv > thresh) && (FITS || b0 + j < n_blocks)) nib |= 1u << j; }
+            else if ((!(lbv > thresh) || b0 + j == g / BS) && b0 + j < n_blocks) need |= ONE << (b0 + j);
         }
+        if (LEAN) need |= (need_t)nib << b0;
     }
 #endif  // SDP_BNB_UNIFORM_ON
+    if (LEAN) {
+        // no block past the lattice (uniform), and the guess's own block whatever its bound says (0 <= g < n)
+        const need_t live = n_blocks >= (int)(8 * sizeof(need_t)) ? ~(need_t)0 : (ONE << n_blocks) - 1;
+        need = (need & live) | (ONE << ((unsigned)g / (unsigned)BS));
+    }
 #ifdef SDP_DIAG_BNB_COUNT                                  // diagnostic: J := blocks asked for (+ 100 x the guess's block)
-    sdp_diag_cnt = (sdp_real)(__popcll(need) + 100 * (g / BS));
+    sdp_diag_cnt = (sdp_real)((sizeof(need_t) == 4 ? __popc((unsigned)need) : __popcll(need)) + 100 * (g / BS));
 #endif
     // ---- the blocks that stay, lane by lane, groups of controls in stages (a lane reads ITS block's entries of the
     // control table; lanes with nothing left idle through the trip)
+    constexpr int K = SDP_SHORT_GROUP;
+    static_assert(BS % K == 0, "branch and bound: whole groups per block");
+    if (LEAN) {
+        // one block of this lane; WHOLE: every block of the lattice has BS controls
+        auto block = [&](const int b, auto whole_c) {
+            constexpr bool WHOLE = decltype(whole_c)::value;
+            for (int j0 = 0; j0 < BS; j0 += K) {
+                int q0[K], ci[K];
+                sdp_real av[K], lam0[K], hv[K];
+                double a0[K], a1[K], bq[SHIFT ? K : 1];
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    ci[j] = WHOLE ? b * BS + j0 + j : min(b * BS + j0 + j, n - 1);     // (past the end: the last control again, not inserted)
+                    av[j] = utab[ci[j] * SDP_COL_UTAB + SDP_LEAN2_A_SLOT];
+                    hv[j] = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : utab[ci[j] * SDP_COL_UTAB + HS];
+                }
+#pragma unroll
+                for (int j = 0; j < K; ++j) cell(SDP_LEAN2_LEAD(X, av[j]), q0[j], lam0[j]);
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    a0[j] = row(q0[j]);
+                    a1[j] = row(q0[j] + 1);
+                    if (SHIFT) bq[j] = brow(q0[j]);
+                }
+                if (SHIFT) {
+#pragma unroll
+                    for (int j = 0; j < K; ++j)
+                        if (WHOLE || b * BS + j0 + j < n) *b_seen = sdp_vmax(*b_seen, (sdp_real)bq[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const double h = fma((double)lam0[j], a1[j] - a0[j], a0[j]);
+                    const double Fp = pack(SDP_LEAN2_H_SLOT < 0 ? h : fma((double)(SDP_LEAN2_HNEG ? -hv[j] : hv[j]), psum, h), ci[j]);
+                    insert(WHOLE || b * BS + j0 + j < n ? Fp : 0x1.fffffffffffffp+1023);
+                }
+            }
+        };
+        // (a lane leaves the loop with its last block: the others are masked out of the trips that remain)
+        // (a lane leaves the loop with its last block: the others are masked out of the trips that remain)
+        while (need != 0) {
+            const int b = lowest(need) - 1;
+            need &= need - 1;
+            if (b * BS + BS <= n) block(b, std::true_type());
+            else {
+                // the last block of a lattice that is not whole blocks: its controls one by one
+                for (int c = b * BS; c < n; ++c) {
+                    int q;
+                    sdp_real lam;
+                    cell(SDP_LEAN2_LEAD(X, utab[c * SDP_COL_UTAB + SDP_LEAN2_A_SLOT]), q, lam);
+                    const sdp_real hc = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : utab[c * SDP_COL_UTAB + HS];
+                    const double a0 = row(q), a1 = row(q + 1);
+                    if (SHIFT) *b_seen = sdp_vmax(*b_seen, (sdp_real)brow(q));
+                    const double h = fma((double)lam, a1 - a0, a0);
+                    insert(pack(SDP_LEAN2_H_SLOT < 0 ? h : fma((double)(SDP_LEAN2_HNEG ? -hc : hc), psum, h), c));
+                }
+            }
+        }
+        return;
+    }
     while (__any(need != 0ull)) {
         const bool on = need != 0ull;
-        const int b = on ? __ffsll((long long)need) - 1 : 0;
+        const int b = on ? lowest(need) - 1 : 0;
         need &= need - 1ull;
-        constexpr int K = SDP_SHORT_GROUP;
-        static_assert(BS % K == 0, "branch and bound: whole groups per block");
         for (int j0 = 0; j0 < BS; j0 += K) {
             int q0[K], ci[K];
             sdp_real av[K], lam0[K], hv[K];
