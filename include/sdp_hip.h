@@ -530,6 +530,41 @@ int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_t B, int64_
                           int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
                           void *host_x_final, uint64_t *host_occupancy);
 
+/*
+ * One-step lookahead at arbitrary states for a family (csrc/sdp_family_lookahead_kernel.h).  The family's LOOKAHEAD
+ * unit (codegen.family_lookahead_unit: kernels sdp_family_lookahead and, for a stochastic family,
+ * sdp_family_montecarlo_lookahead) is loaded beside the sweep unit; its sdp_meta is checked.
+ */
+int sdp_family_load_lookahead_unit(sdp_family *f, const char *module_path);
+/*
+ * What the unit's box function reads for every member: box_params [P][n_box] float64, the constants of the traced
+ * control_box (n_box must be what the unit was built for), and steps [P][nu] float64, the members' control step
+ * hints (NaN is refused).  To be set after every sdp_family_load_lookahead_unit.
+ */
+int sdp_family_set_lookahead_box(sdp_family *f, const double *box_params, int32_t n_box, const double *steps);
+/*
+ * sdp_problem_lookahead of every member of the handle in one launch, the lattice made on the device: member p at
+ * its B states host_x[p] ([P][d][B] reals) with the cost-to-go of sdp_family_set_value, the constants of
+ * sdp_family_set_params and the box of sdp_family_set_lookahead_box.  host_J [P][B] reals, host_u [P][nu][B] reals,
+ * host_idx [P][B]; a state without a valid lattice gives NaN, NaN, -1.  Member p has the bits of
+ * sdp_problem_lookahead on problem p alone.  SDP_EINVAL for a NULL pointer, a negative size, no unit loaded, no box
+ * set, or values that are not those of sdp_family_set_value.
+ */
+int sdp_family_lookahead(sdp_family *f, int64_t B, const void *host_x, double t_k, void *host_J, void *host_u,
+                         int32_t *host_idx);
+/*
+ * sdp_problem_montecarlo_lookahead of every member of the handle, together, with one cost-to-go per member (the
+ * value array of sdp_family_set_value) for every step: the arguments and results of sdp_family_montecarlo without
+ * the policy.  The law the plant draws from is the caller's; the expectation inside the backup runs over the
+ * member's own law.  n_outside and the occupancy are zeroed before the first launch; sdp_family_last_kernel_ms
+ * covers the call.
+ */
+int sdp_family_montecarlo_lookahead(sdp_family *f, int64_t B, int64_t T, int64_t n_burn, const uint64_t *host_seeds,
+                                    uint64_t traj_offset, const void *host_x0, const double *host_cum, int32_t n_law,
+                                    const void *host_law_grid, double t0, int64_t steps_per_launch,
+                                    void *host_cost_sum, int64_t *host_n_outside, void *host_x_final,
+                                    uint64_t *host_occupancy);
+
 /* ---- tabulated backup (models that cannot be traced into device code) ------- */
 /*
  * Replaces the numeric part of DPSolver._value_at_state_vect

@@ -151,6 +151,11 @@ def _declare(lib):
         'sdp_family_load_mc_unit': (C.c_int, [vp, C.c_char_p]),
         'sdp_family_montecarlo': (C.c_int, [vp, vp, i64, i64, i64, vp, C.c_uint64, vp, vp, i32, vp, dbl, i64, vp, vp,
                                             vp, vp]),
+        'sdp_family_load_lookahead_unit': (C.c_int, [vp, C.c_char_p]),
+        'sdp_family_set_lookahead_box': (C.c_int, [vp, vp, i32, vp]),
+        'sdp_family_lookahead': (C.c_int, [vp, i64, vp, dbl, vp, vp, vp]),
+        'sdp_family_montecarlo_lookahead': (C.c_int, [vp, i64, i64, i64, vp, C.c_uint64, vp, vp, i32, vp, dbl, i64, vp,
+                                                      vp, vp, vp]),
         'sdp_transop_create': (C.c_int, [vp, vp, dbl, P(vp)]),
         'sdp_transop_from_coo': (C.c_int, [C.c_int, i64, i64, vp, vp, vp, P(vp)]),
         'sdp_transop_destroy': (C.c_int, [vp]),

@@ -726,17 +726,31 @@ def line_functions_source(model):
     return '\n\n'.join(out)
 
 
-def box_function_source(box):
+def box_function_source(box, at=False):
     """C++ text of `sdp_model_box(const double *x, double t, double *lo, double *hi)` for a TracedBox: the ends of the
     admissible box of every control at a state, in DOUBLE whatever the unit's reals (csrc/sdp_lookahead_kernel.h
     widens a 4-byte state first, as the host's scalar calls do).  The body is `_emit_body`'s and the np.interp tables
     are `interp_tables_source`'s, printed once more under names of their own with `double` for `sdp_real`: every
     helper the emitter names is a template or has a double overload (csrc/sdp_device.h), so no box that traces is
-    left without its function."""
-    lines = ['SDP_DEV void sdp_model_box(const sdp_real *x, sdp_real t, sdp_real *lo, sdp_real *hi)',
-             '{',
-             '    (void)x; (void)t;']
-    names = _emit_body(box, box.live_nodes(), lines)
+    left without its function.
+    at: `sdp_model_box_at(const double *x, double t, const double *bprm, double *lo, double *hi)` instead, for a box
+    with lifted constants (TracedBox.lift_constants): the same body with `bprm[slot]` in the place of each literal
+    (csrc/sdp_family_lookahead_kernel.h hands over the row of a family's member)."""
+    if at != (getattr(box, 'param_index', None) is not None):
+        raise ValueError('sdp_model_box_at is the function of a box with lifted constants, sdp_model_box of one without')
+    if at:
+        lines = ['SDP_DEV void sdp_model_box_at(const sdp_real *x, sdp_real t, const sdp_real *__restrict__ bprm, sdp_real *lo, sdp_real *hi)',
+                 '{',
+                 '    (void)x; (void)t; (void)bprm;']
+        body = []
+        names = _emit_body(box, box.live_nodes(), body)
+        lines += [ln.replace('sdp_model_prm[', 'bprm[') for ln in body]
+        names = {k: v.replace('sdp_model_prm[', 'bprm[') for k, v in names.items()}
+    else:
+        lines = ['SDP_DEV void sdp_model_box(const sdp_real *x, sdp_real t, sdp_real *lo, sdp_real *hi)',
+                 '{',
+                 '    (void)x; (void)t;']
+        names = _emit_body(box, box.live_nodes(), lines)
     for c, (lo, hi) in enumerate(box.ends):
         lines.append('    lo[{}] = {};'.format(c, names[lo.id]))
         lines.append('    hi[{}] = {};'.format(c, names[hi.id]))
@@ -823,6 +837,29 @@ def family_mc_unit(model, dtype):
     head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
     head.insert(at + 1, '#define SDP_FAMILY_MC 1       // .. and sdp_family_montecarlo in the place of sdp_family_sweep')
     head += ['#include "sdp_family_mc_kernel.h"    // brings in sdp_family_kernel.h and the draw helpers of sdp_mc_kernel.h', '']
+    return '\n'.join(head)
+
+
+def family_lookahead_unit(model, box, dtype, lanes):
+    """The generated source of a family LOOKAHEAD unit (csrc/sdp_family_lookahead_kernel.h, kernels
+    `sdp_family_lookahead` and `sdp_family_montecarlo_lookahead`): the direct prologue of a model with lifted
+    constants, marked SDP_FAMILY and SDP_FAMILY_LOOKAHEAD, the box function of a TracedBox with lifted constants
+    (`sdp_model_box_at`, SDP_NBOXPARAMS of them per member) and the lookahead header in the place of
+    sdp_sweep_kernel.h.  `lanes` is the largest lane count of the members: the lanes of a state's control loop."""
+    if model.param_index is None or getattr(box, 'param_index', None) is None:
+        raise ValueError('a family lookahead unit takes a model and a box with lifted constants (lift_constants)')
+    if model.n_perturb >= 2:
+        raise NotImplementedError('a family unit takes one perturbation variable at most')
+    if box.t_value is not None or box.inexact_ops():
+        raise ValueError('the box function of a lookahead unit is a trace with a symbolic time index and exact operations')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, lanes, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
+    head.insert(at + 1, '#define SDP_FAMILY_LOOKAHEAD 1   // .. and the two lookahead kernels in the place of sdp_family_sweep')
+    head += ['#define SDP_NBOXPARAMS {}     // constants of the box function, read from the member\'s row'.format(len(box.param_index)),
+             box_function_source(box, at=True), '',
+             '#include "sdp_family_lookahead_kernel.h"    // brings in sdp_family_kernel.h, the lattice rule and the draw helpers', '']
     return '\n'.join(head)
 
 
@@ -1521,8 +1558,9 @@ def source_key(source):
         with open(os.path.join(CSRC, 'sdp_multiw_kernel.h'), 'rb') as f:
             h.update(f.read())
     if '#define SDP_LOOKAHEAD ' in source:
-        with open(os.path.join(CSRC, 'sdp_lookahead_kernel.h'), 'rb') as f:
-            h.update(f.read())
+        for fn in ('sdp_lookahead_kernel.h', 'sdp_lattice_kernel.h'):
+            with open(os.path.join(CSRC, fn), 'rb') as f:
+                h.update(f.read())
     if '#define SDP_FAMILY ' in source:
         with open(os.path.join(CSRC, 'sdp_family_kernel.h'), 'rb') as f:
             h.update(f.read())
@@ -1532,6 +1570,11 @@ def source_key(source):
     if '#define SDP_FAMILY_MC ' in source:
         with open(os.path.join(CSRC, 'sdp_family_mc_kernel.h'), 'rb') as f:
             h.update(f.read())
+    if '#define SDP_FAMILY_LOOKAHEAD ' in source:
+        # (it includes sdp_family_kernel.h, above, sdp_mc_kernel.h, one of _HEADERS, and the lattice rule)
+        for fn in ('sdp_family_lookahead_kernel.h', 'sdp_lattice_kernel.h'):
+            with open(os.path.join(CSRC, fn), 'rb') as f:
+                h.update(f.read())
     h.update(source.encode())
     h.update(' '.join(HIPCC_FLAGS[:-1]).encode())
     h.update(compiler_identity().encode())

@@ -3775,6 +3775,13 @@ struct sdp_family {
     // Monte Carlo evaluation (sdp_family_load_mc_unit): the unit and its kernel; the arrays of a run live for the call
     hipModule_t mcmod = nullptr;
     hipFunction_t f_montecarlo = nullptr;
+    // lookahead at arbitrary states (sdp_family_load_lookahead_unit): the unit, its two kernels, the lanes of a state and
+    // the constants of its box function per member; the members' box constants and control steps (sdp_family_set_lookahead_box)
+    hipModule_t lkmod = nullptr;
+    hipFunction_t f_lookahead = nullptr, f_mc_lookahead = nullptr;
+    int look_lanes = 0, n_box = 0;
+    DevBuf bprm, look_steps;
+    bool has_look_box = false;
     int cur = 0;                           // buf[cur] is read (V), buf[cur ^ 1] written (J)
     std::vector<int32_t> active;           // the members the next launch runs
     std::vector<int> where;                // [P] the buffer that holds the member's latest values
@@ -3792,6 +3799,7 @@ struct sdp_family {
         if (mod) (void)hipModuleUnload(mod);
         if (pmod) (void)hipModuleUnload(pmod);
         if (mcmod) (void)hipModuleUnload(mcmod);
+        if (lkmod) (void)hipModuleUnload(lkmod);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -4561,6 +4569,226 @@ extern "C" int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_
         a.step_begin = k;
         a.step_end = (T - k < steps_per_launch) ? T : k + steps_per_launch;
         HIP_TRY(hipModuleLaunchKernel(f->f_montecarlo, (unsigned)(per_xcd * 8), 1, 1, threads, 1, 1, lds, f->stream, nullptr, extra));
+    }
+    HIP_TRY(hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    f->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, P * (size_t)f->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One-step lookahead at arbitrary states, and its Monte Carlo score, for a family (csrc/sdp_family_lookahead_kernel.h):
+// sdp_problem_lookahead and sdp_problem_montecarlo_lookahead of every member in one launch (per cut of the steps).  The
+// unit is loaded beside the sweep unit; J_next is the handle's value array (sdp_family_set_value).
+// ---------------------------------------------------------------------------
+extern "C" int sdp_family_load_lookahead_unit(sdp_family *f, const char *module_path)
+{
+    if (!f || !module_path) return fail(SDP_EINVAL, "NULL argument");
+    if (f->lkmod) { (void)hipModuleUnload(f->lkmod); f->lkmod = nullptr; f->f_lookahead = nullptr; f->f_mc_lookahead = nullptr; }
+    f->has_look_box = false;
+    const size_t rs = real_size(f->dtype);
+    hipError_t e = hipModuleLoad(&f->lkmod, module_path);
+    if (e != hipSuccess) { f->lkmod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", module_path, hipGetErrorString(e)); }
+    int32_t m[SDP_META_WORDS] = {0};
+    hipDeviceptr_t mptr = nullptr;
+    size_t mbytes = 0;
+    const char *why = nullptr;
+    if (hipModuleGetGlobal(&mptr, &mbytes, f->lkmod, "sdp_meta") != hipSuccess || mbytes != sizeof(m)) {
+        (void)hipGetLastError();
+        why = "it does not declare `sdp_meta`";
+    } else {
+        HIP_TRY(hipMemcpyDtoH(m, mptr, sizeof(m)));
+        if (m[SDP_META_MAGIC_AT] != SDP_META_MAGIC) why = "bad magic";
+        else if (!(m[SDP_META_FLAGS] & SDP_META_F_FAMILY_LOOKAHEAD)) why = "not a family lookahead unit";
+        else if (m[SDP_META_THREADS] != 256) why = "built for another workgroup size";
+        else if (m[SDP_META_REAL_BYTES] != (int)rs) why = "built for other reals";
+        else if (m[SDP_META_D] != f->d) why = "built for another number of state variables";
+        else if (m[SDP_META_NU] != f->nu) why = "built for another number of controls";
+        else if ((m[SDP_META_HAS_W] != 0) != (f->W > 0)) why = "built for another kind of perturbation";
+        else if (m[SDP_META_COL_ROWS] < 1 || m[SDP_META_COL_ROWS] > 64 || (m[SDP_META_COL_ROWS] & (m[SDP_META_COL_ROWS] - 1))) why = "its lanes per state are no power of two in 1..64";
+        else if (m[SDP_META_UTAB] < 0) why = "a negative number of box constants";
+    }
+    hipDeviceptr_t pptr = nullptr;
+    size_t pbytes = 0;
+    if (!why) {
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->lkmod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs) why = "another number of lifted constants";
+    }
+    if (!why && hipModuleGetFunction(&f->f_lookahead, f->lkmod, "sdp_family_lookahead") != hipSuccess) why = "no sdp_family_lookahead kernel";
+    if (!why && f->W > 0 && hipModuleGetFunction(&f->f_mc_lookahead, f->lkmod, "sdp_family_montecarlo_lookahead") != hipSuccess)
+        why = "no sdp_family_montecarlo_lookahead kernel";
+    if (why) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(f->lkmod);
+        f->lkmod = nullptr; f->f_lookahead = nullptr; f->f_mc_lookahead = nullptr;
+        return fail(SDP_EMODULE, "code object %s was not built for this family's lookahead: %s", module_path, why);
+    }
+    f->look_lanes = m[SDP_META_COL_ROWS];
+    f->n_box = m[SDP_META_UTAB];
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_set_lookahead_box(sdp_family *f, const double *box_params, int32_t n_box, const double *steps)
+{
+    if (!f || !steps || n_box < 0 || (n_box > 0 && !box_params)) return fail(SDP_EINVAL, "sdp_family_set_lookahead_box: bad arguments");
+    if (!f->f_lookahead) return fail(SDP_EINVAL, "no lookahead unit loaded (sdp_family_load_lookahead_unit)");
+    if (n_box != f->n_box)
+        return fail(SDP_EINVAL, "sdp_family_set_lookahead_box: the unit's box function has %d constant(s) per member, %d given", f->n_box, (int)n_box);
+    const size_t P = (size_t)f->P;
+    for (size_t i = 0; i < P * (size_t)f->nu; ++i)
+        if (!(steps[i] == steps[i])) return fail(SDP_EINVAL, "sdp_family_set_lookahead_box: control step hint %zu of member %zu is NaN", i % f->nu, i / f->nu);
+    f->has_look_box = false;
+    int rc;
+    HIP_TRY(hipStreamSynchronize(f->stream));        // (launches that still read the old rows)
+    // (a row of at least one double, so that a box without constants still has a table to point to)
+    if ((rc = f->bprm.alloc(P * (size_t)(n_box > 0 ? n_box : 1) * 8))) return rc;
+    if (n_box > 0) HIP_TRY(hipMemcpy(f->bprm.p, box_params, P * (size_t)n_box * 8, hipMemcpyHostToDevice));
+    if ((rc = upload(f->look_steps, steps, P * (size_t)f->nu * 8))) return rc;
+    f->has_look_box = true;
+    return SDP_OK;
+}
+
+// what both lookahead launches start from: the unit, the members' box rows, J_next of every member in buf[cur]
+static int family_lookahead_checks(const sdp_family *f, const char *what)
+{
+    if (!f->f_lookahead) return fail(SDP_EINVAL, "%s: no lookahead unit loaded (sdp_family_load_lookahead_unit)", what);
+    if (!f->has_look_box) return fail(SDP_EINVAL, "%s: the members' box constants and control steps are not set (sdp_family_set_lookahead_box)", what);
+    for (int p = 0; p < f->P; ++p)
+        if (f->where[(size_t)p] != f->cur)
+            return fail(SDP_EINVAL, "%s: the cost-to-go is the value array of sdp_family_set_value: set it before the call", what);
+    return SDP_OK;
+}
+
+static void family_lookahead_block(const sdp_family *f, SdpFamilyArgs &a, double t_k)
+{
+    memset(&a, 0, sizeof(a));
+    a.V = f->buf[f->cur].p;
+    a.axes = f->axes.p; a.wgrid = f->wgrid.p; a.proba = f->proba.p; a.prm = f->prm.p;
+    a.S = f->S; a.t_k = t_k;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = f->orders[k]; a.axis_off[k] = f->axis_off[k]; }
+    a.n_axes = f->n_axes; a.W = f->W; a.box_per_node = 0; a.n_active = f->P;
+}
+
+// a tile of (64 / lanes) * 4 states of one member is a workgroup of 256.  A multiple of 8 workgroups (one share per XCD,
+// sdp_family_lookahead_kernel.h): per XCD as many as it has tiles to walk, in all at most the workgroups that are resident
+// at once (8 per CU at most), the rest in the stride loop
+static unsigned family_lookahead_grid(const sdp_family *f, hipFunction_t fn, int64_t B, unsigned lds)
+{
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 8) per_cu = 8;
+    const int64_t tile = (int64_t)(64 / f->look_lanes) * 4;
+    const int64_t tiles = (B + tile - 1) / tile;
+    const int parts = f->P >= 8 ? 1 : 8 / f->P;
+    int64_t per_xcd = f->P >= 8 ? (int64_t)((f->P + 7) / 8) * tiles : (tiles + parts - 1) / parts;
+    const int64_t cap = (int64_t)f->cus * per_cu / 8;
+    if (per_xcd > cap) per_xcd = cap;
+    if (per_xcd < 1) per_xcd = 1;
+    return (unsigned)(per_xcd * 8);
+}
+
+extern "C" int sdp_family_lookahead(sdp_family *f, int64_t B, const void *host_x, double t_k, void *host_J, void *host_u,
+                                    int32_t *host_idx)
+{
+    if (!f || !host_x || !host_J || !host_u || !host_idx) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0) return fail(SDP_EINVAL, "negative size");
+    int rc;
+    if ((rc = family_lookahead_checks(f, "sdp_family_lookahead"))) return rc;
+    if (B == 0) return SDP_OK;
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    DevBuf dx, dJ, du, didx;
+    if ((rc = upload(dx, host_x, P * (size_t)f->d * B * rs))) return rc;                  // [P][d][B]
+    if ((rc = dJ.alloc(P * (size_t)B * rs))) return rc;
+    if ((rc = du.alloc(P * (size_t)f->nu * B * rs))) return rc;
+    if ((rc = didx.alloc(P * (size_t)B * 4))) return rc;
+    SdpFamilyLookArgs a;
+    memset(&a, 0, sizeof(a));
+    family_lookahead_block(f, a.f, t_k);
+    a.bprm = (const double *)f->bprm.p; a.steps = (const double *)f->look_steps.p;
+    a.x = dx.p; a.J = dJ.p; a.idx = (int32_t *)didx.p; a.u = du.p; a.B = B;
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    const unsigned blocks = family_lookahead_grid(f, f->f_lookahead, B, 0);
+    HIP_TRY(hipStreamSynchronize(f->stream));        // lifted constants and values set on the family's stream
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    HIP_TRY(hipModuleLaunchKernel(f->f_lookahead, blocks, 1, 1, 256, 1, 1, 0, f->stream, nullptr, extra));
+    HIP_TRY(hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    f->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_J, dJ.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_u, du.p, P * (size_t)f->nu * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_idx, didx.p, P * (size_t)B * 4, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_montecarlo_lookahead(sdp_family *f, int64_t B, int64_t T, int64_t n_burn, const uint64_t *host_seeds,
+                                               uint64_t traj_offset, const void *host_x0, const double *host_cum, int32_t n_law,
+                                               const void *host_law_grid, double t0, int64_t steps_per_launch,
+                                               void *host_cost_sum, int64_t *host_n_outside, void *host_x_final,
+                                               uint64_t *host_occupancy)
+{
+    if (!f || !host_seeds || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0 || T < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (f->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    int rc;
+    if ((rc = family_lookahead_checks(f, "sdp_family_montecarlo_lookahead"))) return rc;
+    if (!f->f_mc_lookahead) return fail(SDP_EINVAL, "the lookahead unit has no sdp_family_montecarlo_lookahead kernel");
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    // (the draw table of one member in LDS: the cumulative sums, then the values)
+    const size_t lds_bytes = (size_t)(n_law - 1) * 8 + (size_t)n_law * rs;
+    if (lds_bytes > 65536)
+        return fail(SDP_EINVAL, "a law of %d points needs %zu bytes of LDS: at most 65536", (int)n_law, lds_bytes);
+    DevBuf dx, dacc, dout, dcum, dlaw, dseed, docc;
+    if ((rc = upload(dx, host_x0, P * (size_t)f->d * B * rs))) return rc;                 // [P][d][B]
+    if ((rc = upload(dcum, host_cum, P * (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, P * (size_t)n_law * rs))) return rc;
+    if ((rc = upload(dseed, host_seeds, P * 8))) return rc;
+    if ((rc = dacc.alloc(P * (size_t)B * rs))) return rc;
+    if ((rc = dout.alloc(P * (size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, P * (size_t)B * rs, f->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, P * (size_t)B * 8, f->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc(P * (size_t)f->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, P * (size_t)f->S * 8, f->stream));
+    }
+    SdpFamilyLookMcArgs a;
+    memset(&a, 0, sizeof(a));
+    family_lookahead_block(f, a.f, t0);
+    a.bprm = (const double *)f->bprm.p; a.steps = (const double *)f->look_steps.p;
+    a.cum = (const double *)dcum.p; a.law_grid = dlaw.p; a.seed = (const uint64_t *)dseed.p;
+    a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.traj_offset = traj_offset; a.n_burn = n_burn; a.t0 = t0; a.n_law = n_law;
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    const unsigned lds = (unsigned)lds_bytes;
+    const unsigned blocks = family_lookahead_grid(f, f->f_mc_lookahead, B, lds);
+    HIP_TRY(hipStreamSynchronize(f->stream));        // lifted constants and values set on the family's stream
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int64_t k = 0; k < T; k += steps_per_launch) {
+        a.step_begin = k;
+        a.step_end = (T - k < steps_per_launch) ? T : k + steps_per_launch;
+        HIP_TRY(hipModuleLaunchKernel(f->f_mc_lookahead, blocks, 1, 1, 256, 1, 1, lds, f->stream, nullptr, extra));
     }
     HIP_TRY(hipEventRecord(f->ev1, f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream));

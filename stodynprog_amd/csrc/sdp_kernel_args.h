@@ -39,8 +39,11 @@ enum {
     SDP_META_F_FAMILY_POLICY = 2048,   // a family evaluation unit (sdp_family_policy_kernel.h): sdp_family_evalpol and
                             // sdp_family_evalpol_resident; SDP_META_THREADS is the resident kernel's workgroup size and
                             // SDP_META_COL_ROWS the nodes of a member its two LDS buffers hold
-    SDP_META_F_FAMILY_MC = 4096        // a family Monte Carlo unit (sdp_family_mc_kernel.h): sdp_family_montecarlo and nothing
+    SDP_META_F_FAMILY_MC = 4096,       // a family Monte Carlo unit (sdp_family_mc_kernel.h): sdp_family_montecarlo and nothing
                             // else; SDP_META_THREADS is its workgroup size, the trajectories of a tile
+    SDP_META_F_FAMILY_LOOKAHEAD = 8192 // a family lookahead unit (sdp_family_lookahead_kernel.h): sdp_family_lookahead and
+                            // sdp_family_montecarlo_lookahead; SDP_META_THREADS is their workgroup size, SDP_META_COL_ROWS the
+                            // lanes of a state (SDP_LANES) and SDP_META_UTAB the constants of the box function per member
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -182,6 +185,46 @@ struct SdpFamilyMcArgs {
     int32_t pad_;
     int32_t orders[SDP_MAXD];
     int32_t axis_off[SDP_MAXD];
+};
+
+// One-step lookahead at arbitrary states for a family (sdp_family_lookahead_kernel.h, kernel `sdp_family_lookahead`):
+// SdpLookArgs with a member index in front of every array and the lattice always made on the device, by the unit's
+// `sdp_model_box_at` on the member's row of box constants.  `f` is the block of the sweep with `f.V` the cost-to-go
+// J_next [P][S]; its box arrays, `f.J`, `f.pol`, `f.idx` and `f.members` are unused (null) and `f.n_active` is P: all
+// members run, each on its own B states.
+struct SdpFamilyLookArgs {
+    SdpFamilyArgs f;
+    const double *bprm;    // [P][SDP_NBOXPARAMS] constants of the box function, row p for member p (float64 whatever the reals)
+    const double *steps;   // [P][nu] control step hints (DPSolver.control_steps of every member)
+    const void *x;         // [P][d][B] states
+    void *J;               // [P][B] minimised expected value
+    int32_t *idx;          // [P][B] flat C-order index of the optimal control in the state's lattice
+    void *u;               // [P][nu][B] optimal control VALUES
+    int64_t B;             // states of one member
+};
+
+// Monte Carlo evaluation under lookahead controls for a family (kernel `sdp_family_montecarlo_lookahead`): SdpLookMcArgs
+// with a member index in front of every array, one cost-to-go per member for every step.  The law the backup sums
+// over (f.wgrid, f.proba) is the member's own; the law the plant draws from (cum, law_grid) is the caller's.
+struct SdpFamilyLookMcArgs {
+    SdpFamilyArgs f;       // as SdpFamilyLookArgs (f.t_k is not read: the time index of step k is t0 + k)
+    const double *bprm;    // [P][SDP_NBOXPARAMS]
+    const double *steps;   // [P][nu]
+    const double *cum;     // [P][n_law] float64 running sums of the drawn laws' probabilities (the last entry is not read)
+    const void *law_grid;  // [P][n_law] drawn perturbation values (reals)
+    const uint64_t *seed;  // [P] Philox keys
+    void *x;               // [P][d][B] states: x at step_begin in, x at step_end out
+    void *acc;             // [P][B] running cost sums (reals)
+    long long *n_outside;  // [P][B] steps k >= n_burn whose x_k lies outside the member's state grid or is NaN
+    unsigned long long *occupancy;   // [P][S] visits of the node nearest to x_k, k >= n_burn (null: not counted)
+    int64_t B;             // trajectories of one member
+    uint64_t traj_offset;  // id of row 0 (Philox counter words 0 and 1 hold traj_offset + row)
+    int64_t step_begin;    // step of the call (Philox counter words 2 and 3) of this launch's first step
+    int64_t step_end;      // one past its last step
+    int64_t n_burn;        // steps before this one advance the state only
+    double t0;             // time index of step 0 of the call
+    int32_t n_law;         // points of every drawn law (>= 1)
+    int32_t pad_;
 };
 
 // Batched closed-loop simulation (the user loop of the reference's examples, e.g.

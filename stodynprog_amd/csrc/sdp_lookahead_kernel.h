@@ -48,17 +48,7 @@ SDP_DEV void sdp_look_sweep_args(const Args &a, SdpSweepArgs &s)
     for (int k = 0; k < SDP_MAXD; ++k) { s.orders[k] = a.orders[k]; s.axis_off[k] = a.axis_off[k]; }
 }
 
-// what sdp_load_box derives from (lo, hi, n)
-SDP_DEV void sdp_look_finish_box(SdpBox &b)
-{
-    b.total = 1;
-#pragma unroll
-    for (int c = 0; c < SDP_NU; ++c) {
-        b.delta[c] = b.hi[c] - b.lo[c];
-        b.step[c] = (b.n[c] > 1) ? b.delta[c] / (sdp_real)(b.n[c] - 1) : (sdp_real)0;
-        b.total *= b.n[c];
-    }
-}
+#include "sdp_lattice_kernel.h"  // sdp_look_finish_box, sdp_look_lattice: the lattice rule, shared with the family lookahead kernels
 
 // the lattice of state b from host-made arrays [nu][B]; false: the state has none
 SDP_DEV bool sdp_look_box_host(const void *box_lo, const void *box_hi, const int32_t *box_n, int64_t B, int64_t b, SdpBox &box)
@@ -76,33 +66,10 @@ SDP_DEV bool sdp_look_box_host(const void *box_lo, const void *box_hi, const int
 
 #if defined(SDP_LOOKAHEAD_BOX)
 // the lattice of the state x from the unit's own box function: DPSolver._box_lattice in double, one rounding
+// (sdp_lattice_kernel.h)
 SDP_DEV bool sdp_look_box_device(const sdp_real *x, double t, const double *steps, SdpBox &box)
 {
-    double xd[SDP_D], lo[SDP_NU], hi[SDP_NU];
-#pragma unroll
-    for (int k = 0; k < SDP_D; ++k) xd[k] = (double)x[k];
-    sdp_model_box(xd, t, lo, hi);
-    bool ok = true;
-    double total = 1.0;
-#pragma unroll
-    for (int c = 0; c < SDP_NU; ++c) {
-        const double n_interv = (hi[c] - lo[c]) / steps[c];
-        const bool single = n_interv < 0.1;
-        const double npts = single ? 1.0 : ceil(n_interv) + 1.0;
-        ok = ok && fabs(lo[c]) < (double)INFINITY && fabs(hi[c]) < (double)INFINITY && npts < 2147483648.0;
-        const double mid = (lo[c] + hi[c]) / 2;
-        box.lo[c] = (sdp_real)(single ? mid : lo[c]);
-        box.hi[c] = (sdp_real)(single ? mid : hi[c]);
-        box.n[c] = ok ? (int)npts : 0;
-        total *= npts;
-    }
-    ok = ok && total < 2147483648.0;
-    if (!ok) {
-#pragma unroll
-        for (int c = 0; c < SDP_NU; ++c) box.n[c] = 0;
-    }
-    sdp_look_finish_box(box);
-    return ok;
+    return sdp_look_lattice(x, steps, box, [t](const double *xd, double *lo, double *hi) { sdp_model_box(xd, t, lo, hi); });
 }
 #endif
 

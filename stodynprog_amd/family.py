@@ -14,8 +14,14 @@ one launch of `sdp_family_evalpol` per step, or all steps of a member in one wor
 `sdp_family_montecarlo` per cut of the steps runs every member's trajectories, a tile of 256 of one member a workgroup;
 with one seed the members see the same draws (common random numbers, `FamilyMonteCarloResult.paired`).
 
+`lookahead` and `monte_carlo_lookahead` decide at arbitrary states, and score the members in closed loop under those
+decisions -- the controller that would run -- together (csrc/sdp_family_lookahead_kernel.h): kernels
+`sdp_family_lookahead` and `sdp_family_montecarlo_lookahead`, a tile of (64 / lanes) x 4 states of one member a
+workgroup, every lattice made on the device from the member's traced control_box with its constants lifted.
+
 The definition is the solo call: member p of every result equals, bit for bit, what `solvers[p]` returns from the
-same method with `kernel = 'generic'` (`monte_carlo`: on its device path, whatever its kernel).
+same method with `kernel = 'generic'` (`monte_carlo`, `lookahead`, `monte_carlo_lookahead`: on its device path,
+whatever its kernel).
 
 Members may differ in every real constant of dyn / cost, in the ends of the state grid, in the perturbation grid
 and weights, in control_steps and control_box.  They must agree in the grid's shape, the dtype, the number of
@@ -172,6 +178,43 @@ class _FamilyProblem(object):
             nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
         return cost_sum, n_out, x_final, occ
 
+    # ---- lookahead at arbitrary states (csrc/sdp_family_lookahead_kernel.h)
+    def load_lookahead_unit(self, module):
+        nat.check(nat.lib().sdp_family_load_lookahead_unit(self.h, module.encode()))
+
+    def set_lookahead_box(self, bprm, steps):
+        """bprm [P][n_box] float64, the constants of every member's box; steps [P][nu] float64, its control steps"""
+        bprm = np.ascontiguousarray(bprm, dtype=np.float64)
+        steps = np.ascontiguousarray(steps, dtype=np.float64)
+        assert bprm.shape[0] == self.P and steps.shape == (self.P, self.nu)
+        nat.check(nat.lib().sdp_family_set_lookahead_box(self.h, nat.ptr(bprm) if bprm.size else None, int(bprm.shape[1]),
+                                                         nat.ptr(steps)))
+
+    def lookahead(self, x, t_k):
+        """x [P][d][B] at the values set: (J [P][B], u [P][nu][B], idx [P][B])"""
+        B = x.shape[2]
+        assert x.shape[0] == self.P and x.flags.c_contiguous and x.dtype == self.dtype
+        J = np.empty((self.P, B), dtype=self.dtype)
+        u = np.empty((self.P, self.nu, B), dtype=self.dtype)
+        idx = np.empty((self.P, B), dtype=np.int32)
+        nat.check(nat.lib().sdp_family_lookahead(self.h, B, nat.ptr(x), float(t_k), nat.ptr(J), nat.ptr(u), nat.ptr(idx)))
+        return J, u, idx
+
+    def montecarlo_lookahead(self, x0, n_steps, n_burn, seeds, traj_offset, cum, law_grid, t0, steps_per_launch, occupancy):
+        """x0 [P][d][B], cum / law_grid [P][n_law], seeds [P], at the values set: what `montecarlo` returns"""
+        d, B = x0.shape[1], x0.shape[2]
+        assert x0.shape[0] == self.P and cum.shape == law_grid.shape
+        assert all(a.flags.c_contiguous for a in (x0, cum, law_grid, seeds))
+        cost_sum = np.empty((self.P, B), dtype=self.dtype)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, d, B), dtype=self.dtype)
+        occ = np.empty((self.P, self.S), dtype=np.uint64) if occupancy else None
+        nat.check(nat.lib().sdp_family_montecarlo_lookahead(
+            self.h, B, int(n_steps), int(n_burn), nat.ptr(seeds), int(traj_offset), nat.ptr(x0), nat.ptr(cum),
+            int(cum.shape[1]), nat.ptr(law_grid), float(t0), int(steps_per_launch), nat.ptr(cost_sum), nat.ptr(n_out),
+            nat.ptr(x_final), nat.ptr(occ)))
+        return cost_sum, n_out, x_final, occ
+
     def get_value(self):
         J = np.empty((self.P,) + self.shape, dtype=self.dtype)
         nat.check(nat.lib().sdp_family_get_value(self.h, nat.ptr(J)))
@@ -208,18 +251,22 @@ def _trace_member(s, t_k=None):
     return model
 
 
-def _structure_message(p, model, first, where=''):
-    """why member p cannot share member 0's code object"""
+def _structure_message(p, model, first, where='', what=('model', 'dyn / cost')):
+    """why member p cannot share member 0's code object (`what`: how the message names the trace -- the model's, or
+    that of control_box, a TracedBox)"""
     n_p, n_0 = len(model.param_values()), len(first.param_values())
     ops = lambda m: [n.op for n in m.live_nodes() if n.op != 'const']
     if n_p != n_0 and ops(model) == ops(first):
         # the trace shares equal constants (one node for h and for c where h == c): the DAG has another shape
         few = p if n_p < n_0 else 0
-        return ('member {}{}: constants that coincide in member {} make its traced model another structure ({} distinct '
+        return ('member {}{}: constants that coincide in member {} make its traced {} another structure ({} distinct '
                 'constants against {}): equal values are one node of the trace.  Give the coinciding constants '
-                'different values, or solve that member alone'.format(p, where, few, min(n_p, n_0), max(n_p, n_0)))
-    return ('member {}{}: the structure of the traced dyn / cost differs from member 0\'s (another expression, another '
-            'np.interp table, or a different time dependence)'.format(p, where))
+                'different values, or solve that member alone'.format(p, where, few, what[0], min(n_p, n_0), max(n_p, n_0)))
+    return ('member {}{}: the structure of the traced {} differs from member 0\'s (another expression, another '
+            'np.interp table, or a different time dependence)'.format(p, where, what[1]))
+
+
+_BOX = ('control_box', 'control_box')
 
 
 class SolverFamily(object):
@@ -337,17 +384,20 @@ class SolverFamily(object):
         step = max(1, int(self.chunk_bytes) // (self._member_bytes(tabs) + extra))
         return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
 
-    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None):
+    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None):
         """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims.  evaluation: the
         call evaluates policies, so every handle also loads the family's evaluation unit and the chunks leave room
         for the prescribed policy.  mc_bytes: the call is a Monte Carlo run whose arrays take that many bytes a
         member beside the handle's, so every handle also loads the family's Monte Carlo unit (J0 is None then: the
-        values of a handle that is reused stay what they were)"""
+        values of a handle that is reused stay what they were).  look: the call is a lookahead (`_lookahead_tables`:
+        source, bprm, steps, bytes a member takes beside the handle's), so every handle also loads the family's
+        lookahead unit and is given its members' box constants and control steps"""
         nat.require_gpu()
         module = nat.compile_model(tabs['source'])
+        look_module = nat.compile_model(look['source']) if look is not None else None
         policy_module = nat.compile_model(codegen.family_policy_unit(tabs['model'], self.dtype)) if evaluation else None
         mc_module = nat.compile_model(codegen.family_mc_unit(tabs['model'], self.dtype)) if mc_bytes is not None else None
-        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else int(mc_bytes or 0))
+        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else int(mc_bytes or 0) + (look['bytes'] if look else 0))
         digest = hashlib.sha256()
         for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
             if tabs[k] is not None:
@@ -370,6 +420,11 @@ class SolverFamily(object):
                 if mc_module is not None and getattr(prob, 'mc_module', None) != mc_module:
                     prob.load_mc_unit(mc_module)
                     prob.mc_module = mc_module
+                if look_module is not None:
+                    if getattr(prob, 'look_module', None) != look_module:
+                        prob.load_lookahead_unit(look_module)
+                        prob.look_module = look_module
+                    prob.set_lookahead_box(look['bprm'][first:last], look['steps'][first:last])
                 prob.set_params(tabs['prm'][first:last])
                 if J0 is not None:
                     prob.set_value(J0[first:last])
@@ -781,6 +836,164 @@ class SolverFamily(object):
             if occupancy:
                 occ[a:b] = o.astype(np.int64).reshape((b - a,) + self.dims)
         self._run(tabs, None, work, mc_bytes=self._mc_member_bytes(B, n_law, occupancy))
+        self.backend_info['monte_carlo'] = dict(members=self.P, n_traj=B, chunks=self.backend_info['chunks'],
+                                                launches=self.backend_info['chunks'] * (-(-n_steps // min(spl, 1 << 30))))
+        return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
+
+    # ------------------------------------------------------------------ lookahead at arbitrary states
+    def _lookahead_boxes(self, t_k):
+        """control_box of every member, traced with a symbolic time index and with EVERY constant lifted: a list of
+        TracedBox of one structure.  There is no host fallback in a family: a box that does not trace, traces only at
+        a concrete time index or uses inexact operations is refused, and so are boxes of different structures."""
+        boxes = []
+        for p, s in enumerate(self.solvers):
+            tb = s._trace_box_now(None if self.stationnary else (0 if t_k is None else t_k))
+            if isinstance(tb, TraceError):
+                raise NotImplementedError('member {}: control_box does not trace ({}): a family makes every lattice on the '
+                                          'device, there is no host path'.format(p, tb))
+            if tb.t_value is not None:
+                raise NotImplementedError('member {}: control_box traces only at a concrete time index (data[k]): a box '
+                                          'function per step is not built for families'.format(p))
+            tb.lift_constants()
+            if p and tb.structure_key() != boxes[0].structure_key():
+                raise ValueError(_structure_message(p, tb, boxes[0], what=_BOX))
+            boxes.append(tb)
+        return boxes
+
+    def _lookahead_tables(self, t_k, extra_bytes):
+        """(tabs, look) of a lookahead call at the time index t_k (None: stationary members), no GPU needed: the
+        tables of the sweep, and for `_run` the source of the lookahead unit, the members' box constants [P][n_box]
+        and control steps [P][nu] in float64 and the bytes a member takes beside the handle's"""
+        for p, s in enumerate(self.solvers):
+            if isinstance(_trace_member(s, None), TraceError):       # (it traces at a concrete step only: the constructor saw to that)
+                raise NotImplementedError('member {}: its model looks data up at a concrete time index (data[k]): a table '
+                                          'of constants per step is not built for families'.format(p))
+        boxes = self._lookahead_boxes(t_k)
+        tabs = self._tables(None if self.stationnary else t_k)
+        bprm = np.ascontiguousarray([b.param_values() for b in boxes], dtype=np.float64).reshape(self.P, -1)
+        steps = np.ascontiguousarray([s.control_steps for s in self.solvers], dtype=np.float64).reshape(self.P, self.nu)
+        if np.isnan(steps).any():
+            raise ValueError('member {}: a control step is NaN'.format(int(np.argwhere(np.isnan(steps))[0][0])))
+        look = dict(source=codegen.family_lookahead_unit(tabs['model'], boxes[0], self.dtype, tabs['lanes']),
+                    bprm=bprm, steps=steps, bytes=int(extra_bytes) + 8 * (bprm.shape[1] + self.nu))
+        return tabs, look
+
+    def _cost_to_go(self, J_next):
+        """J_next of every member, (P,) + dims, from dims or (P,) + dims; a further leading axis is a time-indexed
+        cost-to-go, which is not built"""
+        J_next = np.asarray(J_next)
+        if J_next.ndim > len(self.dims) + 1 and J_next.shape[-len(self.dims):] == self.dims:
+            raise NotImplementedError('J_next of shape {}: a time-indexed cost-to-go (a leading axis beside the members\') is '
+                                      'not built for families'.format(J_next.shape))
+        return self._start(J_next, False)
+
+    def lookahead(self, J_next, x, t_k=None):
+        """`DPSolver.lookahead` of every member in one device call (kernel sdp_family_lookahead,
+        csrc/sdp_family_lookahead_kernel.h): (J_opt (P, B), u_opt (P, B, nu), idx (P, B) int32), member p equal, bit for
+        bit, to what `solvers[p].lookahead(J_next[p], x[p], t_k)` returns on its device path.
+
+        J_next : dims (the same cost-to-go for every member) or (P,) + dims
+        x      : (d,), (B, d) shared by all members, or (P, B, d); 4-byte members round them once
+        t_k    : the time index (time-dependent members)
+        A state without a valid lattice gives NaN, NaN, -1.  Every lattice is made on the device from the traced
+        control_box of the member; there is no host path.  Not built: a time-indexed J_next, models that look data up
+        as data[k]."""
+        d = len(self.dims)
+        J0 = self._cost_to_go(J_next)
+        x = np.asarray(x, dtype=float)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim not in (2, 3) or x.shape[-1] != d or (x.ndim == 3 and x.shape[0] != self.P):
+            raise ValueError('x must have shape ({0},), (B, {0}) or ({1}, B, {0}), not {2}'.format(d, self.P, x.shape))
+        B = x.shape[-2]
+        if x.ndim == 2:
+            x = np.broadcast_to(x, (self.P, B, d))
+        if self.stationnary:
+            t_k = None
+        elif t_k is None:
+            raise ValueError('a time-dependent system needs the time index t_k')
+        rs = self.dtype.itemsize
+        tabs, look = self._lookahead_tables(t_k, (d + 1 + self.nu) * B * rs + 4 * B)
+        J = np.empty((self.P, B), dtype=self.dtype)
+        u = np.empty((self.P, B, self.nu), dtype=self.dtype)
+        idx = np.empty((self.P, B), dtype=np.int32)
+        if B == 0:
+            return J, u, idx
+        x_d = np.ascontiguousarray(np.moveaxis(x, -1, 1), dtype=self.dtype)                             # [P][d][B]
+
+        def work(prob, a, b):
+            J[a:b], u_d, idx[a:b] = prob.lookahead(x_d[a:b], 0.0 if t_k is None else t_k)
+            u[a:b] = np.moveaxis(u_d, 1, 2)
+        self._run(tabs, J0, work, look=look)
+        self.backend_info.update(lookahead_path='device', lookahead_box='device', box_constants=int(look['bprm'].shape[1]))
+        return J, u, idx
+
+    def monte_carlo_lookahead(self, J_next, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False,
+                              traj_offset=0, t0=0):
+        """`DPSolver.monte_carlo_lookahead` of every member in one device call per cut of the steps (kernel
+        sdp_family_montecarlo_lookahead, csrc/sdp_family_lookahead_kernel.h): a `montecarlo.FamilyMonteCarloResult`,
+        member p of every field equal, bit for bit, to what `solvers[p].monte_carlo_lookahead` returns on its device
+        path -- the sizings of a study ranked under the controller that would run, not under the interpolated policy.
+
+        J_next : dims or (P,) + dims, the cost-to-go every step looks ahead into
+        x0, seed, law, n_burn, n_traj, occupancy, traj_offset, t0 : as in `monte_carlo`.  `law` is the law the PLANT
+                 draws from; the expectation inside the backup always runs over member p's own discretised law.
+        Not built: a time-indexed J_next, models that look data up as data[k], deterministic members."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        for p, s in enumerate(self.solvers):
+            if self._law_points(s) == 0:
+                raise ValueError('member {}: a deterministic system has nothing to draw: use simulate_lookahead(J_next, x0, '
+                                 'n_steps=...)'.format(p))
+        laws = self._mc_laws(law)
+        J0 = self._cost_to_go(J_next)
+        x0 = np.asarray(x0, dtype=float)
+        shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
+        if x0.ndim == 1:
+            if x0.shape != (d,):
+                raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
+            if n_traj is None:
+                raise ValueError('give n_traj with a single start state')
+            if int(n_traj) < 1:
+                raise ValueError('n_traj must be at least 1')
+            x0 = np.broadcast_to(x0, (int(n_traj), d))
+        elif x0.ndim not in (2, 3) or x0.shape[-1] != d or (x0.ndim == 3 and x0.shape[0] != self.P):
+            raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
+        elif n_traj is not None and int(n_traj) != x0.shape[-2]:
+            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[-2]))
+        B = x0.shape[-2]
+        if x0.ndim == 2:
+            x0 = np.broadcast_to(x0, (self.P, B, d))
+        n_steps, n_burn = int(n_steps), int(n_burn)
+        if n_steps < 1 or not 0 <= n_burn < n_steps:
+            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
+        seeds = self._mc_seeds(seed)
+        DPSolver._mc_ids(B, traj_offset)
+        spl = int(self.steps_per_launch)
+        if spl < 1:
+            raise ValueError('steps_per_launch must be at least 1')
+        dt = self.dtype
+        S, n_law, rs = int(np.prod(self.dims)), len(laws[0][1]), self.dtype.itemsize
+        extra = (d + 1) * B * rs + 8 * B + (8 * S if occupancy else 0) + n_law * (8 + rs) + 8
+        tabs, look = self._lookahead_tables(None if self.stationnary else t0, extra)
+        # ---- member-major device arrays
+        x0_d = np.ascontiguousarray(np.moveaxis(x0, -1, 1), dtype=dt)                                     # [P][d][B]
+        cum = np.ascontiguousarray([mc.cumulative(proba) for _, proba in laws])                           # [P][n_law]
+        law_d = np.ascontiguousarray([grid for grid, _ in laws], dtype=dt)
+        seeds_d = np.array(seeds, dtype=np.uint64)
+        cost_sum = np.empty((self.P, B), dtype=dt)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, B, d), dtype=dt)
+        occ = np.empty((self.P,) + self.dims, dtype=np.int64) if occupancy else None
+
+        def work(prob, a, b):
+            c, n, xf, o = prob.montecarlo_lookahead(x0_d[a:b], n_steps, n_burn, seeds_d[a:b], traj_offset, cum[a:b],
+                                                    law_d[a:b], t0, spl, occupancy)
+            cost_sum[a:b], n_out[a:b], x_final[a:b] = c, n, np.moveaxis(xf, 1, 2)
+            if occupancy:
+                occ[a:b] = o.astype(np.int64).reshape((b - a,) + self.dims)
+        self._run(tabs, J0, work, look=look)
+        self.backend_info.update(lookahead_path='device', lookahead_box='device', box_constants=int(look['bprm'].shape[1]))
         self.backend_info['monte_carlo'] = dict(members=self.P, n_traj=B, chunks=self.backend_info['chunks'],
                                                 launches=self.backend_info['chunks'] * (-(-n_steps // min(spl, 1 << 30))))
         return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')

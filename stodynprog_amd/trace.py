@@ -1051,6 +1051,39 @@ class TracedBox(object):
     def __init__(self, graph, ends, n_state, time_dep, t_value, paths):
         self.graph, self.ends, self.n_state = graph, ends, n_state
         self.time_dep, self.t_value, self.paths = time_dep, t_value, paths
+        self.param_index = None       # node id -> slot, after lift_constants()
+
+    def lift_constants(self):
+        """Turn every real constant of the live DAG into a parameter (slot order = recording order), as
+        TracedModel.lift_constants does: codegen.box_function_source(box, at=True) then reads `bprm[slot]` instead of
+        a literal, so boxes that differ only by constants -- the rated energy and power of the members of a family --
+        share one box function.  Returns the parameter values of THIS box."""
+        consts = [n for n in self.live_nodes() if n.op == 'const']
+        self.param_index = {n.id: i for i, n in enumerate(consts)}
+        return [n.value for n in consts]
+
+    def param_values(self):
+        return [n.value for n in self.live_nodes() if n.op == 'const']
+
+    def structure_key(self):
+        """Text identifying the live DAG up to the values of its real constants (two boxes with equal keys generate
+        the same box function once their constants are lifted)."""
+        import hashlib
+        live = self.live_nodes()
+        pos = {n.id: i for i, n in enumerate(live)}
+        parts = []
+        for n in live:
+            if n.op == 'const':
+                parts.append('c')
+            elif n.op in ('var', 'bconst'):
+                parts.append('{}:{}'.format(n.op, n.value))
+            elif n.op == 'interp1':
+                digest = hashlib.sha256(b''.join(self.graph.tables[n.value][4])).hexdigest()[:16]
+                parts.append('interp1[{}]({})'.format(digest, pos[n.args[0].id]))
+            else:
+                parts.append('{}({})'.format(n.op, ','.join(str(pos[a.id]) for a in n.args)))
+        outs = ['{}:{}'.format(pos[lo.id], pos[hi.id]) for lo, hi in self.ends]
+        return ';'.join(parts) + '|' + ','.join(outs) + '|t={}'.format('sym' if self.time_dep else self.t_value)
 
     def live_nodes(self):
         seen, order = set(), []
@@ -1091,17 +1124,24 @@ class TracedBox(object):
         sig.append(tuple((lo.id, hi.id) for lo, hi in self.ends))
         return tuple(sig)
 
-    def evaluate(self, x, t=None):
-        """the box on numpy arrays (any mutually broadcastable shapes, e.g. an open grid): [(lo, hi)] per control"""
+    def evaluate(self, x, t=None, params=None):
+        """the box on numpy arrays (any mutually broadcastable shapes, e.g. an open grid): [(lo, hi)] per control.
+        params: a row of constants in slot order (`param_values` of a box of the same structure) read in the place of
+        this box's own -- the numpy twin of the box function with lifted constants (`sdp_model_box_at`)"""
         vals = {'x%d' % i: v for i, v in enumerate(x)}
         vals['t'] = t
         env = {}
+        slot = None
+        if params is not None:
+            slot = {n.id: i for i, n in enumerate(n for n in self.live_nodes() if n.op == 'const')}
+            if len(params) != len(slot):
+                raise ValueError('{} constants for a box with {}'.format(len(params), len(slot)))
         with np.errstate(all='ignore'):
             for n in self.live_nodes():
                 if n.op == 'var':
                     env[n.id] = np.asarray(vals[n.value], dtype=float)
                 elif n.op == 'const':
-                    env[n.id] = np.float64(n.value)
+                    env[n.id] = np.float64(n.value if slot is None else params[slot[n.id]])
                 elif n.op == 'bconst':
                     env[n.id] = np.bool_(n.value)
                 elif n.op == 'interp1':
