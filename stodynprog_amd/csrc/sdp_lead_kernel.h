@@ -179,12 +179,13 @@ extern "C" __global__ void __launch_bounds__(256) sdp_lead_reduce(SdpSweepArgs a
     sdp_lacc *__restrict__ A = (sdp_lacc *)a.aux_a;
     sdp_real *__restrict__ Vt = (sdp_real *)a.aux_v;
     sdp_real *__restrict__ E = (sdp_real *)a.aux_e;
-    const sdp_real *__restrict__ wgrid = (const sdp_real *)a.wgrid;
     const sdp_real *__restrict__ proba = (const sdp_real *)a.proba;
-    const sdp_real t = (sdp_real)a.t_k;
     SdpLeadGeom geo;
     sdp_lead_geom(a, geo);
 #if SDP_LEAD_AXES < SDP_D
+    // (no exogenous axis: nothing below reads the perturbation points or the time)
+    const sdp_real *__restrict__ wgrid = (const sdp_real *)a.wgrid;
+    const sdp_real t = (sdp_real)a.t_k;
     SdpGrid<sdp_real, SDP_LT> tg;
     sdp_lead_trail_grid(a, geo, tg);
 #endif

@@ -108,8 +108,10 @@ def test_special_values(gpu, case):
 
 
 def test_one_exogenous_axis_less_and_one_more(gpu):
-    """d = 2 with both state variables controlled (no exogenous axis: the perturbation only reaches the
-    cost-free part, i.e. nothing) is not this family; d = 4 with two exogenous axes is"""
+    """one exogenous axis more: d = 4, two stocks listed first and two exogenous axes, plans this family and gives
+    the direct kernel's bits.  (One axis less -- d = 2 with both state variables controlled, the perturbation in the
+    cost alone -- is this family too: TracedModel.controlled_axes returns m = d and the plan is `lead`; that form
+    is the case `all_stocks` of tests/lead_forms.py, run by tests/test_gpu_lead_forms.py.)"""
     def make():
         sysd = SysDescription((4, 2, 1), name='two stocks, two exogenous')
         sysd.dyn = lambda a, b, y, z, u, v, w: (a + 0.5 * y - u, b + u - v, 0.7 * y + w, 0.5 * z - 0.3 * w + 0.1 * y)
