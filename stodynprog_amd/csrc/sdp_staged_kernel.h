@@ -282,7 +282,10 @@ extern "C" __global__ void __launch_bounds__(SDP_STG_THREADS, SDP_STG_MIN_WAVES)
                     if (vol > SDP_STG_CAP) {
                         const int64_t other = vol / rowlen;
                         const int fit = (int)(SDP_STG_CAP / other);
-                        if (fit < 3) any = false;                 // nothing useful fits
+                        // nothing useful fits: every cell reads global memory.  The strides of the
+                        // leading axes become 0, so that the unused read at "vertex 0" stays within
+                        // the first two reals of the box whatever row length was predicted
+                        if (fit < 3) { any = false; rowlen = 0; }
                         else { rowlen = fit; ext[SDP_D - 1] = min(ext[SDP_D - 1], fit); }
                     }
                 }
