@@ -44,12 +44,14 @@ DEBUG_INT_MACROS = ('SDP_COL_MIN_WAVES', 'SDP_COL_BATCH', 'SDP_COL_UNROLL_U', 'S
 # (SDP_BNB_UNIFORM = 0 keeps the branch and bound on the bound stage that locates every block end per node: an A/B switch)
 # (SDP_BNB_LEAN = 0 keeps the branch and bound's bookkeeping of before round 9 -- the 64-bit block mask, the per-control
 #  selects of the evaluation: an A/B switch that nothing plans, copied into the unit only when a caller sets it)
+# (SDP_BNB_UNIFORM_EVAL = 0 keeps the branch and bound on the evaluation that locates every control per node, with its radius
+#  of before: an A/B switch of uniform_eval_plan)
 # every name a `debug` dict may carry (a typo must not pass silently)
 DEBUG_NAMES = frozenset(DEBUG_INT_MACROS + (
     'SDP_STAMP', 'SDP_NO_POW2', 'SDP_EXTRA_DEFINES', 'SDP_COL_FILTER_SCALE', 'SDP_LEAD_FILTER_SCALE',
     'SDP_LEAD_UNROLL', 'SDP_COL_A_LW', 'SDP_COL_FILTER', 'SDP_COL_SHIFT', 'SDP_COL_UTAB', 'SDP_LEAD_FILTER',
     'SDP_COL_THREADS', 'SDP_COL_WCHUNK', 'SDP_STG_CU', 'SDP_COL_WPAIR', 'SDP_COL_WRES', 'SDP_COL_LEAN2', 'SDP_COL_BNB',
-    'SDP_LINE_FILTER', 'SDP_LINE_FILTER_SCALE', 'SDP_LINE_TOP2', 'SDP_BNB_UNIFORM'))
+    'SDP_LINE_FILTER', 'SDP_LINE_FILTER_SCALE', 'SDP_LINE_TOP2', 'SDP_BNB_UNIFORM', 'SDP_BNB_UNIFORM_EVAL'))
 
 
 def check_debug(debug):
@@ -594,6 +596,65 @@ def uniform_stage_pad(model, dtype, unit, axis, box):
     return BNB_PAD
 
 
+# rows: 2 delta D = 4096 u D at most, against a radius of (160 + 256) u S_node >= 1248 u D at W = 32 and 64 controls -- the
+# position term may reach 3.3 times the radius of before (the benchmark: 2180 u D, 1.7 times: the radius grows 2.7-fold at
+# most); beyond that the filter would be given away for the instructions saved, and the unit keeps the evaluation it had
+EVAL_DELTA_CAP = 2.0 ** -42
+
+
+def uniform_eval_delta(axis, n0):
+    """(delta, dx, unit_axis) of `uniform_eval_plan` for a stock axis of `n0` rows: the arithmetic alone"""
+    x = np.asarray(axis, dtype=np.float64).ravel()
+    n0 = int(n0)
+    smin, span = x[0], x[-1] - x[0]
+    k = np.float64(n0 - 1) / span
+    unit_axis = bool(smin == 0.0 and span == 1.0)
+    dx = float(np.max(np.abs((x - smin) * k - np.arange(n0, dtype=np.float64))))
+    # (.. rounded up to a power of two, 2^-60 at least: the check compares against an immediate operand)
+    dx = max(float(2.0 ** math.ceil(math.log2(dx))) if dx > 0.0 else 0.0, 2.0 ** -60)
+    u = 2.0 ** -53
+    m = n0 + BNB_PAD
+    count = (2 * m + n0) if unit_axis else (6 * m + abs(float(smin)) * float(k) + 2 * n0)
+    return (dx + u * (count + 2 * BNB_PAD + 2)) * (1.0 + 2.0 ** -20), dx, unit_axis
+
+
+def uniform_eval_plan(model, dtype, unit, axis, debug=None):
+    """THE place that decides the uniform EVALUATION stage of the branch and bound (SDP_BNB_UNIFORM_EVAL of
+    csrc/sdp_column_kernel.h), on a unit that `uniform_stage_pad` has padded: None, or (delta, dx, unit_axis).
+
+    delta bounds, in rows, the distance between the position the reference's chain forms for control c of row r
+    (sdp_lean2_cell: fl(X_r +- a_c), - smin, / span or * rspan, * nm1, and the rounding of lam0 where the cell is clamped)
+    and  r + pa_c,  pa_c = fl(+-a_c k) as the control table's wave forms it, k = fl((n - 1) / span), for EVERY a_c whose
+    pa_c stays inside the padding (the wave checks that) -- so for every control of every lattice the unit runs on:
+
+      * dx: the largest |fl(fl(X_r - smin) k) - r| over the rows of the stored axis, in the kernel's own arithmetic; the
+        kernel checks every node against it, so a node that passes sits within dx + c n u of its row in real numbers (the
+        two roundings of the check, one on the unit axis where X - 0 is exact);
+      * the chain's roundings, each at most u of a position (|p| <= M = n + PAD rows) or of x0' itself (|smin| k more): two
+        on the unit axis (the sum, the product; k = n - 1 exactly), six otherwise (sum, difference, quotient or product
+        with an exact reciprocal, product, and k's own: counted as in the division form);
+      * u |pa_c| <= u PAD for pa_c, u (PAD + 1) for lam0 beyond either end, u where phi_c rounds to 1.
+
+    The roundings are COUNTED, on purpose, where one could enumerate every (row, control) pair of the planned lattice on the
+    host (496 u on the benchmark against the 1 090 u counted): the enumeration says nothing about a lattice whose values the
+    kernel forms an ulp away from numpy's, or about the box of another call; the count holds for whatever lies inside the
+    padding.  tests/test_uniform_eval_exact.py measures the true distance pair by pair against it.  Planned where delta stays below
+    EVAL_DELTA_CAP and a depends on the control alone: the records then lie where the control tables of the two parities
+    held a, which such a unit reads from no table, and the LDS image is what it was.  (The record says so whether or not the
+    A/B switch SDP_BNB_UNIFORM = 0 leaves both uniform stages out of the text.)"""
+    if not unit.bnb_pad or _dbg(debug, 'SDP_BNB_UNIFORM_EVAL') == '0':
+        return None
+    # (the records take the slots a has in the control tables and serve every column: a of x0' = x0 +- a has to follow from
+    # the control alone, SDP_LEAN2_A_FIXED)
+    a_slot = int(model.additive_control_split(unit.frontier)['lead'][1])
+    if unit.frontier[a_slot].deps & DEP_X:
+        return None
+    delta, dx, unit_axis = uniform_eval_delta(axis, unit.n0)
+    if not (np.isfinite(delta) and delta <= EVAL_DELTA_CAP):
+        return None
+    return delta, dx, unit_axis
+
+
 def shift_chain(model):
     """additions of a chain of sums that the shifted lattice regrouped (SDP_COL_SHIFT_CHAIN / SDP_LINE_CHAIN; 0: the
     final-sum form)"""
@@ -662,6 +723,12 @@ def _column_lines(model, dtype, unit, debug):
             short += '\n#define SDP_BNB_PAD_ROWS {}    // the reduced table continued linearly on either side'.format(unit.bnb_pad)
         if unit.uniform:
             short += uniform_define
+        if unit.eval_delta and unit.uniform:          # (uniform_eval_plan; the stage needs the uniform bound stage)
+            short += ('\n#define SDP_BNB_UNIFORM_EVAL 1       // controls evaluated at row r + k_c + phi_c, the same offsets in every lane'
+                      '\n#define SDP_BNB_UNIFORM_EVAL_DELTA {}    // rows between that position and the reference\'s, at most: added to the radius'
+                      '\n#define SDP_BNB_UNIFORM_EVAL_DX {}       // .. of which the node\'s own distance from its row, checked per node'
+                      '\n#define SDP_BNB_UNIFORM_EVAL_UNIT {}     // the roundings were counted for the axis [0, 1]').format(
+                          float(unit.eval_delta).hex(), float(unit.eval_dx).hex(), 1 if unit.eval_unit_axis else 0)
         lines += [short, '']
     elif unit.short == 'wide2':
         short = short_pass_source(model, unit.frontier, 'SDP_COL_WIDE2')
@@ -1346,6 +1413,9 @@ def column_lds_bytes(n0, w, n_state, dtype):
 #   short           the short first pass: 'none' / 'lean2' (resident chunks, 8-byte reals) / 'wide2' (full table, 4-byte)
 #   bnb             .. as a branch and bound over blocks of controls (SDP_COL_BNB)
 #   bnb_pad, uniform            rows the reduced table is padded by (SDP_BNB_PAD_ROWS) and the uniform bound stage on them
+#   eval_delta, eval_dx, eval_unit_axis     the uniform evaluation stage (SDP_BNB_UNIFORM_EVAL; eval_delta 0.0: not planned): the
+#                   rows its positions may lie from the reference's, the node's share of them that the kernel checks, and
+#                   whether the roundings were counted for the axis [0, 1] (uniform_eval_plan)
 #   window_rows, seg_nodes      rows of the row window's table; nodes of a column per unit (0: the whole column)
 #   wchunk          perturbation points per table of the table per control (SDP_COL_WCHUNK)
 #   unroll_w, min_waves, a_lw, a_group, wide_loads, tail_hold, bnb_chunk, colu_wide_loads
@@ -1357,8 +1427,9 @@ ColumnUnit = collections.namedtuple('ColumnUnit', (
     'form', 'n0', 'w', 'max_controls', 'n_columns', 'threads', 'lds_bytes',
     'filtered', 'wpair', 'shift', 'shift_rows', 'wres', 'frontier', 'utab_n', 'short', 'bnb', 'bnb_pad', 'uniform',
     'window_rows', 'seg_nodes', 'wchunk',
-    'unroll_w', 'min_waves', 'a_lw', 'a_group', 'wide_loads', 'tail_hold', 'bnb_chunk', 'colu_wide_loads'),
-    defaults=(False, False, False, 0, 0, None, 0, 'none', False, 0, False, 0, 0, 0) + (None,) * 8)
+    'unroll_w', 'min_waves', 'a_lw', 'a_group', 'wide_loads', 'tail_hold', 'bnb_chunk', 'colu_wide_loads',
+    'eval_delta', 'eval_dx', 'eval_unit_axis'),
+    defaults=(False, False, False, 0, 0, None, 0, 'none', False, 0, False, 0, 0, 0) + (None,) * 8 + (0.0, 0.0, False))
 
 
 def _with_build_order(unit, dtype, debug):
@@ -1450,6 +1521,10 @@ def column_table_unit(model, dtype, shape, W, max_controls, box, axis, certified
         unit = unit._replace(bnb_pad=pad, uniform=_dbg(debug, 'SDP_BNB_UNIFORM') != '0',
                              lds_bytes=_column_lds(unit.wres, max(unit.w, 1), n0, n_state, rs, unit.threads, reduced=True,
                                                    utab_values=kw['utab_values'], bnb_pad=True))
+        # (.. and its uniform evaluation stage, at no cost in LDS; SDP_BNB_UNIFORM_EVAL = 0 leaves it out: the A/B switch)
+        ev = uniform_eval_plan(model, dtype, unit, axis, debug)
+        if ev:
+            unit = unit._replace(eval_delta=ev[0], eval_dx=ev[1], eval_unit_axis=ev[2])
     if wres and rs == 8 and shift and not _dbg(debug, 'SDP_COL_UNROLL_W'):
         # the second pass of the shifted lattice's resident-chunk kernel one batch of perturbation points at a time: unrolled
         # four times it kept 8 points' cells, table entries and weights per survivor in flight (two survivors in half of the

@@ -537,8 +537,9 @@ SDP_DEV void sdp_col_lean_eval_tab(const sdp_real *A, const sdp_real *utab, cons
 SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_real *x, sdp_real t, int first = 0,
                              int count = 0, const SdpBox *box_c = nullptr, sdp_real psum = (sdp_real)0,
                              sdp_real k_rows = (sdp_real)0, sdp_real x_cap = (sdp_real)0, double psum_d = 0.0,
-                             bool a_known = false)
+                             bool a_known = false, sdp_real *erec = nullptr)
 {
+    (void)erec;
     // a_known (SDP_LEAN2_A_FIXED: the part a of x0' = X +- a depends on the control alone -- the same lattice of positions
     // in every column): this parity buffer already holds what follows from a -- its smallest and largest value, the blocks'
     // starts, their order, the row count -- from the table made here two units ago; only what follows from h is redone.
@@ -582,6 +583,15 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
     // difference -- argued here, not checked on the device; tests/test_uniform_bound_exact.py asserts it case by case.
     // Made from the records once they are all there (a lane per end; the wave's own writes: in order).
     // (The planner proves rows and reach on the host, codegen.uniform_stage_pad: uni_fine below only guards the reads.)
+    // The uniform evaluation stage (SDP_BNB_EVAL_ON) takes control c of lane r at  row r + k_c + phi_c  the same way:
+    // k_c = floor(pa_c), phi_c = pa_c - k_c of the pa_c formed below (exact, or 2^-53 rows off where it rounds to 1) -- one
+    // record per control, ((8 k_c, c), phi_c).  It costs no LDS: such a unit reads a from no table -- a follows from the control
+    // alone there, the evaluation needs its whole part and fraction only, the candidate test takes the same form and a wave
+    // that cannot run the stage sends its nodes the long way (csrc/sdp_colres_kernel.h) -- so a's slot of this table holds
+    // (8 k_c, c) and a's slot of the OTHER parity's table, `erec`, holds phi_c.  The caller hands `erec` over with the
+    // workgroup's FIRST table, before the barrier that publishes it; every later table leaves a's slot alone, so the records
+    // stand for every column and nobody writes them while they are read.  pa_c lies between the first block's start and the
+    // last one's end, DELTA inside either: every k_c is within the padding where the ends are.
 #endif
     for (int c0 = 0; c0 < n_tab; c0 += 64) {               // (every lane of the wave takes part in every round: shuffles)
         int ci = c0 + lane_u;
@@ -595,7 +605,8 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
         sdp_model_utab(x, u, t, tab);
         if (ci < n_tab) {
 #pragma unroll
-            for (int k = 0; k < SDP_COL_UTAB; ++k) utab[ci * SDP_COL_UTAB + k] = tab[k];
+            for (int k = 0; k < SDP_COL_UTAB; ++k)
+                if (!SDP_BNB_EVAL_ON || k != SDP_LEAN2_A_SLOT) utab[ci * SDP_COL_UTAB + k] = tab[k];      // (the uniform evaluation: a's slots hold its records)
             if (!a_known) {
                 a_lo = sdp_vmin(a_lo, tab[SDP_LEAN2_A_SLOT]);
                 a_hi = sdp_vmax(a_hi, tab[SDP_LEAN2_A_SLOT]);
@@ -631,6 +642,13 @@ SDP_DEV void sdp_col_phase_u(const SdpSweepArgs &a, sdp_real *utab, const sdp_re
         const sdp_real pa = (SDP_LEAN2_FORM == 1 ? -av : av) * k_rows;
         bnb_fine = bnb_fine && (!have || (pa == pa && hpv == hpv && fabs(pa) < (sdp_real)INFINITY));
         bnb_amax = sdp_vmax_abs(bnb_amax, have ? av : (sdp_real)0);
+#if SDP_BNB_EVAL_ON
+        if (erec != nullptr && have) {
+            const sdp_real kf = floor(pa);
+            utab[ci * SDP_COL_UTAB + SDP_LEAN2_A_SLOT] = (sdp_real)__hiloint2double(ci, (int)((unsigned)(int)kf << 3));      // (a k_c beyond the padding is never read)
+            erec[ci * SDP_COL_UTAB + SDP_LEAN2_A_SLOT] = pa - kf;
+        }
+#endif
         sdp_real lo = have ? pa : (sdp_real)INFINITY, hi = have ? pa : -(sdp_real)INFINITY;
         // minima / maxima over the aligned groups of SEG lanes: the blocks
         if (SEG == 8) {
@@ -1077,6 +1095,29 @@ SDP_DEV void sdp_wide2_pass1(const sdp_real *ad, const sdp_real *utab, const Sdp
 // - 1 absorbs the roundings of that difference: argued in sdp_col_phase_u, asserted by tests/test_uniform_bound_exact.py);
 // any further row that the clamped extra reads (row k_b - 1 where two ends share a cell) only lowers the bound.  A NaN or an infinity in a row the bound reads keeps
 // the block as before.
+// UNIFORM EVALUATION stage (SDP_BNB_EVAL_ON, round 10: a unit with the uniform bound stage whose planner has proved
+// SDP_BNB_UNIFORM_EVAL_DELTA, codegen.uniform_eval_plan; such a unit has no other evaluation).  Control c of lane r is NOT
+// located: F' is taken at row_u + k_c + phi_c, k_c = floor(pa_c) and phi_c = pa_c - k_c of the control's own pa_c = fl(+-a_c k)
+// (one record per control, ((8 k_c, c), phi_c), made once per workgroup by the control table's wave in the slots a has in the
+// two parities' control tables, `rc_tab` and `phi_tab` -- a follows from the control alone in such a unit and no table holds
+// it: sdp_col_phase_u), on the padded table: one add for the address, the two rows, a subtraction, two
+// fma, the index or-ed in from the record, the insert.  This is NOT the reference's cell: its position p = q0 + lam0 comes
+// out of its own chain of roundings (fl(X + a), - smin, / span, * nm1).  The planner bounds |p - (row_u + pa_c)| <= delta
+// for every node that passes the caller's check |fl(fl(X - smin) k) - row_u| <= DX and every pa_c inside the padding, by
+// counting those roundings (at most u of a position of at most N0 + PAD rows each; tests/test_uniform_eval_exact.py
+// measures the true distance of every pair against it).  L is continuous and piecewise linear with slopes
+// |A[q+1] - A[q]| <= 2 D, and the padded rows continue its end cells with the same slopes: so L moves by at most 2 delta D
+// between the two positions, also where they fall in neighbouring cells or beyond an end; the padded rows' own two
+// roundings cost 8 u S_node as in the bound stage; phi_c in [0, 1] and the rows it reads are bounded like lam0 and the
+// reference's, so the roundings of this F' are those the radius counted already.  Hence
+//     |E - K P* - F'| <= radius + 2 delta D + 8 u S_node,
+// and the caller's radius IS that sum (csrc/sdp_colres_kernel.h): the single-survivor test, the candidate test and the
+// bound stage's slack (twice the radius) all use it.  The guess's F' takes the same form, and so does the candidate test of
+// the multi-survivor path (sdp_uniform_value: the same theorem, the same F').  The second pass is on the reference's cells as
+// before.  A wave that cannot run the stage -- a node off its row, a lattice out of order or past the padding: what the plan
+// rules out -- has no table to read a from: its nodes take every control the long way (csrc/sdp_colres_kernel.h).
+// Not finite: a NaN or infinite a poisons the column's statistics (no branch and bound); a table entry that is not finite
+// makes D infinite, every node of the column `bad`, and what this stage computed is not used -- as before.
 // BOOKKEEPING (SDP_BNB_LEAN, round 9; 0 keeps the earlier form for A/B runs).  Which blocks a lane asks for, and which
 // controls it inserts, is the same set either way -- only how it is written down differs, so that the vector stream holds
 // little beside the arithmetic:
@@ -1088,11 +1129,27 @@ SDP_DEV void sdp_wide2_pass1(const sdp_real *ad, const sdp_real *utab, const Sdp
 //    inserting the largest finite number for every control (inserting a block twice would NOT be harmless: the second
 //    smallest value would become the smallest), and where every lane's lattice is whole blocks the trip carries no
 //    clamp and no test of the control's index.  A control past the end is never inserted, as before.
+#if SDP_BNB_EVAL_ON
+// F' of one control in the uniform evaluation's form, without the index in its low bits (the candidate test)
+SDP_DEV double sdp_uniform_value(const sdp_real *A_row, const sdp_real *rc_tab, const sdp_real *phi_tab, const sdp_real *utab,
+                                 const SdpColFilter &f, int c)
+{
+    const double rc = (double)rc_tab[c * SDP_COL_UTAB + SDP_LEAN2_A_SLOT], phi = (double)phi_tab[c * SDP_COL_UTAB + SDP_LEAN2_A_SLOT];
+    const char *at = (const char *)A_row + __double2loint(rc);
+    const double a0 = (double)*(const sdp_real *)at, a1 = (double)*(const sdp_real *)(at + 8);
+    const double h = fma(phi, a1 - a0, a0);
+    if (SDP_LEAN2_H_SLOT < 0) return h;
+    const sdp_real hv = utab[c * SDP_COL_UTAB + (SDP_LEAN2_H_SLOT < 0 ? 0 : SDP_LEAN2_H_SLOT)];
+    return fma((double)(SDP_LEAN2_HNEG ? -hv : hv), (double)f.psum, h);
+}
+#endif
 template <int AXIS, bool WIDE, typename INSERT>
 SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpColFilter &f, const SdpLeadAxis &l,
                            sdp_real X, sdp_real k_rows, int c_lo, int n, int mask, double slack, int guess, INSERT &insert,
-                           sdp_real &sdp_diag_cnt, sdp_real *b_seen = nullptr, int row_u = -1)
+                           sdp_real &sdp_diag_cnt, sdp_real *b_seen = nullptr, int row_u = -1, const sdp_real *rc_tab = nullptr,
+                           const sdp_real *phi_tab = nullptr)
 {
+    (void)rc_tab; (void)phi_tab;
     // SDP_COL_SHIFT (round 6): `A` holds the (A', B') pairs of the shifted lattice, `l` is the lattice.  A control's F' is off
     // from the real number it stands for by its OWN cell's chord bound B'[q0] on top of the rounding radius, so a block is
     // ruled out against the guess g only when   LB - max B'[the rows the block's positions can fall in]  >  F'_g + B'[q0(g)] + slack
@@ -1125,6 +1182,17 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
     // ---- stage 1: what the bounds need from the LDS -- the guess's entry of the control table, the blocks' records
     // ---- stage 2: the cells, the reads of the reduced table        (all of a stage's reads are in flight together)
     // ---- stage 3: F' of the guess (an upper bound of the node's smallest F'), the bounds, the blocks to evaluate
+#if SDP_BNB_EVAL_ON
+    // (the uniform evaluation: the guess's cell from its record, like every control's below)
+    const sdp_real gh = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : utab[g * SDP_COL_UTAB + HS];
+    (void)k_rows; (void)X;
+    const int extra = __builtin_amdgcn_readfirstlane(__double2loint((double)rec[2 * n_blocks + 1]));
+    const char *Ae = (const char *)(A + row_u);            // this lane's row of the (padded) reduced table
+    auto at_e = [&](int off) -> double { return (double)*(const sdp_real *)(Ae + off); };
+    const sdp_real glam = phi_tab[g * SDP_COL_UTAB + SDP_LEAN2_A_SLOT];
+    const int gko = __double2loint((double)rc_tab[g * SDP_COL_UTAB + SDP_LEAN2_A_SLOT]);
+    const double gA0 = at_e(gko), gA1 = at_e(gko + 8), gB = 0.0;
+#else
     const sdp_real ga = utab[g * SDP_COL_UTAB + SDP_LEAN2_A_SLOT];
     const sdp_real gh = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : utab[g * SDP_COL_UTAB + HS];
     (void)k_rows;
@@ -1134,6 +1202,7 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
     sdp_real glam;
     cell(SDP_LEAN2_LEAD(X, ga), gq, glam);
     const double gA0 = row(gq), gA1 = row(gq + 1), gB = brow(gq);
+#endif
     double thresh = 0.0;
     constexpr int CB = NB < SDP_BNB_CHUNK ? NB : SDP_BNB_CHUNK;
     constexpr bool LEAN = SDP_BNB_LEAN != 0;
@@ -1273,13 +1342,64 @@ SDP_DEV void sdp_short_bnb(const sdp_real *A, const sdp_real *utab, const SdpCol
         const need_t live = n_blocks >= (int)(8 * sizeof(need_t)) ? ~(need_t)0 : (ONE << n_blocks) - 1;
         need = (need & live) | (ONE << ((unsigned)g / (unsigned)BS));
     }
-#ifdef SDP_DIAG_BNB_COUNT                                  // diagnostic: J := blocks asked for (+ 100 x the guess's block)
+#ifdef SDP_DIAG_BNB_COUNT                                  // diagnostic: J := blocks asked for (+ 100 x the guess's block; the caller: + 10000 x "more than one survivor")
     sdp_diag_cnt = (sdp_real)((sizeof(need_t) == 4 ? __popc((unsigned)need) : __popcll(need)) + 100 * (g / BS));
 #endif
     // ---- the blocks that stay, lane by lane, groups of controls in stages (a lane reads ITS block's entries of the
     // control table; lanes with nothing left idle through the trip)
     constexpr int K = SDP_SHORT_GROUP;
     static_assert(BS % K == 0, "branch and bound: whole groups per block");
+#if SDP_BNB_EVAL_ON
+    {
+        static_assert(!SHIFT && !WIDE, "uniform evaluation: 8-byte reals, not the shifted lattice");
+        // The uniform evaluation, the only one of such a unit: a control's record and its h at constant offsets from the
+        // block's first, the two rows at the lane's own address + 8 k_c -- no conversion, clamp or position arithmetic.
+        auto value = [&](int c) -> double {
+            const sdp_real *ut = utab + c * SDP_COL_UTAB;
+            const double rc = (double)rc_tab[c * SDP_COL_UTAB + SDP_LEAN2_A_SLOT], phi = (double)phi_tab[c * SDP_COL_UTAB + SDP_LEAN2_A_SLOT];
+            const sdp_real hv = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : ut[HS];
+            const int ko = __double2loint(rc);
+            const double a0 = at_e(ko), a1 = at_e(ko + 8);
+            const double h = fma(phi, a1 - a0, a0);
+            const double F = SDP_LEAN2_H_SLOT < 0 ? h : fma((double)(SDP_LEAN2_HNEG ? -hv : hv), psum, h);
+            return __hiloint2double(__double2hiint(F), (__double2loint(F) & ~mask) | __double2hiint(rc));
+        };
+        while (need != 0) {
+            const int b = lowest(need) - 1;
+            need &= need - 1;
+            const int e0 = (b * BS) * SDP_COL_UTAB + SDP_LEAN2_A_SLOT;      // (the block's first record: the others at constant offsets)
+            const sdp_real *ut = utab + (b * BS) * SDP_COL_UTAB;
+            if (b * BS + BS <= n) {
+                for (int j0 = 0; j0 < BS; j0 += K) {
+                    // (in stages, like the evaluation below: a group's reads are in flight together)
+                    double rc[K], phi[K], a0[K], a1[K];
+                    sdp_real hv[K];
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        rc[j] = (double)rc_tab[e0 + (j0 + j) * SDP_COL_UTAB];
+                        phi[j] = (double)phi_tab[e0 + (j0 + j) * SDP_COL_UTAB];
+                        hv[j] = SDP_LEAN2_H_SLOT < 0 ? (sdp_real)0 : ut[(j0 + j) * SDP_COL_UTAB + HS];
+                    }
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        a0[j] = at_e(__double2loint(rc[j]));
+                        a1[j] = at_e(__double2loint(rc[j]) + 8);
+                    }
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        const double h = fma(phi[j], a1[j] - a0[j], a0[j]);
+                        const double F = SDP_LEAN2_H_SLOT < 0 ? h : fma((double)(SDP_LEAN2_HNEG ? -hv[j] : hv[j]), psum, h);
+                        insert(__hiloint2double(__double2hiint(F), (__double2loint(F) & ~mask) | __double2hiint(rc[j])));
+                    }
+                }
+            } else {
+                // the last block of a lattice that is not whole blocks: its controls one by one
+                for (int c = b * BS; c < n; ++c) insert(value(c));
+            }
+        }
+        return;
+    }
+#endif
     if (LEAN) {
         // one block of this lane; WHOLE: every block of the lattice has BS controls
         auto block = [&](const int b, auto whole_c) {

@@ -339,6 +339,11 @@ SDP_DEV void sdp_lean2s_pass1(const sdp_real *A, const sdp_real *utab, const Sdp
 
 #endif  // SDP_COL_LEAN2
 
+#if SDP_BNB_EVAL_ON
+#define SDP_EREC sdp_lds.utab[0], sdp_lds.utab[1]      // the records of the uniform evaluation stage: a's slots of the two tables
+#else
+#define SDP_EREC nullptr
+#endif
 #define SDP_LDS_AD (sdp_lds.ad + SDP_BNB_PAD)            // row 0 of the reduced table (behind the padding of the uniform bound stage)
 extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES) sdp_sweep_col(SdpSweepArgs a)
 {
@@ -426,7 +431,12 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
         sdp_col_coords(a, sdp_col_of_unit(a, unit), xn);
         sdp_col_phase_w(a, tg, s, xn, nullptr, t);
 #if SDP_COL_UTAB
+#if SDP_BNB_EVAL_ON
+        // (.. and makes the records of the uniform evaluation stage, once per workgroup)
+        sdp_col_phase_u(a, sdp_lds.utab[0], xn, t, 0, 64, box_c, filt.psum, k_rows, x_cap, (double)filt.psum, false, sdp_lds.utab[1]);
+#else
         sdp_col_phase_u(a, sdp_lds.utab[0], xn, t, 0, 64, box_c, filt.psum, k_rows, x_cap, (double)filt.psum);      // (one wave: it also reduces the table's statistics)
+#endif
 #endif
 #if SDP_COL_SHIFT
         sdp_col_phase_shift(a, sdp_lds, lead, xn, t, 0);
@@ -656,35 +666,69 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
             const sdp_real s_node = fma(filt.pcap, fabs(K) + ust[2], ((sdp_real)1 + (sdp_real)2 * l_cap) * dcol);
             const bool bad = !filt.ok || !(s_node < SDP_COL_FILTER_LIMIT) || !(fabs(lam_lo) + fabs(lam_hi) < (sdp_real)1073741824.0) ||
                              bits > 24 || box.total > SDP_COL_UTAB_N;
+#if SDP_BNB_EVAL_ON
+            // (the uniform evaluation stage: F' is taken SDP_BNB_UNIFORM_EVAL_DELTA rows at most from the reference's position, on a
+            // table whose slope is at most 2 D per row, and reads padded rows -- 2 delta D + 8 u S_node more: sdp_short_bnb)
+            const sdp_real radius = fma((sdp_real)(SDP_COL_FILTER_SCALE), fma((sdp_real)(2.0 * (SDP_BNB_UNIFORM_EVAL_DELTA)), dcol, ((sdp_real)4 * SDP_COL_FILTER_EPS) * s_node),
+                                        (filt.cu + (sdp_real)(SDP_COL_FILTER_SCALE) * ldexp(SDP_COL_FILTER_EPS, bits + 1)) * s_node);
+#else
             const sdp_real radius = (filt.cu + (sdp_real)(SDP_COL_FILTER_SCALE) * ldexp(SDP_COL_FILTER_EPS, bits + 1)) * s_node;
+#endif
 #if SDP_COL_BNB
             // a block is skipped when its lower bound exceeds f1 by more than 2 radius + 16 u S_node (8 x EPS = 16 u).
             // Only where the column's blocks are in order and |X| is small enough for the bounds' positions (ust[3]:
             // sdp_col_phase_u); a wave with a node that does not qualify takes the full pass.
             // (the uniform bound stage: 8 u S_node more for the roundings of the padded rows it reads)
             const sdp_real slack = fma((sdp_real)2, radius, ((sdp_real)(SDP_BNB_UNIFORM_ON ? 12 : 8) * SDP_COL_FILTER_EPS) * s_node);
-#if SDP_BNB_UNIFORM_ON
+#if SDP_BNB_EVAL_ON
+            // .. and where this lane's node sits at its own row to within its share of SDP_BNB_UNIFORM_EVAL_DELTA (the planner's DX:
+            // what the axis it proved the distance on gives here, a power of two: codegen.uniform_eval_plan) -- and, below,
+            // on the axis form it counted the roundings of (as a scalar branch: in the lanes' condition it cost two scalar
+            // registers across the unit loop).  DX is what numpy's 8-byte arithmetic gives for this very expression on the stored
+            // axis, rounded up to a power of two: the comparison holds on a planned unit only because the units are compiled with
+            // -ffp-contract=off (codegen.HIPCC_FLAGS) -- contracted into an fma the left side is another number, larger than DX on
+            // short axes, and every wave would take the long way below.
+            const bool bnb = fabs(X) < ust[3] && fabs((X - lead.smin) * k_rows - (sdp_real)i) <= (sdp_real)(SDP_BNB_UNIFORM_EVAL_DX);
+#elif SDP_BNB_UNIFORM_ON
             // .. and where this lane's node sits at its own row: the position as the bound stage forms it, against the row
             const bool bnb = fabs(X) < ust[3] && fabs((X - lead.smin) * k_rows - (sdp_real)i) <= (sdp_real)0x1p-22;
 #else
             const bool bnb = fabs(X) < ust[3];
 #endif
             const int row_u = i;
+#if SDP_BNB_EVAL_ON
+            if ((axis_mode == 2 || !(SDP_BNB_UNIFORM_EVAL_UNIT)) && __all(bnb)) {
+#else
             if (__all(bnb)) {                                  // (over the lanes that have a node)
+#endif
                 auto ins = [&](double Fq) {
                     bd.f2 = sdp_vmin(bd.f2, sdp_vmax(bd.f1, Fq));
                     bd.f1 = sdp_vmin(bd.f1, Fq);
                 };
-                if (axis_mode == 2) sdp_short_bnb<2, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u);
-                else if (axis_mode == 1) sdp_short_bnb<1, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u);
-                else sdp_short_bnb<0, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u);
+#if SDP_BNB_EVAL_ON
+                // (no stage of it locates a cell: one instance whatever the axis form)
+                sdp_short_bnb<0, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u, SDP_EREC);
+#else
+                if (axis_mode == 2) sdp_short_bnb<2, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u, SDP_EREC);
+                else if (axis_mode == 1) sdp_short_bnb<1, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u, SDP_EREC);
+                else sdp_short_bnb<0, false>(SDP_LDS_AD, utab, filt, lead, X, k_rows, 0, box.total, mask, slack, guess, ins, diag_cnt, nullptr, row_u, SDP_EREC);
+#endif
             } else
 #endif
+#if SDP_BNB_EVAL_ON
+            {
+                // (a's slots of the control table hold the stage's records in such a unit: there is no full first pass to fall
+                // back on.  The wave's nodes keep no survivor and take every control the long way below -- exact, about 64 times
+                // the work, and never taken on a unit as planned: the diagnostic build SDP_DIAG_BNB_COUNT stores -1 for such a
+                // node, which tests/test_gpu_uniform_eval.py asserts does not happen on either axis form)
+            }
+#else
             {
                 if (axis_mode == 2) sdp_lean2_pass1<2>(SDP_LDS_AD, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
                 else if (axis_mode == 1) sdp_lean2_pass1<1>(SDP_LDS_AD, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
                 else sdp_lean2_pass1<0>(SDP_LDS_AD, utab, filt, lead, X, box.total, mask, bd.f1, bd.f2);
             }
+#endif
             bd.i1 = bd.f1 < (sdp_real)INFINITY ? (__double2loint(bd.f1) & mask) : INT_MAX;
 #else
             SdpColBounds bd;
@@ -723,6 +767,9 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
 #else
             const bool pair = SDP_COL_TOP2 && !bad && !single && bd.i2 != INT_MAX && bd.f3 - radius > m_hi;
 #endif
+#ifdef SDP_DIAG_BNB_COUNT                                  // diagnostic: + 10000 where the first pass left more than its survivors
+            if (!(single || pair) && diag_cnt >= (sdp_real)0) diag_cnt = diag_cnt + (sdp_real)10000;
+#endif
             if (single || pair) {
                 // the survivors ARE the only candidates for the reference's argmin
                 // (their controls, cost and -- a stock the perturbation does not reach -- cell: once)
@@ -744,12 +791,23 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
                 for (int ci = 0; ci < box.total; ++ci) {
                     sdp_real u[SDP_NU];
                     sdp_controls_at(box, ci, u);
+#if SDP_BNB_EVAL_ON
+                    // (no smallest F': the wave could not run the stage, or no F' of the node is a number -- every control the long way)
+                    bool cand = bad || bd.i1 == INT_MAX;
+#else
                     bool cand = bad;
+#endif
                     if (!cand) {
 #if SDP_COL_LEAN2 && SDP_COL_SHIFT
                         sdp_real b_unused = (sdp_real)0;       // (the radius holds the largest B' of the node already)
                         const sdp_real F = lead.pow2 ? sdp_lean2s_value<1>(SDP_LDS_AD, utab, filt, lead1, X, ci, b_unused)
                                                      : sdp_lean2s_value<0>(SDP_LDS_AD, utab, filt, lead1, X, ci, b_unused);
+#elif SDP_BNB_EVAL_ON
+                        // (the uniform evaluation's own form: m_hi is its number, and no table holds a)
+                        const sdp_real F = (sdp_real)sdp_uniform_value(SDP_LDS_AD + i, SDP_EREC, utab, filt, ci);
+                        // (.. and the control m_hi belongs to stays a candidate whatever the radius: with the proven radius it
+                        // is one anyway; with the test knob that shrinks the radius below the index packed into f1's low
+                        // bits, a node was left without any candidate)
 #elif SDP_COL_LEAN2
                         const sdp_real F = lead.pow2 ? sdp_lean2_value<1>(SDP_LDS_AD, utab, filt, lead, X, ci)
                                                      : sdp_lean2_value<0>(SDP_LDS_AD, utab, filt, lead, X, ci);
@@ -758,7 +816,7 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
                         if (lead.pow2) sdp_col_lean_eval<1>(SDP_LDS_AD, filt, lead1, x, u, t, F, pm, gm, bm);
                         else sdp_col_lean_eval<0>(SDP_LDS_AD, filt, lead1, x, u, t, F, pm, gm, bm);
 #endif
-                        cand = !(F - radius > m_hi);
+                        cand = !(F - radius > m_hi) || (SDP_BNB_EVAL_ON && ci == bd.i1);
                     }
                     if (cand) {
                         const sdp_real jc = sdp_col_cost_global<false>(a, tg, s, wts, lead, x, u, t);

@@ -231,6 +231,24 @@
 #else
 #define SDP_BNB_UNIFORM_ON 0
 #endif
+// The UNIFORM EVALUATION stage (round 10; generated with SDP_BNB_UNIFORM_EVAL_DELTA and SDP_BNB_UNIFORM_EVAL_DX where
+// codegen.uniform_eval_plan proves them, only in a unit with the uniform bound stage): control c of lane r is evaluated at
+// row r + k_c + phi_c, k_c = floor(pa_c) and phi_c = pa_c - k_c of the control's own pa_c = fl(+-a_c k) -- the same in every
+// lane -- instead of at the reference's cell; the radius pays for the distance between the two (sdp_short_bnb).  Its
+// records, 16 bytes per control -- (8 k_c, the control's index) as two integers, then phi_c -- lie in the slots a has in the
+// control tables of the two parities, which nothing reads in such a unit (sdp_col_phase_u): the LDS image is what it was.
+// 0 keeps the evaluation that locates every control per node: an A/B switch.
+#ifndef SDP_BNB_UNIFORM_EVAL
+#define SDP_BNB_UNIFORM_EVAL 0
+#endif
+#if SDP_BNB_UNIFORM_ON && SDP_BNB_UNIFORM_EVAL
+#define SDP_BNB_EVAL_ON 1
+#if !SDP_LEAN2_A_FIXED
+#error "SDP_BNB_UNIFORM_EVAL: one copy of the per-control records -- a has to depend on the control alone"
+#endif
+#else
+#define SDP_BNB_EVAL_ON 0
+#endif
 // controls per block of the branch and bound, and the block statistics kept beside the control table (four reals per
 // block: smallest a, largest a, smallest +-h psum, unused): at most 64 blocks -- one lane of the table's wave each
 #ifndef SDP_LEAN2_A_FIXED

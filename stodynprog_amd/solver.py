@@ -2665,6 +2665,10 @@ def plan_info(plan):
                       ('reduced array' if plan['lead_axes'] else 'reduced table'))),
         # x0' = a chain of sums in another nesting than ((a +- b) +- ..), x + (w - u): regrouped for the first pass
         regrouped_sums=bool(filtered and shifted and codegen.shift_chain(model)),
+        # the branch and bound's uniform evaluation stage (codegen.uniform_eval_plan): the rows its positions may lie from the
+        # reference's -- what the radius pays for -- and the node's share of them that the kernel checks
+        uniform_eval=(dict(delta_rows=unit.eval_delta, node_rows=unit.eval_dx, unit_axis=bool(unit.eval_unit_axis))
+                      if (unit is not None and unit.eval_delta and unit.uniform) else None),
         lanes_per_node=plan['lanes'], max_controls=plan['max_u'], box_per_node=bool(plan['per_node']),
         # perturbation variables; 2 or more: kernel 'generic' is the family of csrc/sdp_multiw_kernel.h on their flat law
         n_perturb=int(model.n_perturb), perturb_vars=int(model.n_perturb))
