@@ -39,6 +39,8 @@ DEBUG_INT_MACROS = ('SDP_COL_MIN_WAVES', 'SDP_COL_BATCH', 'SDP_COL_UNROLL_U', 'S
                     'SDP_COL_A_GROUP', 'SDP_COL_FILTER_UNROLL', 'SDP_COL_FILTER_TOP2', 'SDP_COL_FILTER_RUNROLL',
                     'SDP_COL_A_WIDE_LOADS', 'SDP_COLU_WIDE_LOADS', 'SDP_COLU_A_GROUP',
                     'SDP_COL_TAIL_HOLD', 'SDP_SHORT_GROUP', 'SDP_BNB_CHUNK', 'SDP_BNB_LEAN')
+# the reductions of the plain resident-chunk form (table_phase_plan): 0 leaves an item out of the plan -- the A/B switches
+TABLE_PHASE_MACROS = ('SDP_COL_REDUCE_FUSED', 'SDP_COL_DMAX_HI')
 # (SDP_COL_LEAN2 = 0 keeps the resident-chunk kernel on the first pass of section 3.1c: an A/B switch of short_pass_source)
 # (SDP_COL_WRES is a planning switch: it sizes the LDS image -- column_config)
 # (SDP_BNB_UNIFORM = 0 keeps the branch and bound on the bound stage that locates every block end per node: an A/B switch)
@@ -51,7 +53,8 @@ DEBUG_NAMES = frozenset(DEBUG_INT_MACROS + (
     'SDP_STAMP', 'SDP_NO_POW2', 'SDP_EXTRA_DEFINES', 'SDP_COL_FILTER_SCALE', 'SDP_LEAD_FILTER_SCALE',
     'SDP_LEAD_UNROLL', 'SDP_COL_A_LW', 'SDP_COL_FILTER', 'SDP_COL_SHIFT', 'SDP_COL_UTAB', 'SDP_LEAD_FILTER',
     'SDP_COL_THREADS', 'SDP_COL_WCHUNK', 'SDP_STG_CU', 'SDP_COL_WPAIR', 'SDP_COL_WRES', 'SDP_COL_LEAN2', 'SDP_COL_BNB',
-    'SDP_LINE_FILTER', 'SDP_LINE_FILTER_SCALE', 'SDP_LINE_TOP2', 'SDP_BNB_UNIFORM', 'SDP_BNB_UNIFORM_EVAL'))
+    'SDP_LINE_FILTER', 'SDP_LINE_FILTER_SCALE', 'SDP_LINE_TOP2', 'SDP_BNB_UNIFORM', 'SDP_BNB_UNIFORM_EVAL')
+    + TABLE_PHASE_MACROS)
 
 
 def check_debug(debug):
@@ -700,6 +703,11 @@ def _column_lines(model, dtype, unit, debug):
             lines.append('#define SDP_COL_A_WIDE_LOADS 1')
         if unit.tail_hold:
             lines.append('#define SDP_COL_TAIL_HOLD 1    // the tail of the table is built once and held in registers')
+    # (table_phase_plan: the reductions of the plain resident-chunk form)
+    if unit.reduce_fused:
+        lines.append('#define SDP_COL_REDUCE_FUSED 1 // A[r] by fused multiply-adds, one rounding per point')
+    if unit.dmax_hi:
+        lines.append('#define SDP_COL_DMAX_HI 1      // the column bound\'s maximum over the high words, rounded up')
     if unit.form == 'row window':
         lines.append('#define SDP_COL_ROWS {}'.format(unit.window_rows))
     if unit.form == 'table per control':
@@ -1422,14 +1430,18 @@ def column_lds_bytes(n0, w, n_state, dtype):
 #                   the tuning macros the planner defines (SDP_COL_UNROLL_W .. SDP_COLU_WIDE_LOADS); None: not defined -- the
 #                   header's default, or the value an explicit `debug` dict carries (copied as it is); a_lw None: the build
 #                   deals its entries round-robin (no SDP_COL_A_ORDER)
+#   reduce_fused, dmax_hi
+#                   the reductions of the plain resident-chunk form (SDP_COL_REDUCE_FUSED, SDP_COL_DMAX_HI; None: not planned) --
+#                   table_phase_plan
 # ---------------------------------------------------------------------------
 ColumnUnit = collections.namedtuple('ColumnUnit', (
     'form', 'n0', 'w', 'max_controls', 'n_columns', 'threads', 'lds_bytes',
     'filtered', 'wpair', 'shift', 'shift_rows', 'wres', 'frontier', 'utab_n', 'short', 'bnb', 'bnb_pad', 'uniform',
     'window_rows', 'seg_nodes', 'wchunk',
     'unroll_w', 'min_waves', 'a_lw', 'a_group', 'wide_loads', 'tail_hold', 'bnb_chunk', 'colu_wide_loads',
-    'eval_delta', 'eval_dx', 'eval_unit_axis'),
-    defaults=(False, False, False, 0, 0, None, 0, 'none', False, 0, False, 0, 0, 0) + (None,) * 8 + (0.0, 0.0, False))
+    'eval_delta', 'eval_dx', 'eval_unit_axis', 'reduce_fused', 'dmax_hi'),
+    defaults=(False, False, False, 0, 0, None, 0, 'none', False, 0, False, 0, 0, 0) + (None,) * 8 + (0.0, 0.0, False)
+    + (None,) * 2)
 
 
 def _with_build_order(unit, dtype, debug):
@@ -1459,6 +1471,18 @@ def _with_build_order(unit, dtype, debug):
                     and (tail // groups) * (unit.n0 // (2 * lw)) * 4 <= 32):
                 more['tail_hold'] = 1
     return unit._replace(**more)
+
+
+def table_phase_plan(unit, dtype, debug=None):
+    """THE place that decides the lean reductions of a unit (round 11): `unit` with reduce_fused and dmax_hi set where they
+    apply -- the plain resident-chunk form of 8-byte reals, not the shifted lattice.  A[r] and the column's bound feed the
+    certified filter only: no value of the result depends on either.  (`debug`: NAME = 0 leaves an item out.)"""
+    rs = np.dtype(dtype).itemsize
+    if not (unit.form == 'resident chunks' and unit.wres and rs == 8 and unit.filtered and not unit.shift and not unit.wpair):
+        return unit
+    on = lambda name: _dbg(debug, name) != '0'
+    return unit._replace(reduce_fused=1 if on('SDP_COL_REDUCE_FUSED') else None,
+                         dmax_hi=1 if on('SDP_COL_DMAX_HI') else None)
 
 
 def _short_pass(model, dtype, unit, debug):
@@ -1540,7 +1564,7 @@ def column_table_unit(model, dtype, shape, W, max_controls, box, axis, certified
         # spill_hazards); else the small workgroups of the filtered kernel, without a register cap
         unit = unit._replace(min_waves=(max(1, min(4, (COLUMN_LDS_MAX // unit.lds_bytes) * unit.threads // 256))
                                         if wres else 1))
-    return _with_build_order(unit, dtype, debug)
+    return table_phase_plan(_with_build_order(unit, dtype, debug), dtype, debug)
 
 
 def column_percontrol_unit(model, dtype, shape, W, max_controls, debug=None):

@@ -111,6 +111,51 @@ SDP_DEV void sdp_colres_tail(const SdpSweepArgs &a, const SdpGrid<sdp_real, SDP_
 }
 #endif
 
+// ---------------------------------------------------------------------------
+// The reductions of the plain form (round 11; 8-byte reals, no SDP_COL_SHIFT).  A[r] and the column's bound D feed the
+// certified filter alone -- J, policy and index are the reference's bits whatever the filter keeps -- so the sums may round
+// differently and D may be any upper bound of what it was.  One generated macro each (codegen.table_phase_plan); 0 keeps the
+// instruction stream of before, for A/B runs.
+//   SDP_COL_REDUCE_FUSED  A[r] = fma(p_w, T[w][r], ..) in w order, the tail's sum added last: ONE rounding per point where
+//                         the separate product and sum had two (the units are built with -ffp-contract=off: the fma is
+//                         written out), so the (2W+8) u of the radius' derivation covers it with W u to spare.
+//                         tests/test_reduce_fused_exact.py restates this form and holds the radius against it.
+//   SDP_COL_DMAX_HI       the wave's maximum of D[r] from the HIGH WORDS alone: D[r] >= 0 (or +inf), where the unsigned
+//                         order of the high words is the numeric order; D' = (max high word + 1, low word 0) >= D, at most
+//                         D (1 + 2^-20), capped at +inf's pattern.  Every radius and slack is linear in D and needs D' >= D only.
+#ifndef SDP_COL_REDUCE_FUSED
+#define SDP_COL_REDUCE_FUSED 0
+#endif
+#ifndef SDP_COL_DMAX_HI
+#define SDP_COL_DMAX_HI 0
+#endif
+#if (SDP_COL_REDUCE_FUSED || SDP_COL_DMAX_HI) && SDP_COL_SHIFT
+#error "SDP_COL_REDUCE_FUSED / SDP_COL_DMAX_HI: the plain resident-chunk form, not the shifted lattice"
+#endif
+#if !SDP_COL_SHIFT
+// the weights' address for one reduction, opaque to the optimiser: the weights are the same in every unit, and with the
+// fused sums their scalar loads were hoisted out of the unit loop into scalar registers the kernel does not have -- spilled,
+// and read back lane by lane per unit.  (An opaque zero added to it; the pointer itself through the asm cost ten spills more.)
+SDP_DEV const sdp_cst_real *sdp_colres_weights(const sdp_cst_real *p)
+{
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    return p + z;
+}
+// an upper bound of the wave's largest d (d >= 0 or +inf in every lane, never a NaN), the same in every lane: see SDP_COL_DMAX_HI
+// (DPP row shifts, then the rows' last lanes handed on: 0 where a shift has no source lane, the identity of the maximum)
+SDP_DEV double sdp_wave_bound_hi(double d)
+{
+    unsigned h = (unsigned)__double2hiint(d);
+#define SDP_HI_STAGE(ctrl) h = max(h, (unsigned)__builtin_amdgcn_update_dpp(0, (int)h, ctrl, 0xF, 0xF, true))
+    SDP_HI_STAGE(0x111); SDP_HI_STAGE(0x112); SDP_HI_STAGE(0x114); SDP_HI_STAGE(0x118);      // row_shr 1, 2, 4, 8: lane 15 of a row holds the row's
+    SDP_HI_STAGE(0x142); SDP_HI_STAGE(0x143);                                                // row_bcast 15, 31: lane 63 holds the wave's
+#undef SDP_HI_STAGE
+    const int top = __builtin_amdgcn_readlane((int)h, 63);
+    return __hiloint2double(min(top + 1, 0x7ff00000), 0);
+}
+#endif
+
 // diagnostic builds only (results wrong): bit mask of the parts of a unit to leave out -- 1 first build of the tail and
 // its reduction, 2 build of the head and its reduction, 4 first pass, 8 second pass over the head, 16 rebuild of the
 // tail, 32 second pass over the tail, 64 the next unit's column-level tables, 128 the stores
@@ -476,10 +521,17 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
 #else
         sdp_real acc_t = (sdp_real)0, big = (sdp_real)0;
         if (r < N0 && !(SDP_DIAG_SKIP & 1)) {
+#if SDP_COL_REDUCE_FUSED
+            const sdp_cst_real *pt = sdp_colres_weights(pw + C);
+#endif
 #pragma unroll SDP_COL_FILTER_RUNROLL
             for (int w = 0; w < R; ++w) {
                 const sdp_real v = sdp_lds.T[w * N0 + r];
+#if SDP_COL_REDUCE_FUSED
+                acc_t = fma((sdp_real)pt[w], v, acc_t);
+#else
                 acc_t = acc_t + pw[C + w] * v;
+#endif
                 big = sdp_vmax_abs(big, v);
             }
         }
@@ -500,10 +552,17 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
 #endif
             if (r < N0) {
                 sdp_real acc = (sdp_real)0;
+#if SDP_COL_REDUCE_FUSED
+                const sdp_cst_real *ph = sdp_colres_weights(pw);
+#endif
 #pragma unroll SDP_COL_FILTER_RUNROLL
                 for (int w = 0; w < ((SDP_DIAG_SKIP & 2) ? 0 : C); ++w) {
                     const sdp_real v = sdp_lds.T[w * N0 + r];
+#if SDP_COL_REDUCE_FUSED
+                    acc = fma((sdp_real)ph[w], v, acc);
+#else
                     acc = acc + pw[w] * v;
+#endif
                     big = sdp_vmax_abs(big, v);
                 }
                 acc = acc + acc_t;
@@ -536,7 +595,11 @@ extern "C" __global__ void __launch_bounds__(SDP_COL_THREADS, SDP_COL_MIN_WAVES)
                 if (pl < SDP_BNB_PAD) SDP_LDS_AD[N0 + pl] = fma((sdp_real)(pl + 1), a0 - a1, a0);
             }
 #endif
+#if SDP_COL_DMAX_HI
+            dmax = (sdp_real)sdp_wave_bound_hi((double)dmax);
+#else
             dmax = sdp_wave_max(dmax);
+#endif
             if (lane == 0) atomicMax(&sdp_lds.dcol[parity], (unsigned long long)__double_as_longlong((double)dmax));
         }
 #endif

@@ -12,7 +12,7 @@ import sys
 
 SWITCHES = [
     'SDP_COL_FILTER=0', 'SDP_COL_SHIFT=0', 'SDP_COL_UTAB=0', 'SDP_COL_LEAN2=0', 'SDP_COL_BNB=0', 'SDP_BNB_UNIFORM=0',
-    'SDP_BNB_UNIFORM_EVAL=0',
+    'SDP_BNB_UNIFORM_EVAL=0', 'SDP_COL_REDUCE_FUSED=0', 'SDP_COL_DMAX_HI=0',
     'SDP_COL_WRES=0', 'SDP_COL_WRES=24', 'SDP_COL_TAIL_HOLD=0',
     'SDP_COL_WPAIR=0', 'SDP_COL_WPAIR=1',
     'SDP_COL_THREADS=512', 'SDP_COL_THREADS=1024', 'SDP_COL_MIN_WAVES=2', 'SDP_COL_UNROLL_W=2',
