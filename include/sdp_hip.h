@@ -531,6 +531,39 @@ int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_t B, int64_
                           void *host_x_final, uint64_t *host_occupancy);
 
 /*
+ * Closed loops of a family over a horizon (csrc/sdp_family_horizon_kernel.h).  The family's HORIZON unit
+ * (codegen.family_horizon_unit: kernels sdp_family_simulate and, for a stochastic family, sdp_family_montecarlo_h) is
+ * loaded beside the sweep unit; its sdp_meta is checked (SDP_META_F_FAMILY_HORIZON, the two workgroup sizes).
+ */
+int sdp_family_load_horizon_unit(sdp_family *f, const char *module_path);
+/*
+ * sdp_problem_simulate_h of every member of the handle, together: B trajectories of T >= 1 steps per member.
+ * host_pol is [P][pol_steps][nu][S] reals: a time-indexed policy (pol_timed != 0, pol_steps == T: it goes up a chunk
+ * of whole steps of all members at a time, at most chunk_bytes, a larger step a chunk of its own) or one stationary
+ * policy per member (pol_timed == 0, pol_steps == 1: uploaded once, read with a step stride of 0).  host_prm is the
+ * table of lifted constants [P][T][n_prm] (prm_timed != 0) or [P][1][n_prm] (prm_timed == 0: a model that is symbolic
+ * in time, one row per member for every step); n_prm is the family's.  host_x0 [P][d][B], host_w [P][T][B] (NULL: a
+ * deterministic family); results host_x [P][T+1][d][B], host_u [P][T][nu][B], host_g [P][T][B].  Member p of every
+ * result has the bits of sdp_problem_simulate_h on problem p alone; no cut changes one.  sdp_family_last_kernel_ms
+ * covers the call.  SDP_EINVAL for a NULL pointer, a negative size, T < 1, a policy or table of another length,
+ * chunk_bytes < 1, missing perturbation sequences, or no unit loaded.
+ */
+int sdp_family_simulate(sdp_family *f, const void *host_pol, int64_t pol_steps, int32_t pol_timed, const void *host_prm,
+                        int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes, int64_t B, int64_t T,
+                        const void *host_x0, const void *host_w, double t0, void *host_x, void *host_u, void *host_g);
+/*
+ * sdp_problem_montecarlo_h of every member of the handle, together: the arguments and results of
+ * sdp_family_montecarlo with the policy and the table of sdp_family_simulate.  Launches are cut at the policy's
+ * chunks and at steps_per_launch; the states, the sums, n_outside and the occupancy stay on the device in between.
+ */
+int sdp_family_montecarlo_h(sdp_family *f, const void *host_pol, int64_t pol_steps, int32_t pol_timed,
+                            const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes, int64_t B,
+                            int64_t T, int64_t n_burn, const uint64_t *host_seeds, uint64_t traj_offset,
+                            const void *host_x0, const double *host_cum, int32_t n_law, const void *host_law_grid,
+                            double t0, int64_t steps_per_launch, void *host_cost_sum, int64_t *host_n_outside,
+                            void *host_x_final, uint64_t *host_occupancy);
+
+/*
  * One-step lookahead at arbitrary states for a family (csrc/sdp_family_lookahead_kernel.h).  The family's LOOKAHEAD
  * unit (codegen.family_lookahead_unit: kernels sdp_family_lookahead and, for a stochastic family,
  * sdp_family_montecarlo_lookahead) is loaded beside the sweep unit; its sdp_meta is checked.

@@ -151,6 +151,10 @@ def _declare(lib):
         'sdp_family_load_mc_unit': (C.c_int, [vp, C.c_char_p]),
         'sdp_family_montecarlo': (C.c_int, [vp, vp, i64, i64, i64, vp, C.c_uint64, vp, vp, i32, vp, dbl, i64, vp, vp,
                                             vp, vp]),
+        'sdp_family_load_horizon_unit': (C.c_int, [vp, C.c_char_p]),
+        'sdp_family_simulate': (C.c_int, [vp, vp, i64, i32, vp, i32, i32, i64, i64, i64, vp, vp, dbl, vp, vp, vp]),
+        'sdp_family_montecarlo_h': (C.c_int, [vp, vp, i64, i32, vp, i32, i32, i64, i64, i64, i64, vp, C.c_uint64, vp, vp,
+                                              i32, vp, dbl, i64, vp, vp, vp, vp]),
         'sdp_family_load_lookahead_unit': (C.c_int, [vp, C.c_char_p]),
         'sdp_family_set_lookahead_box': (C.c_int, [vp, vp, i32, vp]),
         'sdp_family_lookahead': (C.c_int, [vp, i64, vp, dbl, vp, vp, vp]),

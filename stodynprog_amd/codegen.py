@@ -915,6 +915,26 @@ def family_mc_unit(model, dtype):
     return '\n'.join(head)
 
 
+def family_horizon_unit(model, dtype):
+    """The generated source of a family HORIZON unit (csrc/sdp_family_horizon_kernel.h, kernels `sdp_family_simulate`
+    and, for a stochastic model, `sdp_family_montecarlo_h`): the direct prologue of a model with lifted constants,
+    marked SDP_FAMILY and SDP_FAMILY_HORIZON, and the horizon header in the place of sdp_sweep_kernel.h.  A closed
+    loop has no control lattice, so there is one unit per model structure and real type (the lane count the prologue
+    prints is 1 and nothing reads it); the steps of a model traced per step (`data[k]`) share it, each with its row
+    of constants."""
+    if model.param_index is None:
+        raise ValueError('a family unit takes a model with lifted constants (TracedModel.lift_constants)')
+    if model.n_perturb >= 2:
+        raise NotImplementedError('a family unit takes one perturbation variable at most')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, 1, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
+    head.insert(at + 1, '#define SDP_FAMILY_HORIZON 1  // .. and the closed loops over a horizon in the place of sdp_family_sweep')
+    head += ['#include "sdp_family_horizon_kernel.h"    // brings in sdp_family_kernel.h and the draw helpers of sdp_mc_kernel.h', '']
+    return '\n'.join(head)
+
+
 def family_lookahead_unit(model, box, dtype, lanes):
     """The generated source of a family LOOKAHEAD unit (csrc/sdp_family_lookahead_kernel.h, kernels
     `sdp_family_lookahead` and `sdp_family_montecarlo_lookahead`): the direct prologue of a model with lifted
@@ -1668,6 +1688,10 @@ def source_key(source):
             h.update(f.read())
     if '#define SDP_FAMILY_MC ' in source:
         with open(os.path.join(CSRC, 'sdp_family_mc_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_FAMILY_HORIZON ' in source:
+        # (it includes sdp_family_kernel.h, above, and sdp_mc_kernel.h, one of _HEADERS)
+        with open(os.path.join(CSRC, 'sdp_family_horizon_kernel.h'), 'rb') as f:
             h.update(f.read())
     if '#define SDP_FAMILY_LOOKAHEAD ' in source:
         # (it includes sdp_family_kernel.h, above, sdp_mc_kernel.h, one of _HEADERS, and the lattice rule)

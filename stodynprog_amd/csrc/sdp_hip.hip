@@ -3775,6 +3775,10 @@ struct sdp_family {
     // Monte Carlo evaluation (sdp_family_load_mc_unit): the unit and its kernel; the arrays of a run live for the call
     hipModule_t mcmod = nullptr;
     hipFunction_t f_montecarlo = nullptr;
+    // closed loops over a horizon (sdp_family_load_horizon_unit): the unit and its kernels (f_hz_montecarlo: a stochastic
+    // family's only); the arrays of a run live for the call
+    hipModule_t hzmod = nullptr;
+    hipFunction_t f_hz_simulate = nullptr, f_hz_montecarlo = nullptr;
     // lookahead at arbitrary states (sdp_family_load_lookahead_unit): the unit, its two kernels, the lanes of a state and
     // the constants of its box function per member; the members' box constants and control steps (sdp_family_set_lookahead_box)
     hipModule_t lkmod = nullptr;
@@ -3799,6 +3803,7 @@ struct sdp_family {
         if (mod) (void)hipModuleUnload(mod);
         if (pmod) (void)hipModuleUnload(pmod);
         if (mcmod) (void)hipModuleUnload(mcmod);
+        if (hzmod) (void)hipModuleUnload(hzmod);
         if (lkmod) (void)hipModuleUnload(lkmod);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -4575,6 +4580,261 @@ extern "C" int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
     f->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, P * (size_t)f->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Closed loops of a family over a horizon (csrc/sdp_family_horizon_kernel.h): sdp_problem_simulate_h and
+// sdp_problem_montecarlo_h of every member in one launch per cut of the steps.  The unit is loaded beside the sweep
+// unit; the arrays of a run live for the call.  The policy [P][pol_steps][nu][S] is time-indexed (pol_steps == T: it
+// goes up a chunk of whole steps of all members at a time, at most chunk_bytes) or stationary (pol_steps == 1: one
+// slice per member, uploaded once and read with a step stride of 0); the table of constants [P][rows][n_prm] has
+// rows == T or, for a model that is symbolic in time, rows == 1 and a step stride of 0.
+// ---------------------------------------------------------------------------
+extern "C" int sdp_family_load_horizon_unit(sdp_family *f, const char *module_path)
+{
+    if (!f || !module_path) return fail(SDP_EINVAL, "NULL argument");
+    if (f->hzmod) { (void)hipModuleUnload(f->hzmod); f->hzmod = nullptr; f->f_hz_simulate = nullptr; f->f_hz_montecarlo = nullptr; }
+    const size_t rs = real_size(f->dtype);
+    hipError_t e = hipModuleLoad(&f->hzmod, module_path);
+    if (e != hipSuccess) { f->hzmod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", module_path, hipGetErrorString(e)); }
+    int32_t m[SDP_META_WORDS] = {0};
+    hipDeviceptr_t mptr = nullptr;
+    size_t mbytes = 0;
+    const char *why = nullptr;
+    if (hipModuleGetGlobal(&mptr, &mbytes, f->hzmod, "sdp_meta") != hipSuccess || mbytes != sizeof(m)) {
+        (void)hipGetLastError();
+        why = "it does not declare `sdp_meta`";
+    } else {
+        HIP_TRY(hipMemcpyDtoH(m, mptr, sizeof(m)));
+        if (m[SDP_META_MAGIC_AT] != SDP_META_MAGIC) why = "bad magic";
+        else if (!(m[SDP_META_FLAGS] & SDP_META_F_FAMILY_HORIZON)) why = "not a family horizon unit";
+        else if (m[SDP_META_COL_ROWS] != 64) why = "its closed loop is built for another workgroup size";
+        else if (m[SDP_META_REAL_BYTES] != (int)rs) why = "built for other reals";
+        else if (m[SDP_META_D] != f->d) why = "built for another number of state variables";
+        else if (m[SDP_META_NU] != f->nu) why = "built for another number of controls";
+        else if ((m[SDP_META_HAS_W] != 0) != (f->W > 0)) why = "built for another kind of perturbation";
+        else if (f->W > 0 && m[SDP_META_THREADS] != 256) why = "its Monte Carlo loop is built for another workgroup size";
+    }
+    hipDeviceptr_t pptr = nullptr;
+    size_t pbytes = 0;
+    if (!why) {
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->hzmod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs) why = "another number of lifted constants";
+    }
+    if (!why && hipModuleGetFunction(&f->f_hz_simulate, f->hzmod, "sdp_family_simulate") != hipSuccess) why = "no sdp_family_simulate kernel";
+    if (!why && f->W > 0 && hipModuleGetFunction(&f->f_hz_montecarlo, f->hzmod, "sdp_family_montecarlo_h") != hipSuccess)
+        why = "no sdp_family_montecarlo_h kernel";
+    if (why) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(f->hzmod);
+        f->hzmod = nullptr; f->f_hz_simulate = nullptr; f->f_hz_montecarlo = nullptr;
+        return fail(SDP_EMODULE, "code object %s was not built for this family's closed loops over a horizon: %s", module_path, why);
+    }
+    return SDP_OK;
+}
+
+// what both calls check of the policy and the table, and the steps of policy one upload holds (of all members)
+static int family_horizon_checks(sdp_family *f, const char *what, int64_t pol_steps, int32_t pol_timed, const void *host_prm,
+                                 int32_t n_prm, int64_t chunk_bytes, int64_t T, int64_t *per_chunk)
+{
+    if (T < 1) return fail(SDP_EINVAL, "%s: %lld steps: at least 1", what, (long long)T);
+    if (pol_steps != (pol_timed ? T : 1))
+        return fail(SDP_EINVAL, "%s: %lld policy steps for %lld steps (%s)", what, (long long)pol_steps, (long long)T,
+                    pol_timed ? "a time-indexed policy has one per step" : "a stationary policy has one");
+    if (chunk_bytes < 1) return fail(SDP_EINVAL, "%s: chunk_bytes = %lld: at least 1", what, (long long)chunk_bytes);
+    if (n_prm != f->n_params || (n_prm > 0 && !host_prm))
+        return fail(SDP_EINVAL, "%s: the family has %d lifted constant(s) per member and step, the table has %d", what,
+                    (int)f->n_params, (int)n_prm);
+    const size_t step_bytes = (size_t)f->P * f->nu * f->S * real_size(f->dtype);
+    int64_t n = pol_timed ? (int64_t)((size_t)chunk_bytes / step_bytes) : T;
+    if (n < 1) n = 1;
+    if (n > T) n = T;
+    *per_chunk = n;
+    return SDP_OK;
+}
+
+// the slices [first, first + n) of every member's policy into the device's [P][per_chunk][nu][S]
+static int family_horizon_upload_policy(sdp_family *f, DevBuf &dpol, const void *host_pol, int64_t pol_steps,
+                                        int64_t per_chunk, int64_t first, int64_t n)
+{
+    const size_t slice = (size_t)f->nu * f->S * real_size(f->dtype);
+    for (size_t p = 0; p < (size_t)f->P; ++p)
+        HIP_TRY(hipMemcpy((char *)dpol.p + p * (size_t)per_chunk * slice,
+                          (const char *)host_pol + (p * (size_t)pol_steps + (size_t)first) * slice, (size_t)n * slice,
+                          hipMemcpyHostToDevice));
+    return SDP_OK;
+}
+
+// workgroups per XCD of a launch whose members have `tiles` tiles each (sdp_family_horizon_kernel.h), at most `cap`
+static int64_t family_horizon_per_xcd(const sdp_family *f, int64_t tiles, int64_t cap)
+{
+    const int parts = f->P >= 8 ? 1 : 8 / f->P;
+    int64_t per_xcd = f->P >= 8 ? (int64_t)((f->P + 7) / 8) * tiles : (tiles + parts - 1) / parts;
+    if (per_xcd > cap) per_xcd = cap;
+    if (per_xcd < 1) per_xcd = 1;
+    return per_xcd;
+}
+
+extern "C" int sdp_family_simulate(sdp_family *f, const void *host_pol, int64_t pol_steps, int32_t pol_timed,
+                                   const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes,
+                                   int64_t B, int64_t T, const void *host_x0, const void *host_w, double t0,
+                                   void *host_x, void *host_u, void *host_g)
+{
+    if (!f || !host_pol || !host_x0 || !host_x || !host_u || !host_g) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0) return fail(SDP_EINVAL, "negative size");
+    if (!f->f_hz_simulate) return fail(SDP_EINVAL, "no horizon unit loaded (sdp_family_load_horizon_unit)");
+    int rc;
+    int64_t per_chunk = 0;
+    if ((rc = family_horizon_checks(f, "sdp_family_simulate", pol_steps, pol_timed, host_prm, n_prm, chunk_bytes, T, &per_chunk))) return rc;
+    if (f->W > 0 && !host_w) return fail(SDP_EINVAL, "a stochastic family needs the perturbation sequences");
+    if (B == 0) return SDP_OK;
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    const size_t slice = (size_t)f->nu * f->S * rs;
+    const int64_t prm_rows = prm_timed ? T : 1;
+    DevBuf dpol, dprm, dw, dx, du, dg;
+    if ((rc = dpol.alloc(P * (size_t)(pol_timed ? per_chunk : 1) * slice))) return rc;
+    if (n_prm > 0 && (rc = upload(dprm, host_prm, P * (size_t)prm_rows * n_prm * rs))) return rc;
+    if (f->W > 0 && (rc = upload(dw, host_w, P * (size_t)T * B * rs))) return rc;                // [P][T][B]
+    if ((rc = dx.alloc(P * (size_t)(T + 1) * f->d * B * rs))) return rc;
+    if ((rc = du.alloc(P * (size_t)T * f->nu * B * rs))) return rc;
+    if ((rc = dg.alloc(P * (size_t)T * B * rs))) return rc;
+    // row 0 of every member's x
+    for (size_t p = 0; p < P; ++p)
+        HIP_TRY(hipMemcpy((char *)dx.p + p * (size_t)(T + 1) * f->d * B * rs, (const char *)host_x0 + p * (size_t)f->d * B * rs,
+                          (size_t)f->d * B * rs, hipMemcpyHostToDevice));
+    SdpFamilySimHArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.prm = n_prm > 0 ? dprm.p : nullptr; a.axes = f->axes.p; a.w = f->W > 0 ? dw.p : nullptr;
+    a.x = dx.p; a.u = du.p; a.g = dg.p;
+    a.B = B; a.S = f->S; a.T = T; a.t0 = t0; a.n_axes = f->n_axes; a.P = f->P;
+    a.pol_step_stride = pol_timed ? (int64_t)f->nu * f->S : 0;
+    a.pol_member_stride = (int64_t)(pol_timed ? per_chunk : 1) * f->nu * f->S;
+    a.prm_step_stride = prm_timed ? (int64_t)n_prm : 0;
+    a.prm_member_stride = prm_rows * (int64_t)n_prm;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = f->orders[k]; a.axis_off[k] = f->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    // a tile of 64 trajectories of one member is a workgroup.  A multiple of 8 workgroups (one share per XCD): per XCD as
+    // many as it has tiles to walk, at most the solo call's cus * 32 split over the 8 XCDs, the rest in the stride loop
+    const int64_t per_xcd = family_horizon_per_xcd(f, (B + 63) / 64, (int64_t)f->cus * 32 / 8);
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    double kernel_ms = 0;
+    if (!pol_timed && (rc = family_horizon_upload_policy(f, dpol, host_pol, 1, 1, 0, 1))) return rc;
+    for (int64_t k = 0; k < T; k += per_chunk) {
+        const int64_t n = (T - k < per_chunk) ? T - k : per_chunk;
+        // (the kernel of the previous chunk has finished: the stream is synchronised at the end of every round)
+        if (pol_timed && (rc = family_horizon_upload_policy(f, dpol, host_pol, pol_steps, per_chunk, k, n))) return rc;
+        a.chunk_first = k; a.step_begin = k; a.step_end = k + n;
+        HIP_TRY(hipEventRecord(f->ev0, f->stream));
+        HIP_TRY(hipModuleLaunchKernel(f->f_hz_simulate, (unsigned)(per_xcd * 8), 1, 1, 64, 1, 1, 0, f->stream, nullptr, extra));
+        HIP_TRY(hipEventRecord(f->ev1, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+        kernel_ms += ms;
+    }
+    f->last_kernel_ms = kernel_ms;
+    HIP_TRY(hipMemcpy(host_x, dx.p, P * (size_t)(T + 1) * f->d * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_u, du.p, P * (size_t)T * f->nu * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_g, dg.p, P * (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_montecarlo_h(sdp_family *f, const void *host_pol, int64_t pol_steps, int32_t pol_timed,
+                                       const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes,
+                                       int64_t B, int64_t T, int64_t n_burn, const uint64_t *host_seeds,
+                                       uint64_t traj_offset, const void *host_x0, const double *host_cum, int32_t n_law,
+                                       const void *host_law_grid, double t0, int64_t steps_per_launch,
+                                       void *host_cost_sum, int64_t *host_n_outside, void *host_x_final,
+                                       uint64_t *host_occupancy)
+{
+    if (!f || !host_pol || !host_seeds || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0) return fail(SDP_EINVAL, "negative size");
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (f->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw: use sdp_family_simulate");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    if (!f->f_hz_montecarlo) return fail(SDP_EINVAL, "no horizon unit loaded (sdp_family_load_horizon_unit)");
+    int rc;
+    int64_t per_chunk = 0;
+    if ((rc = family_horizon_checks(f, "sdp_family_montecarlo_h", pol_steps, pol_timed, host_prm, n_prm, chunk_bytes, T, &per_chunk))) return rc;
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    const size_t slice = (size_t)f->nu * f->S * rs;
+    const int64_t prm_rows = prm_timed ? T : 1;
+    // (the draw table of one member in LDS: the cumulative sums, then the values)
+    const size_t lds_bytes = (size_t)(n_law - 1) * 8 + (size_t)n_law * rs;
+    if (lds_bytes > 65536)
+        return fail(SDP_EINVAL, "a law of %d points needs %zu bytes of LDS: at most 65536", (int)n_law, lds_bytes);
+    DevBuf dpol, dprm, dx, dacc, dout, dcum, dlaw, dseed, docc;
+    if ((rc = dpol.alloc(P * (size_t)(pol_timed ? per_chunk : 1) * slice))) return rc;
+    if (n_prm > 0 && (rc = upload(dprm, host_prm, P * (size_t)prm_rows * n_prm * rs))) return rc;
+    if ((rc = upload(dx, host_x0, P * (size_t)f->d * B * rs))) return rc;                 // [P][d][B]
+    if ((rc = upload(dcum, host_cum, P * (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, P * (size_t)n_law * rs))) return rc;
+    if ((rc = upload(dseed, host_seeds, P * 8))) return rc;
+    if ((rc = dacc.alloc(P * (size_t)B * rs))) return rc;
+    if ((rc = dout.alloc(P * (size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, P * (size_t)B * rs, f->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, P * (size_t)B * 8, f->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc(P * (size_t)f->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, P * (size_t)f->S * 8, f->stream));
+    }
+    SdpFamilyMcHArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.prm = n_prm > 0 ? dprm.p : nullptr; a.axes = f->axes.p; a.cum = (const double *)dcum.p; a.law_grid = dlaw.p;
+    a.seed = (const uint64_t *)dseed.p; a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.S = f->S; a.traj_offset = traj_offset; a.n_burn = n_burn; a.t0 = t0;
+    a.n_law = n_law; a.n_axes = f->n_axes; a.P = f->P;
+    a.pol_step_stride = pol_timed ? (int64_t)f->nu * f->S : 0;
+    a.pol_member_stride = (int64_t)(pol_timed ? per_chunk : 1) * f->nu * f->S;
+    a.prm_step_stride = prm_timed ? (int64_t)n_prm : 0;
+    a.prm_member_stride = prm_rows * (int64_t)n_prm;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = f->orders[k]; a.axis_off[k] = f->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    // (the launch shape of sdp_family_montecarlo)
+    const int threads = 256;
+    const unsigned lds = (unsigned)lds_bytes;
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f->f_hz_montecarlo, threads, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 8) per_cu = 8;
+    const int64_t per_xcd = family_horizon_per_xcd(f, (B + threads - 1) / threads, (int64_t)f->cus * per_cu / 8);
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    double kernel_ms = 0;
+    if (!pol_timed && (rc = family_horizon_upload_policy(f, dpol, host_pol, 1, 1, 0, 1))) return rc;
+    for (int64_t c = 0; c < T; c += per_chunk) {
+        const int64_t c_end = (T - c < per_chunk) ? T : c + per_chunk;
+        if (pol_timed && (rc = family_horizon_upload_policy(f, dpol, host_pol, pol_steps, per_chunk, c, c_end - c))) return rc;
+        a.chunk_first = c;
+        HIP_TRY(hipEventRecord(f->ev0, f->stream));
+        for (int64_t k = c; k < c_end; k += steps_per_launch) {
+            a.step_begin = k;
+            a.step_end = (c_end - k < steps_per_launch) ? c_end : k + steps_per_launch;
+            HIP_TRY(hipModuleLaunchKernel(f->f_hz_montecarlo, (unsigned)(per_xcd * 8), 1, 1, threads, 1, 1, lds, f->stream, nullptr, extra));
+        }
+        HIP_TRY(hipEventRecord(f->ev1, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+        kernel_ms += ms;
+    }
+    f->last_kernel_ms = kernel_ms;
     HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));

@@ -44,6 +44,9 @@ enum {
     SDP_META_F_FAMILY_LOOKAHEAD = 8192 // a family lookahead unit (sdp_family_lookahead_kernel.h): sdp_family_lookahead and
                             // sdp_family_montecarlo_lookahead; SDP_META_THREADS is their workgroup size, SDP_META_COL_ROWS the
                             // lanes of a state (SDP_LANES) and SDP_META_UTAB the constants of the box function per member
+    , SDP_META_F_FAMILY_HORIZON = 16384 // a family horizon unit (sdp_family_horizon_kernel.h): sdp_family_simulate and, for a
+                            // stochastic family, sdp_family_montecarlo_h; SDP_META_THREADS is the Monte Carlo kernel's
+                            // workgroup size and SDP_META_COL_ROWS that of sdp_family_simulate
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -225,6 +228,63 @@ struct SdpFamilyLookMcArgs {
     double t0;             // time index of step 0 of the call
     int32_t n_law;         // points of every drawn law (>= 1)
     int32_t pad_;
+};
+
+// Closed loops of a family over a horizon (sdp_family_horizon_kernel.h): SdpSimHArgs and SdpMcHArgs with a member index
+// in front of every array.  The policy and the table of constants are addressed by two strides each, in reals: member p
+// at step k of the call reads the policy slice pol + p * pol_member_stride + (k - chunk_first) * pol_step_stride and the
+// row prm + p * prm_member_stride + k * prm_step_stride.  A step stride of 0 is one slice (a stationary policy) or one
+// row (a model that is symbolic in time) for every step.
+struct SdpFamilySimHArgs {
+    const void *pol;       // [P][steps of this launch's chunk, or 1][nu][S]
+    const void *prm;       // [P][steps of the call, or 1][SDP_NPARAMS]
+    const void *axes;      // [P][n_axes] concatenated state-grid axes of every member; axis k at axis_off[k]
+    const void *w;         // [P][T][B] perturbation sequences of the whole call (null: deterministic members)
+    void *x;               // [P][T+1][d][B] states of the whole call: row step_begin read, rows step_begin + 1 .. step_end written
+    void *u;               // [P][T][nu][B] controls applied
+    void *g;               // [P][T][B] instantaneous costs
+    int64_t B;             // trajectories of one member
+    int64_t S;             // state nodes of one member
+    int64_t T;             // steps of the whole call
+    int64_t pol_member_stride, pol_step_stride;
+    int64_t prm_member_stride, prm_step_stride;
+    int64_t step_begin;    // first step of this launch (step of the call)
+    int64_t step_end;      // one past its last step
+    int64_t chunk_first;   // step of the call whose policy slice is the member's first on the device
+    double t0;             // time index of step 0 of the call
+    int32_t n_axes;        // sum of orders: reals per row of `axes`
+    int32_t P;             // members (>= 1): all of them run
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+};
+
+struct SdpFamilyMcHArgs {
+    const void *pol;       // as SdpFamilySimHArgs
+    const void *prm;
+    const void *axes;
+    const double *cum;     // as SdpFamilyMcArgs from here on
+    const void *law_grid;
+    const uint64_t *seed;
+    void *x;
+    void *acc;
+    long long *n_outside;
+    unsigned long long *occupancy;
+    int64_t B;
+    int64_t S;
+    int64_t pol_member_stride, pol_step_stride;
+    int64_t prm_member_stride, prm_step_stride;
+    uint64_t traj_offset;
+    int64_t step_begin;
+    int64_t step_end;
+    int64_t n_burn;
+    int64_t chunk_first;   // step of the call whose policy slice is the member's first on the device
+    double t0;
+    int32_t n_law;
+    int32_t n_axes;
+    int32_t P;
+    int32_t pad_;
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
 };
 
 // Batched closed-loop simulation (the user loop of the reference's examples, e.g.

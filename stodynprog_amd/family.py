@@ -19,9 +19,15 @@ decisions -- the controller that would run -- together (csrc/sdp_family_lookahea
 `sdp_family_lookahead` and `sdp_family_montecarlo_lookahead`, a tile of (64 / lanes) x 4 states of one member a
 workgroup, every lattice made on the device from the member's traced control_box with its constants lifted.
 
+`simulate` and `monte_carlo_horizon` run the members' policies forward over a horizon together -- the policies
+`bellman_recursion` returns, time-indexed per member, or stationary ones -- also for members whose model looks data up as
+`data[k]` (csrc/sdp_family_horizon_kernel.h): kernels `sdp_family_simulate`, a tile of 64 trajectories of one member a
+workgroup, and `sdp_family_montecarlo_h`, a tile of 256, each step with the member's policy slice and row of constants
+of that step.
+
 The definition is the solo call: member p of every result equals, bit for bit, what `solvers[p]` returns from the
-same method with `kernel = 'generic'` (`monte_carlo`, `lookahead`, `monte_carlo_lookahead`: on its device path,
-whatever its kernel).
+same method with `kernel = 'generic'` (`monte_carlo`, `lookahead`, `monte_carlo_lookahead`, `simulate` and
+`monte_carlo_horizon`, the latter against `solvers[p].monte_carlo`: on its device path, whatever its kernel).
 
 Members may differ in every real constant of dyn / cost, in the ends of the state grid, in the perturbation grid
 and weights, in control_steps and control_box.  They must agree in the grid's shape, the dtype, the number of
@@ -176,6 +182,43 @@ class _FamilyProblem(object):
             self.h, nat.ptr(pol), B, int(n_steps), int(n_burn), nat.ptr(seeds), int(traj_offset), nat.ptr(x0),
             nat.ptr(cum), int(cum.shape[1]), nat.ptr(law_grid), float(t0), int(steps_per_launch), nat.ptr(cost_sum),
             nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
+        return cost_sum, n_out, x_final, occ
+
+    # ---- closed loops over a horizon (csrc/sdp_family_horizon_kernel.h)
+    def load_horizon_unit(self, module):
+        nat.check(nat.lib().sdp_family_load_horizon_unit(self.h, module.encode()))
+
+    def simulate_h(self, pol, pol_timed, table, prm_timed, chunk_bytes, x0, w, n_steps, t0):
+        """pol [P][T or 1][nu][S], table [P][T or 1][n_prm], x0 [P][d][B], w [P][T][B] or None: (x [P][T+1][d][B],
+        u [P][T][nu][B], g [P][T][B])"""
+        d, B, T = x0.shape[1], x0.shape[2], int(n_steps)
+        assert pol.shape[0] == table.shape[0] == x0.shape[0] == self.P and pol.shape[2:] == (self.nu, self.S)
+        assert w is None or w.shape == (self.P, T, B)
+        assert all(a.flags.c_contiguous for a in (pol, table, x0) + (() if w is None else (w,)))
+        x = np.empty((self.P, T + 1, d, B), dtype=self.dtype)
+        u = np.empty((self.P, T, self.nu, B), dtype=self.dtype)
+        g = np.empty((self.P, T, B), dtype=self.dtype)
+        nat.check(nat.lib().sdp_family_simulate(
+            self.h, nat.ptr(pol), int(pol.shape[1]), int(bool(pol_timed)), nat.ptr(table) if table.size else None,
+            int(table.shape[2]), int(bool(prm_timed)), int(chunk_bytes), B, T, nat.ptr(x0), nat.ptr(w), float(t0),
+            nat.ptr(x), nat.ptr(u), nat.ptr(g)))
+        return x, u, g
+
+    def montecarlo_h(self, pol, pol_timed, table, prm_timed, chunk_bytes, x0, n_steps, n_burn, seeds, traj_offset, cum,
+                     law_grid, t0, steps_per_launch, occupancy):
+        """pol and table as in `simulate_h`, the rest as in `montecarlo`: what `montecarlo` returns"""
+        d, B = x0.shape[1], x0.shape[2]
+        assert pol.shape[0] == table.shape[0] == x0.shape[0] == self.P and pol.shape[2:] == (self.nu, self.S)
+        assert cum.shape == law_grid.shape and all(a.flags.c_contiguous for a in (pol, table, x0, cum, law_grid, seeds))
+        cost_sum = np.empty((self.P, B), dtype=self.dtype)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, d, B), dtype=self.dtype)
+        occ = np.empty((self.P, self.S), dtype=np.uint64) if occupancy else None
+        nat.check(nat.lib().sdp_family_montecarlo_h(
+            self.h, nat.ptr(pol), int(pol.shape[1]), int(bool(pol_timed)), nat.ptr(table) if table.size else None,
+            int(table.shape[2]), int(bool(prm_timed)), int(chunk_bytes), B, int(n_steps), int(n_burn), nat.ptr(seeds),
+            int(traj_offset), nat.ptr(x0), nat.ptr(cum), int(cum.shape[1]), nat.ptr(law_grid), float(t0),
+            int(steps_per_launch), nat.ptr(cost_sum), nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
         return cost_sum, n_out, x_final, occ
 
     # ---- lookahead at arbitrary states (csrc/sdp_family_lookahead_kernel.h)
@@ -384,20 +427,24 @@ class SolverFamily(object):
         step = max(1, int(self.chunk_bytes) // (self._member_bytes(tabs) + extra))
         return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
 
-    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None):
+    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None, horizon=None):
         """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims.  evaluation: the
         call evaluates policies, so every handle also loads the family's evaluation unit and the chunks leave room
         for the prescribed policy.  mc_bytes: the call is a Monte Carlo run whose arrays take that many bytes a
         member beside the handle's, so every handle also loads the family's Monte Carlo unit (J0 is None then: the
         values of a handle that is reused stay what they were).  look: the call is a lookahead (`_lookahead_tables`:
         source, bprm, steps, bytes a member takes beside the handle's), so every handle also loads the family's
-        lookahead unit and is given its members' box constants and control steps"""
+        lookahead unit and is given its members' box constants and control steps.  horizon: the call is a closed loop over
+        a horizon (dict(source, bytes): the horizon unit and the bytes a member takes beside the handle's), so every
+        handle also loads the family's horizon unit (J0 is None then).  Returns the chunks [(first, last), ...] it ran in"""
         nat.require_gpu()
         module = nat.compile_model(tabs['source'])
         look_module = nat.compile_model(look['source']) if look is not None else None
         policy_module = nat.compile_model(codegen.family_policy_unit(tabs['model'], self.dtype)) if evaluation else None
         mc_module = nat.compile_model(codegen.family_mc_unit(tabs['model'], self.dtype)) if mc_bytes is not None else None
-        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else int(mc_bytes or 0) + (look['bytes'] if look else 0))
+        horizon_module = nat.compile_model(horizon['source']) if horizon is not None else None
+        chunks = self._chunks(tabs, self._policy_bytes() if evaluation else
+                              int(mc_bytes or 0) + (look['bytes'] if look else 0) + (horizon['bytes'] if horizon else 0))
         digest = hashlib.sha256()
         for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
             if tabs[k] is not None:
@@ -420,6 +467,9 @@ class SolverFamily(object):
                 if mc_module is not None and getattr(prob, 'mc_module', None) != mc_module:
                     prob.load_mc_unit(mc_module)
                     prob.mc_module = mc_module
+                if horizon_module is not None and getattr(prob, 'horizon_module', None) != horizon_module:
+                    prob.load_horizon_unit(horizon_module)
+                    prob.horizon_module = horizon_module
                 if look_module is not None:
                     if getattr(prob, 'look_module', None) != look_module:
                         prob.load_lookahead_unit(look_module)
@@ -435,6 +485,7 @@ class SolverFamily(object):
         self.backend_info = dict(kernel='family', members=self.P, lanes=tabs['lanes'],
                                  lifted_constants=int(tabs['prm'].shape[1]), chunks=len(chunks), module=module,
                                  per_node=tabs['per_node'], time_specialized=tabs['time_specialized'])
+        return chunks
 
     def _start(self, J_next, rel_dp, name='J_next'):
         """the start of every member, [P] + dims in the family's reals, from an array of shape dims or (P,) + dims"""
@@ -777,7 +828,8 @@ class SolverFamily(object):
         law   : None (each member's own law), one (grid, proba) for all members, or a sequence of P of them; all
                 with the same number of points
         n_burn, occupancy, traj_offset, t0: as in the solo call.
-        Not built: time-indexed policies, models that look data up as data[k], deterministic members."""
+        Not built here: time-indexed policies and models that look data up as data[k] (`monte_carlo_horizon` runs
+        both); deterministic members (`simulate`)."""
         d = len(self.dims)
         # ---- everything that is refused, before a device is touched
         laws = self._mc_laws(law)
@@ -785,7 +837,7 @@ class SolverFamily(object):
         one = self.dims + (self.nu,)
         if pol.ndim > len(one) + 1 and pol.shape[-len(one):] == one:
             raise NotImplementedError('pol of shape {}: a time-indexed policy (a leading axis beside the members\') is not '
-                                      'built for families'.format(pol.shape))
+                                      'what monte_carlo takes: use monte_carlo_horizon'.format(pol.shape))
         pol = self._policy(pol)
         x0 = np.asarray(x0, dtype=float)
         shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
@@ -814,8 +866,8 @@ class SolverFamily(object):
             raise ValueError('steps_per_launch must be at least 1')
         tabs = self._tables(None if self.stationnary else 0)
         if tabs['time_specialized']:
-            raise NotImplementedError('the members\' model looks data up at a concrete time index (data[k]): a table of '
-                                      'constants per step is not built for families')
+            raise NotImplementedError('the members\' model looks data up at a concrete time index (data[k]): monte_carlo '
+                                      'has no table of constants per step: use monte_carlo_horizon')
         # ---- member-major device arrays
         dt = self.dtype
         S, n_law = int(np.prod(self.dims)), len(laws[0][1])
@@ -838,6 +890,220 @@ class SolverFamily(object):
         self._run(tabs, None, work, mc_bytes=self._mc_member_bytes(B, n_law, occupancy))
         self.backend_info['monte_carlo'] = dict(members=self.P, n_traj=B, chunks=self.backend_info['chunks'],
                                                 launches=self.backend_info['chunks'] * (-(-n_steps // min(spl, 1 << 30))))
+        return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
+
+    # ------------------------------------------------------------------ closed loops over a horizon
+    # the policy of a time-indexed run goes up in cuts of whole steps of at most this many bytes (of all members of a
+    # chunk together), as the solo calls cut theirs; the state stays on the device, so no cut changes a bit
+    horizon_chunk_bytes = DPSolver.horizon_chunk_bytes
+
+    def _horizon_policy(self, pol, n_steps, t0):
+        """(the policy as [P][T_c][nu][S] in the family's reals, control axis first -- T_c = n_steps slices of a
+        time-indexed policy, the steps t0 .. t0 + n_steps - 1, or the one slice of a stationary policy --, whether it is
+        time-indexed): from dims + (nu,), (P,) + dims + (nu,) or (P, T_pol) + dims + (nu,)"""
+        pol = np.asarray(pol)
+        one = self.dims + (self.nu,)
+        S = int(np.prod(self.dims))
+        if pol.shape in (one, (self.P,) + one):
+            each = np.broadcast_to(pol, (self.P,) + one)
+            return np.ascontiguousarray(np.moveaxis(each, -1, 1), dtype=self.dtype).reshape(self.P, 1, self.nu, S), False
+        if pol.ndim != len(one) + 2 or pol.shape[0] != self.P or pol.shape[2:] != one:
+            raise ValueError('pol must have shape {} (one stationary policy), {} (one per member) or ({}, T_pol) + {} (a '
+                             'time-indexed one per member), not {}'.format(one, (self.P,) + one, self.P, one, pol.shape))
+        if int(t0) != t0:
+            raise ValueError('t0 = {} must be an integer to index a time-indexed policy'.format(t0))
+        if t0 < 0 or t0 + n_steps > pol.shape[1]:
+            raise ValueError('t0 = {} and n_steps = {} need the policy steps {} .. {}: the policy has T_pol = {}'.format(
+                t0, n_steps, t0, t0 + n_steps - 1, pol.shape[1]))
+        part = np.moveaxis(pol[:, int(t0):int(t0) + n_steps], -1, 2)
+        return np.ascontiguousarray(part, dtype=self.dtype).reshape(self.P, n_steps, self.nu, S), True
+
+    def _horizon_tables(self, n_steps, t0):
+        """(tabs, table, timed) of a run of the steps t0 .. t0 + n_steps - 1, no GPU needed: the tables of the family at
+        the first step, and the lifted constants of every member and step in the family's reals, rounded once --
+        [P][n_steps][n_params] for members whose model is traced per step (`data[k]`; timed), row (p, k) what row k
+        of `solvers[p]._horizon_table` holds, or [P][1][n_params] for members whose model is symbolic in time: one row
+        per member, read at every step.  A family has no host path: a step that does not trace is refused, and so are
+        steps or members whose traces differ in structure."""
+        symbolic = self.stationnary or all(not isinstance(_trace_member(s, None), TraceError) for s in self.solvers)
+        if symbolic:
+            tabs = self._tables(None if self.stationnary else t0)
+            return tabs, np.ascontiguousarray(tabs['prm'].reshape(self.P, 1, -1)), False
+        if int(t0) != t0:
+            raise ValueError('t0 = {} must be an integer: the members\' model looks data up at a concrete time index '
+                             '(data[k])'.format(t0))
+        t0 = int(t0)
+        rows, first = [], None
+        for p, s in enumerate(self.solvers):
+            mine = []
+            for t in range(t0, t0 + n_steps):
+                model = _trace_member(s, t)
+                if isinstance(model, TraceError):
+                    raise NotImplementedError('member {} at step {}: dyn / cost do not trace ({}): a family runs traced '
+                                              'models only, there is no host path'.format(p, t, model))
+                if first is None:
+                    first = model
+                elif model.structure_key() != first.structure_key():
+                    raise ValueError(_structure_message(p, model, first, ' at step {}'.format(t)))
+                mine.append(model.param_values())
+            rows.append(mine)
+        tabs = self._tables(t0)
+        table = np.ascontiguousarray(np.asarray(rows, dtype=float).reshape(self.P, n_steps, -1), dtype=self.dtype)
+        return tabs, table, True
+
+    def _horizon_bytes(self, pol_d, table):
+        """bytes of device arrays one member takes in a run over a horizon beside its states: its policy steps and its
+        rows of the table of constants"""
+        return (pol_d.shape[1] * pol_d.shape[2] * pol_d.shape[3] + table.shape[1] * table.shape[2]) * self.dtype.itemsize
+
+    def _horizon_info(self, chunks, B, n_steps, pol_d, timed, prm_timed, spl):
+        """backend_info['horizon'] of the call that just ran in the member chunks `chunks`: the cuts, restated from the
+        library's rule"""
+        slice_bytes = pol_d.shape[2] * pol_d.shape[3] * self.dtype.itemsize
+        step_chunks = launches = 0
+        for a, b in chunks:
+            per = min(n_steps, max(1, int(self.horizon_chunk_bytes) // ((b - a) * slice_bytes))) if timed else n_steps
+            for c in range(0, n_steps, per):
+                step_chunks += 1
+                launches += 1 if spl is None else -(-min(per, n_steps - c) // spl)
+        self.backend_info['horizon'] = dict(members=self.P, n_traj=B, n_steps=n_steps, timed=bool(timed),
+                                            time_specialized=bool(prm_timed), chunks=len(chunks), step_chunks=step_chunks,
+                                            launches=launches)
+
+    def simulate(self, pol, x0, w=None, n_steps=None, t0=0):
+        """`DPSolver.simulate` of every member in one device call per cut of the steps (kernel sdp_family_simulate,
+        csrc/sdp_family_horizon_kernel.h): (x (P, T+1, B, d), u (P, T, B, nu), g (P, T, B)), member p equal, bit for
+        bit, to what `solvers[p].simulate(pol[p], x0[p], w[p], n_steps, t0)` returns on its device path.
+
+        pol : dims + (nu,) (one stationary policy for all members), (P,) + dims + (nu,) (one per member), or
+              (P, T_pol) + dims + (nu,), what `bellman_recursion` returns: step k then runs at time index t0 + k with
+              the controls of pol[p, t0 + k].  A time-indexed policy always carries both leading axes.
+        x0  : (d,) -- the results then have no B axis --, (B, d) shared by all members, or (P, B, d)
+        w   : (T,), (T, B) shared by all members, or (P, T, B); None for deterministic members (then give n_steps)
+        Models that are symbolic in time and models that look data up as data[k] (traced per member and step) both
+        run; there is no host path."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        x0 = np.asarray(x0, dtype=float)
+        single = x0.ndim == 1
+        if single:
+            x0 = x0[None]
+        if x0.ndim not in (2, 3) or x0.shape[-1] != d or (x0.ndim == 3 and x0.shape[0] != self.P):
+            raise ValueError('x0 must have shape ({0},), (B, {0}) or ({1}, B, {0}), not {2}'.format(
+                d, self.P, x0.shape[1:] if single else x0.shape))
+        B = x0.shape[-2]
+        if B < 1:
+            raise ValueError('x0 holds no start state')
+        if x0.ndim == 2:
+            x0 = np.broadcast_to(x0, (self.P, B, d))
+        if self.W:
+            if w is None:
+                raise ValueError('stochastic members need the perturbation sequence(s) w')
+            w = np.asarray(w, dtype=float)
+            if w.ndim == 1:
+                w = w.reshape(-1, 1)
+            if w.ndim not in (2, 3) or w.shape[-1] != B or (w.ndim == 3 and w.shape[0] != self.P):
+                raise ValueError('w must have shape (T,), (T, {0}) or ({1}, T, {0}), not {2}'.format(B, self.P, w.shape))
+            T = w.shape[-2] if n_steps is None else int(n_steps)
+            if w.shape[-2] < T:
+                raise ValueError('w holds {} steps, n_steps = {}'.format(w.shape[-2], T))
+            if w.ndim == 2:
+                w = np.broadcast_to(w, (self.P,) + w.shape)
+        else:
+            if n_steps is None:
+                raise ValueError('give n_steps for deterministic members')
+            T, w = int(n_steps), None
+        if T < 1:
+            raise ValueError('need n_steps >= 1')
+        pol_d, timed = self._horizon_policy(pol, T, t0)
+        tabs, table, prm_timed = self._horizon_tables(T, t0)
+        # ---- member-major device arrays
+        dt = self.dtype
+        rs = dt.itemsize
+        x0_d = np.ascontiguousarray(np.moveaxis(x0, -1, 1), dtype=dt)                                     # [P][d][B]
+        w_d = np.ascontiguousarray(w[:, :T], dtype=dt) if w is not None else None                        # [P][T][B]
+        x = np.empty((self.P, T + 1, B, d), dtype=dt)
+        u = np.empty((self.P, T, B, self.nu), dtype=dt)
+        g = np.empty((self.P, T, B), dtype=dt)
+
+        def work(prob, a, b):
+            xs, us, g[a:b] = prob.simulate_h(pol_d[a:b], timed, table[a:b], prm_timed, self.horizon_chunk_bytes, x0_d[a:b],
+                                             None if w_d is None else w_d[a:b], T, t0)
+            x[a:b], u[a:b] = np.moveaxis(xs, 2, 3), np.moveaxis(us, 2, 3)
+        extra = self._horizon_bytes(pol_d, table) + (d * B + (1 if self.W else 0) * T * B + (T + 1) * d * B
+                                                     + T * self.nu * B + T * B) * rs
+        self._horizon_info(self._run_horizon(tabs, work, extra), B, T, pol_d, timed, prm_timed, None)
+        if single:
+            return x[:, :, 0], u[:, :, 0], g[:, :, 0]
+        return x, u, g
+
+    def _run_horizon(self, tabs, work, extra):
+        """`_run` of a closed loop over a horizon whose arrays take `extra` bytes a member beside the handle's: the
+        member chunks it ran in"""
+        return self._run(tabs, None, work, horizon=dict(source=codegen.family_horizon_unit(tabs['model'], self.dtype), bytes=int(extra)))
+
+    def monte_carlo_horizon(self, pol, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False, traj_offset=0,
+                            t0=0):
+        """`DPSolver.monte_carlo` of every member under a policy of any of the three shapes `simulate` takes, in one
+        device call per cut of the steps (kernel sdp_family_montecarlo_h, csrc/sdp_family_horizon_kernel.h): a
+        `montecarlo.FamilyMonteCarloResult` with path 'device', member p of every field equal, bit for bit, to what
+        `solvers[p].monte_carlo(pol[p], ...)` returns on its device path.  The other arguments are `monte_carlo`'s.
+        Models that are symbolic in time and models that look data up as data[k] both run; a stationary policy on a
+        symbolic model gives the bits of `monte_carlo`.  Launches are cut at the policy's uploads
+        (horizon_chunk_bytes) and at steps_per_launch.  Not built: deterministic members (use `simulate`)."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        laws = self._mc_laws(law)
+        x0 = np.asarray(x0, dtype=float)
+        shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
+        if x0.ndim == 1:
+            if x0.shape != (d,):
+                raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
+            if n_traj is None:
+                raise ValueError('give n_traj with a single start state')
+            if int(n_traj) < 1:
+                raise ValueError('n_traj must be at least 1')
+            x0 = np.broadcast_to(x0, (int(n_traj), d))
+        elif x0.ndim not in (2, 3) or x0.shape[-1] != d or (x0.ndim == 3 and x0.shape[0] != self.P):
+            raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
+        elif n_traj is not None and int(n_traj) != x0.shape[-2]:
+            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[-2]))
+        B = x0.shape[-2]
+        if x0.ndim == 2:
+            x0 = np.broadcast_to(x0, (self.P, B, d))
+        n_steps, n_burn = int(n_steps), int(n_burn)
+        if n_steps < 1 or not 0 <= n_burn < n_steps:
+            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
+        seeds = self._mc_seeds(seed)
+        DPSolver._mc_ids(B, traj_offset)
+        spl = int(self.steps_per_launch)
+        if spl < 1:
+            raise ValueError('steps_per_launch must be at least 1')
+        pol_d, timed = self._horizon_policy(pol, n_steps, t0)
+        tabs, table, prm_timed = self._horizon_tables(n_steps, t0)
+        # ---- member-major device arrays
+        dt = self.dtype
+        n_law = len(laws[0][1])
+        x0_d = np.ascontiguousarray(np.moveaxis(x0, -1, 1), dtype=dt)                                     # [P][d][B]
+        cum = np.ascontiguousarray([mc.cumulative(proba) for _, proba in laws])                           # [P][n_law]
+        law_d = np.ascontiguousarray([grid for grid, _ in laws], dtype=dt)
+        seeds_d = np.array(seeds, dtype=np.uint64)
+        cost_sum = np.empty((self.P, B), dtype=dt)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, B, d), dtype=dt)
+        occ = np.empty((self.P,) + self.dims, dtype=np.int64) if occupancy else None
+
+        def work(prob, a, b):
+            c, n, xf, o = prob.montecarlo_h(pol_d[a:b], timed, table[a:b], prm_timed, self.horizon_chunk_bytes, x0_d[a:b],
+                                            n_steps, n_burn, seeds_d[a:b], traj_offset, cum[a:b], law_d[a:b], t0, spl,
+                                            occupancy)
+            cost_sum[a:b], n_out[a:b], x_final[a:b] = c, n, np.moveaxis(xf, 1, 2)
+            if occupancy:
+                occ[a:b] = o.astype(np.int64).reshape((b - a,) + self.dims)
+        # (_mc_member_bytes counts one policy slice: the others and the table are what the horizon adds)
+        S = int(np.prod(self.dims))
+        extra = self._mc_member_bytes(B, n_law, occupancy) + self._horizon_bytes(pol_d, table) - self.nu * S * dt.itemsize
+        self._horizon_info(self._run_horizon(tabs, work, extra), B, n_steps, pol_d, timed, prm_timed, min(spl, 1 << 30))
         return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
 
     # ------------------------------------------------------------------ lookahead at arbitrary states

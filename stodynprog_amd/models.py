@@ -443,16 +443,16 @@ def pv_profile(T, dt=0.5):
     return np.where(arc > 0, arc * scale, 0.0)
 
 
-def pv_storage(api=None, T=48, N_E=50, u_step=0.001, dt=0.5, loss=0.05):
+def pv_storage(api=None, T=48, N_E=50, u_step=0.001, dt=0.5, loss=0.05, E_rated=2.0, P_rated=1.0):
     """Storage smoothing the output of a PV plant with perfect knowledge of the
     production -- the shape of the reference's finite-horizon examples
     (examples/01 Deterministic storage control/pv_storage_control.py:48-98 and
     det_storage_control.py:58-98): one state (stored energy), one control, no
     perturbation, `stationnary=False`, and a cost that LOOKS UP the production
     of the time step in a data array (`P_prod_data[k]`).  The admissible box
-    uses np.max / np.min on scalar tuples like the reference's."""
+    uses np.max / np.min on scalar tuples like the reference's.  E_rated and P_rated size the storage (a sizing study
+    runs a range of them as one SolverFamily: examples/sizing_pv_storage.py)."""
     SysDescription, DPSolver = _classes(api)
-    E_rated, P_rated = 2.0, 1.0
     P_prod_data = pv_profile(T, dt)
     sto = SysDescription((1, 1, 0), name='Deterministic Storage for PV', stationnary=False)
 
