@@ -1522,7 +1522,8 @@ class DPSolver(object):
                 t_k = None
             for flat, x_k in enumerate(itertools.product(*self.state_grid)):
                 u_grids, dims = self.control_grids(x_k, t_k)
-                lattice = dims + ((W,) if W else ())
+                # (the control meshes keep the axis of the perturbation, of length 1 for a deterministic system)
+                lattice = dims + (W or 1,)
                 for i in range(nu):
                     u_grids[i] = u_grids[i].reshape((1,) * i + (-1,) + (1,) * (nu - i))
                 args = tuple(x_k) + tuple(u_grids) + w_args
@@ -1593,7 +1594,7 @@ class DPSolver(object):
         u_grids, dims, args = self._node_lattice(x_k, t_k)
         nu = len(u_grids)
         _, proba, W = self._flat_law()
-        lattice = dims + ((W,) if W else ())
+        lattice = dims + (W or 1,)          # (as in _backup_tabulated)
         x_next = self.sys.dyn(*args, **self.sys.params)
         g_grid = self.sys.cost(*args, **self.sys.params)
         xn = np.ascontiguousarray(np.vstack(
@@ -1740,7 +1741,7 @@ class DPSolver(object):
             ug = [la.control_points(lo[c, b], hi[c, b], n[c, b]) for c in range(nu)]
             mesh = [g.reshape((1,) * c + (-1,) + (1,) * (nu - c)) for c, g in enumerate(ug)]
             args = lead + tuple(xd[b]) + tuple(mesh) + tuple(w_args)
-            lattice = dims + ((W,) if W else ())
+            lattice = dims + (W or 1,)          # (as in _backup_tabulated)
             x_next = self.sys.dyn(*args, **self.sys.params)
             g_grid = self.sys.cost(*args, **self.sys.params)
             cells_x.append(np.vstack([np.broadcast_to(np.asarray(v, dtype=float), lattice).ravel() for v in x_next]))
