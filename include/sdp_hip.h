@@ -531,6 +531,34 @@ int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_t B, int64_
                           void *host_x_final, uint64_t *host_occupancy);
 
 /*
+ * Transition operators of a family's policies (csrc/sdp_family_trans_kernel.h).  The family's TRANSITION unit
+ * (codegen.family_trans_unit: kernel sdp_family_transitions) is loaded beside the sweep unit; its sdp_meta is checked
+ * (SDP_META_F_FAMILY_TRANS, the workgroup size and the tile of 256 >> d nodes).
+ */
+int sdp_family_load_trans_unit(sdp_family *f, const char *module_path);
+/*
+ * sdp_transop_create of every member of the handle in one launch and one sort: member p under its policy
+ * host_pol[p] ([P][S][nu] reals, C order) at time index t_k, with its law (deterministic members: one point of weight
+ * 1) and the constants of sdp_family_set_params.  The P operators are ONE block-diagonal sdp_transop on P S rows,
+ * member p's node s row p S + s: sdp_transop_push, _get, _get_mean_cost, _get_csr, _build_ms, _last_kernel_ms,
+ * _set_long_rows and _destroy serve it as they serve a solo operator, on vectors of [P][S] reals, and member p of every
+ * result has the bits of the solo operator of problem p (the sort is stable and members share no row).  The operator
+ * does not refer to the family afterwards.  SDP_EINVAL for a NULL pointer, no unit loaded, P S >= 2^31 rows or
+ * P S W 2^d >= 2^32 entries.
+ */
+int sdp_family_transop_create(sdp_family *f, const void *host_pol, double t_k, sdp_transop **out);
+/*
+ * sdp_transop_push_until with a stop per member, on the operators of a family: every member starts from its slice of
+ * the resident vector and stops at its own first checked push with delta[p] = max |mu_{k+1} - mu_k| over its slice
+ * <= tol, or at push n_max.  A check is one reduction launch over the members still running and 24 bytes a member
+ * back; a member that has stopped is computed no more (both push paths skip its rows) and its slice of the resident
+ * vector stays the iterate it stopped on; the loop ends when no member is left.  n_done [P]: pushes each member ran;
+ * delta [P]: its last checked value (NaN never converges).  SDP_EINVAL for a solo operator.
+ */
+int sdp_transop_push_until_members(sdp_transop *op, int32_t n_max, int32_t check_every, double tol,
+                                   int32_t *n_done, double *delta);
+
+/*
  * Closed loops of a family over a horizon (csrc/sdp_family_horizon_kernel.h).  The family's HORIZON unit
  * (codegen.family_horizon_unit: kernels sdp_family_simulate and, for a stochastic family, sdp_family_montecarlo_h) is
  * loaded beside the sweep unit; its sdp_meta is checked (SDP_META_F_FAMILY_HORIZON, the two workgroup sizes).

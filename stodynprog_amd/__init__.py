@@ -10,7 +10,8 @@ HIP kernels on gfx950 through the C ABI of include/sdp_hip.h.
 from .sysdesc import SysDescription
 from .solver import DPSolver, TransitionOperator
 from .interp import MlinInterpolator
-from .family import SolverFamily
+from .family import SolverFamily, FamilyTransitionOperator
 
 __version__ = '0.1.0'
-__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator', 'SolverFamily']
+__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator', 'SolverFamily',
+           'FamilyTransitionOperator']

@@ -935,6 +935,34 @@ def family_horizon_unit(model, dtype):
     return '\n'.join(head)
 
 
+# kernel sdp_family_transitions (csrc/sdp_family_trans_kernel.h: SDP_FTRANS_THREADS): its workgroup
+FAMILY_TRANS_THREADS = 256
+
+
+def family_trans_tile(d):
+    """nodes of one member a workgroup of kernel sdp_family_transitions holds (SDP_FTRANS_TILE): 2^d lanes a node"""
+    return FAMILY_TRANS_THREADS >> int(d)
+
+
+def family_trans_unit(model, dtype):
+    """The generated source of a family TRANSITION unit (csrc/sdp_family_trans_kernel.h, kernel
+    `sdp_family_transitions`): the direct prologue of a model with lifted constants, marked SDP_FAMILY and
+    SDP_FAMILY_TRANS, and the transition header in the place of sdp_sweep_kernel.h.  The entries of a policy's
+    operator have no control lattice, so there is one unit per model structure and real type (the lane count the
+    prologue prints is 1 and nothing reads it)."""
+    if model.param_index is None:
+        raise ValueError('a family unit takes a model with lifted constants (TracedModel.lift_constants)')
+    if model.n_perturb >= 2:
+        raise NotImplementedError('a family unit takes one perturbation variable at most')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, 1, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
+    head.insert(at + 1, '#define SDP_FAMILY_TRANS 1    // .. and sdp_family_transitions in the place of sdp_family_sweep')
+    head += ['#include "sdp_family_trans_kernel.h"    // brings in sdp_family_kernel.h', '']
+    return '\n'.join(head)
+
+
 def family_lookahead_unit(model, box, dtype, lanes):
     """The generated source of a family LOOKAHEAD unit (csrc/sdp_family_lookahead_kernel.h, kernels
     `sdp_family_lookahead` and `sdp_family_montecarlo_lookahead`): the direct prologue of a model with lifted
@@ -1692,6 +1720,9 @@ def source_key(source):
     if '#define SDP_FAMILY_HORIZON ' in source:
         # (it includes sdp_family_kernel.h, above, and sdp_mc_kernel.h, one of _HEADERS)
         with open(os.path.join(CSRC, 'sdp_family_horizon_kernel.h'), 'rb') as f:
+            h.update(f.read())
+    if '#define SDP_FAMILY_TRANS ' in source:
+        with open(os.path.join(CSRC, 'sdp_family_trans_kernel.h'), 'rb') as f:
             h.update(f.read())
     if '#define SDP_FAMILY_LOOKAHEAD ' in source:
         # (it includes sdp_family_kernel.h, above, sdp_mc_kernel.h, one of _HEADERS, and the lattice rule)

@@ -116,10 +116,11 @@ SDP_DEV sdp_real sdp_family_expected_cost(const SdpFamilyArgs &a, const SdpMembe
 #endif
 }
 
-#if !defined(SDP_FAMILY_POLICY) && !defined(SDP_FAMILY_MC) && !defined(SDP_FAMILY_LOOKAHEAD) && !defined(SDP_FAMILY_HORIZON)
+#if !defined(SDP_FAMILY_POLICY) && !defined(SDP_FAMILY_MC) && !defined(SDP_FAMILY_LOOKAHEAD) && !defined(SDP_FAMILY_HORIZON) \
+    && !defined(SDP_FAMILY_TRANS)
 // (an evaluation unit, sdp_family_policy_kernel.h, takes SdpMember and the helpers above and brings its own kernels; so
-// do a Monte Carlo unit, sdp_family_mc_kernel.h, a lookahead unit, sdp_family_lookahead_kernel.h, and a horizon unit,
-// sdp_family_horizon_kernel.h)
+// do a Monte Carlo unit, sdp_family_mc_kernel.h, a lookahead unit, sdp_family_lookahead_kernel.h, a horizon unit,
+// sdp_family_horizon_kernel.h, and a transition unit, sdp_family_trans_kernel.h)
 extern "C" __global__ void __launch_bounds__(256) sdp_family_sweep(SdpFamilyArgs a)
 {
     constexpr int L = SDP_LANES;

@@ -2841,6 +2841,13 @@ struct sdp_transop {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     double last_kernel_ms = 0, entries_ms = 0, sort_ms = 0;
     int cus = 256;
+    // the operators of a family (sdp_family_transop_create): P block-diagonal members of Sm rows each, S = P Sm.
+    // flags[p] != 0: member p is still running and a push computes its rows (both push paths test it); running: the
+    // list of those members on the device, for the reduction of a check; mstats: its three key words per listed member
+    int P = 0;                             // 0: a solo operator, no flags
+    int64_t Sm = 0;
+    DevBuf flags, running, mstats;
+    bool all_running = true;               // every flag is set
     ~sdp_transop()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -2890,13 +2897,17 @@ __global__ void __launch_bounds__(256) k_trans_count(const int32_t *__restrict__
 // out[t] = sum over the row of data[k] * mu[indices[k]], k ascending: acc = 0; acc = acc + data[k] * mu[..]
 // (row pointers and sources are trusted: the build made them from node ids, sdp_transop_from_coo checked its own).
 // Rows of long_min entries or more are left to k_push_group (long_min = 0: none is).
-template <typename real>
+// MEMBERS (the operators of a family, block-diagonal with Sm rows a member): the rows of a member whose flag is 0 are not
+// computed and out[t] keeps what it holds.
+template <typename real, bool MEMBERS>
 __global__ void __launch_bounds__(256) k_push(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                               const real *__restrict__ data, const real *__restrict__ mu,
-                                              real *__restrict__ out, int64_t S, int32_t long_min)
+                                              real *__restrict__ out, int64_t S, int32_t long_min,
+                                              const int32_t *__restrict__ flags, int32_t Sm)
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < S; t += stride) {
+        if (MEMBERS && !flags[(int32_t)t / Sm]) continue;
         const int64_t b = indptr[t], e = indptr[t + 1];
         if (long_min > 0 && e - b >= long_min) continue;
         real acc = real(0);
@@ -2912,10 +2923,12 @@ __global__ void __launch_bounds__(256) k_push(const int64_t *__restrict__ indptr
 // chain serves the 64 / G rows of the wave.  acc is the same in every lane of a group; its lane 0 stores it.
 // G = 16 for rows below SDP_PUSH_WIDE entries, G = 64 from there on (a trip to memory per 64 entries, not per 16).
 #define SDP_PUSH_WIDE 256
-template <typename real, int G>
+// MEMBERS: as in k_push -- a listed row of a member whose flag is 0 is a dead group (no loads, no store).
+template <typename real, int G, bool MEMBERS>
 __global__ void __launch_bounds__(256) k_push_group(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                     const real *__restrict__ data, const real *__restrict__ mu,
-                                                    real *__restrict__ out, const int32_t *__restrict__ rows, int64_t n_rows)
+                                                    real *__restrict__ out, const int32_t *__restrict__ rows, int64_t n_rows,
+                                                    const int32_t *__restrict__ flags, int32_t Sm)
 {
     constexpr int PER = 64 / G;                                // rows of a wave
     const int lane = threadIdx.x & 63, sub = lane & (G - 1), grp = lane / G;
@@ -2923,8 +2936,9 @@ __global__ void __launch_bounds__(256) k_push_group(const int64_t *__restrict__ 
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t w = wave; w * PER < n_rows; w += waves) {     // the same trips in every lane of a wave
         const int64_t r = w * PER + grp;
-        const bool live = r < n_rows;
+        bool live = r < n_rows;
         const int32_t t = live ? rows[r] : 0;
+        if (MEMBERS && live) live = flags[t / Sm] != 0;
         int64_t b = 0, e = 0;
         if (live) { b = indptr[t]; e = indptr[t + 1]; }
         long long longest = e - b;                             // of the wave's rows: every lane runs that many chunks
@@ -3133,9 +3147,11 @@ extern "C" int sdp_transop_destroy(sdp_transop *op)
     return SDP_OK;
 }
 
-template <typename real>
+template <typename real, bool MEMBERS>
 static int transop_launch_push_as(sdp_transop *op)
 {
+    const int32_t *flags = MEMBERS ? (const int32_t *)op->flags.p : nullptr;
+    const int32_t Sm = MEMBERS ? (int32_t)op->Sm : 1;
     const real *in = (const real *)op->mu[op->cur].p;
     real *outp = (real *)op->mu[1 - op->cur].p;
     const int64_t *indptr = (const int64_t *)op->indptr.p;
@@ -3145,8 +3161,8 @@ static int transop_launch_push_as(sdp_transop *op)
     if (op->n_long < op->S) {
         int64_t blocks = (op->S + 255) / 256;
         if (blocks > (int64_t)op->cus * 8) blocks = (int64_t)op->cus * 8;
-        hipLaunchKernelGGL(k_push<real>, dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp, op->S,
-                           op->long_min);
+        hipLaunchKernelGGL((k_push<real, MEMBERS>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp,
+                           op->S, op->long_min, flags, Sm);
         HIP_TRY(hipGetLastError());
     }
     // the long rows: four to a wave (sixteen to a workgroup), the widest one to a wave
@@ -3155,15 +3171,15 @@ static int transop_launch_push_as(sdp_transop *op)
     if (n_mid > 0) {
         int64_t blocks = (n_mid + 15) / 16;
         if (blocks > (int64_t)op->cus * 64) blocks = (int64_t)op->cus * 64;
-        hipLaunchKernelGGL((k_push_group<real, 16>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp,
-                           rows, n_mid);
+        hipLaunchKernelGGL((k_push_group<real, 16, MEMBERS>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data,
+                           in, outp, rows, n_mid, flags, Sm);
         HIP_TRY(hipGetLastError());
     }
     if (op->n_wide > 0) {
         int64_t blocks = (op->n_wide + 3) / 4;
         if (blocks > (int64_t)op->cus * 64) blocks = (int64_t)op->cus * 64;
-        hipLaunchKernelGGL((k_push_group<real, 64>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data, in, outp,
-                           rows + n_mid, op->n_wide);
+        hipLaunchKernelGGL((k_push_group<real, 64, MEMBERS>), dim3((unsigned)blocks), dim3(256), 0, op->stream, indptr, indices, data,
+                           in, outp, rows + n_mid, op->n_wide, flags, Sm);
         HIP_TRY(hipGetLastError());
     }
     op->cur = 1 - op->cur;
@@ -3172,7 +3188,21 @@ static int transop_launch_push_as(sdp_transop *op)
 
 static int transop_launch_push(sdp_transop *op)
 {
-    return op->dtype == SDP_F32 ? transop_launch_push_as<float>(op) : transop_launch_push_as<double>(op);
+    // (the operators of a family test the members' flags only while some member has stopped)
+    if (op->P > 0 && !op->all_running)
+        return op->dtype == SDP_F32 ? transop_launch_push_as<float, true>(op) : transop_launch_push_as<double, true>(op);
+    return op->dtype == SDP_F32 ? transop_launch_push_as<float, false>(op) : transop_launch_push_as<double, false>(op);
+}
+
+// every member of a family's operators runs again (a solo operator has no flags)
+static int transop_all_running(sdp_transop *op)
+{
+    if (op->P < 1 || op->all_running) return SDP_OK;
+    std::vector<int32_t> ones((size_t)op->P, 1);
+    HIP_TRY(hipMemcpyAsync(op->flags.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    op->all_running = true;
+    return SDP_OK;
 }
 
 static int transop_set(sdp_transop *op, const void *host_mu)
@@ -3196,6 +3226,7 @@ extern "C" int sdp_transop_push(sdp_transop *op, const void *host_mu, int32_t n_
     if (n_steps < 0) return fail(SDP_EINVAL, "n_steps must not be negative");
     int rc;
     if ((rc = transop_set(op, host_mu))) return rc;
+    if ((rc = transop_all_running(op))) return rc;
     HIP_TRY(hipEventRecord(op->ev0, op->stream));
     for (int32_t k = 0; k < n_steps; ++k)
         if ((rc = transop_launch_push(op))) return rc;
@@ -3247,6 +3278,7 @@ extern "C" int sdp_transop_push_until(sdp_transop *op, int32_t n_max, int32_t ch
     if (!(tol >= 0)) return fail(SDP_EINVAL, "tol must be a number >= 0");
     int rc;
     if ((rc = transop_set(op, nullptr))) return rc;
+    if ((rc = transop_all_running(op))) return rc;
     int32_t done = 0;
     double d = NAN;
     HIP_TRY(hipEventRecord(op->ev0, op->stream));
@@ -3786,6 +3818,11 @@ struct sdp_family {
     int look_lanes = 0, n_box = 0;
     DevBuf bprm, look_steps;
     bool has_look_box = false;
+    // transition operators (sdp_family_load_trans_unit): the unit, its kernel and the nodes of a workgroup's tile; an
+    // operator owns its arrays (sdp_transop) and outlives the family
+    hipModule_t trmod = nullptr;
+    hipFunction_t f_transitions = nullptr;
+    int trans_tile = 0;
     int cur = 0;                           // buf[cur] is read (V), buf[cur ^ 1] written (J)
     std::vector<int32_t> active;           // the members the next launch runs
     std::vector<int> where;                // [P] the buffer that holds the member's latest values
@@ -3805,6 +3842,7 @@ struct sdp_family {
         if (mcmod) (void)hipModuleUnload(mcmod);
         if (hzmod) (void)hipModuleUnload(hzmod);
         if (lkmod) (void)hipModuleUnload(lkmod);
+        if (trmod) (void)hipModuleUnload(trmod);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -4584,6 +4622,195 @@ extern "C" int sdp_family_montecarlo(sdp_family *f, const void *host_pol, int64_
     HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));
     if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, P * (size_t)f->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Transition operators of a family's policies (csrc/sdp_family_trans_kernel.h): sdp_transop_create of every member in
+// one launch and one sort.  The members' operators are ONE block-diagonal sdp_transop on P S rows -- member p's node s
+// is row p S + s -- so the CSR build, both push paths and every accessor of the solo operator serve it as they are; the
+// stable sort and the members' disjoint rows keep every member's rows in the solo entry order.  The operator owns its
+// arrays and outlives the family.  sdp_transop_push_until_members is the power iteration with a stop per member.
+// ---------------------------------------------------------------------------
+extern "C" int sdp_family_load_trans_unit(sdp_family *f, const char *module_path)
+{
+    if (!f || !module_path) return fail(SDP_EINVAL, "NULL argument");
+    if (f->trmod) { (void)hipModuleUnload(f->trmod); f->trmod = nullptr; f->f_transitions = nullptr; }
+    const size_t rs = real_size(f->dtype);
+    hipError_t e = hipModuleLoad(&f->trmod, module_path);
+    if (e != hipSuccess) { f->trmod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", module_path, hipGetErrorString(e)); }
+    int32_t m[SDP_META_WORDS] = {0};
+    hipDeviceptr_t mptr = nullptr;
+    size_t mbytes = 0;
+    const char *why = nullptr;
+    if (hipModuleGetGlobal(&mptr, &mbytes, f->trmod, "sdp_meta") != hipSuccess || mbytes != sizeof(m)) {
+        (void)hipGetLastError();
+        why = "it does not declare `sdp_meta`";
+    } else {
+        HIP_TRY(hipMemcpyDtoH(m, mptr, sizeof(m)));
+        if (m[SDP_META_MAGIC_AT] != SDP_META_MAGIC) why = "bad magic";
+        else if (!(m[SDP_META_FLAGS] & SDP_META_F_FAMILY_TRANS)) why = "not a family transition unit";
+        else if (m[SDP_META_THREADS] != 256) why = "built for another workgroup size";
+        else if (m[SDP_META_COL_ROWS] != (256 >> f->d)) why = "built for another tile";
+        else if (m[SDP_META_REAL_BYTES] != (int)rs) why = "built for other reals";
+        else if (m[SDP_META_D] != f->d) why = "built for another number of state variables";
+        else if (m[SDP_META_NU] != f->nu) why = "built for another number of controls";
+        else if ((m[SDP_META_HAS_W] != 0) != (f->W > 0)) why = "built for a model with / without a perturbation";
+    }
+    hipDeviceptr_t pptr = nullptr;
+    size_t pbytes = 0;
+    if (!why) {
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->trmod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs) why = "another number of lifted constants";
+    }
+    if (!why && hipModuleGetFunction(&f->f_transitions, f->trmod, "sdp_family_transitions") != hipSuccess) why = "no sdp_family_transitions kernel";
+    if (why) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(f->trmod);
+        f->trmod = nullptr; f->f_transitions = nullptr;
+        return fail(SDP_EMODULE, "code object %s was not built for this family's transition operators: %s", module_path, why);
+    }
+    f->trans_tile = m[SDP_META_COL_ROWS];
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_transop_create(sdp_family *f, const void *host_pol, double t_k, sdp_transop **out)
+{
+    if (!f || !host_pol || !out) return fail(SDP_EINVAL, "NULL argument");
+    if (!f->f_transitions) return fail(SDP_EINVAL, "no transition unit loaded (sdp_family_load_trans_unit)");
+    const size_t rs = real_size(f->dtype);
+    const int64_t P = f->P, S = f->S, W = f->W > 0 ? f->W : 1, V = (int64_t)1 << f->d;
+    const int64_t rows = P * S;
+    if (rows >= (int64_t)1 << 31)
+        return fail(SDP_EINVAL, "%lld members of %lld nodes: the rows of their operators are 32-bit ids (at most 2^31 - 1 rows)", (long long)P, (long long)S);
+    const int64_t nnz = rows * W * V;
+    if (nnz >= (int64_t)1 << 32)
+        return fail(SDP_EINVAL, "operators of %lld entries together: entry positions are 32-bit words (at most 2^32 - 1 entries)", (long long)nnz);
+    sdp_transop *op = nullptr;
+    int rc;
+    if ((rc = transop_new(f->dtype, rows, nnz, &op))) return rc;
+    std::unique_ptr<sdp_transop> guard(op);
+    op->P = (int)P; op->Sm = S;
+    DevBuf dpol, done, tgt, val;
+    if ((rc = upload(dpol, host_pol, (size_t)rows * f->nu * rs))) return rc;          // [P][S][nu]
+    if (f->W <= 0) {                                       // deterministic members: the law of one point of weight 1
+        const double one8 = 1.0;
+        const float one4 = 1.0f;
+        if ((rc = upload(done, f->dtype == SDP_F32 ? (const void *)&one4 : (const void *)&one8, rs))) return rc;
+    }
+    if ((rc = tgt.alloc((size_t)nnz * 4))) return rc;
+    if ((rc = val.alloc((size_t)nnz * rs))) return rc;
+    if ((rc = op->gbar.alloc((size_t)rows * rs))) return rc;
+    {
+        const std::vector<int32_t> ones((size_t)P, 1);
+        if ((rc = upload(op->flags, ones.data(), (size_t)P * 4))) return rc;
+    }
+    if ((rc = op->running.alloc((size_t)P * 4))) return rc;
+    if ((rc = op->mstats.alloc((size_t)P * 3 * 8))) return rc;
+    SdpFamilyTransArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f.pol = dpol.p; a.f.axes = f->axes.p; a.f.prm = f->prm.p;
+    a.f.wgrid = f->W > 0 ? f->wgrid.p : nullptr;
+    a.f.proba = f->W > 0 ? f->proba.p : done.p;
+    a.f.S = S; a.f.t_k = t_k;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.f.orders[k] = f->orders[k]; a.f.axis_off[k] = f->axis_off[k]; }
+    a.f.n_axes = f->n_axes; a.f.W = f->W; a.f.n_active = (int32_t)P;
+    a.tgt = (int32_t *)tgt.p; a.val = val.p; a.gbar = op->gbar.p; a.W = (int32_t)W;
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    // a tile of 256 >> d nodes of one member is a workgroup: at most the workgroups that are resident, the rest in the
+    // kernel's stride loop
+    const int64_t tiles = (S + f->trans_tile - 1) / f->trans_tile;
+    int64_t blocks = P * tiles;
+    if (blocks > (int64_t)f->cus * 8) blocks = (int64_t)f->cus * 8;
+    HIP_TRY(hipStreamSynchronize(f->stream));        // lifted constants set on the family's stream
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    HIP_TRY(hipModuleLaunchKernel(f->f_transitions, (unsigned)blocks, 1, 1, 256, 1, 1, 0, op->stream, nullptr, extra));
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    if ((rc = transop_build_csr(op, (const int32_t *)tgt.p, val.p, nullptr, (uint32_t)(W * V)))) return rc;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    op->entries_ms = ms;
+    op->last_kernel_ms = op->entries_ms + op->sort_ms;
+    op->has_gbar = true;
+    guard.release();
+    *out = op;
+    return SDP_OK;
+}
+
+extern "C" int sdp_transop_push_until_members(sdp_transop *op, int32_t n_max, int32_t check_every, double tol,
+                                              int32_t *n_done, double *delta)
+{
+    if (!op || !n_done || !delta) return fail(SDP_EINVAL, "NULL argument");
+    if (op->P < 1) return fail(SDP_EINVAL, "not the operators of a family (sdp_family_transop_create)");
+    if (n_max < 1) return fail(SDP_EINVAL, "n_max must be at least 1");
+    if (check_every < 1) return fail(SDP_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0)) return fail(SDP_EINVAL, "tol must be a number >= 0");
+    int rc;
+    if ((rc = transop_set(op, nullptr))) return rc;
+    if ((rc = transop_all_running(op))) return rc;
+    const size_t P = (size_t)op->P;
+    const size_t slice = (size_t)op->Sm * real_size(op->dtype);
+    std::vector<int32_t> running(P), flags(P, 1), keep, leave;
+    for (size_t p = 0; p < P; ++p) { running[p] = (int32_t)p; n_done[p] = 0; delta[p] = NAN; }
+    HIP_TRY(hipMemcpyAsync(op->running.p, running.data(), P * 4, hipMemcpyHostToDevice, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    std::vector<unsigned long long> keys(P * 3);
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    for (int32_t k = 0; k < n_max && !running.empty(); ++k) {
+        if ((rc = transop_launch_push(op))) return rc;     // the rows of the members still running
+        for (int32_t p : running) n_done[p] = k + 1;
+        if ((k + 1) % check_every != 0 && k + 1 != n_max) continue;
+        // one reduction launch over the members still running and 24 bytes a member back
+        const int n = (int)running.size();
+        HIP_TRY(hipMemsetAsync(op->mstats.p, 0, (size_t)n * 3 * 8, op->stream));
+        unsigned bx = (unsigned)((op->Sm + 255) / 256);
+        if (bx > 64) bx = 64;
+        unsigned long long *acc = (unsigned long long *)op->mstats.p;
+        const int32_t *members = (const int32_t *)op->running.p;
+        const void *cur = op->mu[op->cur].p, *old = op->mu[1 - op->cur].p;
+        if (op->dtype == SDP_F32)
+            hipLaunchKernelGGL(sdp_family_diff_stats<float>, dim3(bx, n), dim3(256), 0, op->stream,
+                               (const float *)cur, (const float *)old, op->Sm, members, (int64_t)-1, (int64_t)-1, acc);
+        else
+            hipLaunchKernelGGL(sdp_family_diff_stats<double>, dim3(bx, n), dim3(256), 0, op->stream,
+                               (const double *)cur, (const double *)old, op->Sm, members, (int64_t)-1, (int64_t)-1, acc);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(keys.data(), op->mstats.p, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, op->stream));
+        HIP_TRY(hipStreamSynchronize(op->stream));
+        keep.clear(); leave.clear();
+        for (int i = 0; i < n; ++i) {
+            const int32_t p = running[(size_t)i];
+            double d = NAN;
+            if (!keys[(size_t)i * 3 + 2]) {
+                const double dmin = sdp_key_value(~keys[(size_t)i * 3]), dmax = sdp_key_value(keys[(size_t)i * 3 + 1]);
+                d = dmax > -dmin ? dmax : -dmin;
+            }
+            delta[p] = d;
+            if (d <= tol || k + 1 == n_max) leave.push_back(p);          // NaN never converges
+            else keep.push_back(p);
+        }
+        if (leave.empty()) continue;
+        if (!keep.empty()) {
+            // a member that stops here is computed no more: its iterate goes into the other buffer as well, so it is
+            // in the buffer sdp_transop_get reads however many pushes the others still run
+            for (int32_t p : leave) {
+                flags[(size_t)p] = 0;
+                HIP_TRY(hipMemcpyAsync((char *)op->mu[1 - op->cur].p + (size_t)p * slice, (const char *)op->mu[op->cur].p + (size_t)p * slice,
+                                       slice, hipMemcpyDeviceToDevice, op->stream));
+            }
+            HIP_TRY(hipMemcpyAsync(op->flags.p, flags.data(), P * 4, hipMemcpyHostToDevice, op->stream));
+            HIP_TRY(hipMemcpyAsync(op->running.p, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, op->stream));
+            HIP_TRY(hipStreamSynchronize(op->stream));     // (the lists change before the copies would have run)
+            op->all_running = false;
+        }
+        running.swap(keep);
+    }
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    op->last_kernel_ms = ms;
     return SDP_OK;
 }
 

@@ -47,6 +47,8 @@ enum {
     , SDP_META_F_FAMILY_HORIZON = 16384 // a family horizon unit (sdp_family_horizon_kernel.h): sdp_family_simulate and, for a
                             // stochastic family, sdp_family_montecarlo_h; SDP_META_THREADS is the Monte Carlo kernel's
                             // workgroup size and SDP_META_COL_ROWS that of sdp_family_simulate
+    , SDP_META_F_FAMILY_TRANS = 32768   // a family transition unit (sdp_family_trans_kernel.h): sdp_family_transitions and
+                            // nothing else; SDP_META_THREADS is its workgroup size and SDP_META_COL_ROWS the nodes of a tile
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -396,6 +398,21 @@ struct SdpTransArgs {
     int32_t pad_;
     int32_t orders[SDP_MAXD];
     int32_t axis_off[SDP_MAXD];
+};
+
+// Entries of the transition operators of a family's policies (sdp_family_trans_kernel.h, kernel
+// `sdp_family_transitions`): SdpTransArgs with a member index in front of every array.  `f` is the block of the sweep
+// with `f.pol` the PRESCRIBED policies [P][S][nu] (read, not written); `f.V`, `f.J`, `f.idx`, the box arrays and
+// `f.members` are unused (null) and `f.n_active` is P: all members run.  A deterministic family has f.W = 0 and
+// `f.proba` the one weight 1, which every member reads.  The operators form ONE block-diagonal operator: member p's
+// node s is row p S + s.
+struct SdpFamilyTransArgs {
+    SdpFamilyArgs f;
+    int32_t *tgt;          // [P][S W 2^d] target rows, p S + node
+    void *val;             // [P][S W 2^d] weights (reals)
+    void *gbar;            // [P][S] mean cost of one step under the member's policy (reals)
+    int32_t W;             // points of every member's flat law (>= 1: f.W, or 1 for a deterministic family)
+    int32_t pad_;
 };
 
 // One-step lookahead at arbitrary states (sdp_lookahead_kernel.h, kernel `sdp_lookahead` of a lookahead unit): the

@@ -25,9 +25,15 @@ workgroup, every lattice made on the device from the member's traced control_box
 workgroup, and `sdp_family_montecarlo_h`, a tile of 256, each step with the member's policy slice and row of constants
 of that step.
 
+`transition_operator` and `stationary_distribution` build the transition operators of the members' policies together
+(csrc/sdp_family_trans_kernel.h): one launch of `sdp_family_transitions`, a tile of 256 >> d nodes of one member a
+workgroup, and one stable sort make a block-diagonal CSR per chunk of members (`FamilyTransitionOperator`), which one
+launch per push moves forward for all members; in `stationary` every member stops at its own checked push.
+
 The definition is the solo call: member p of every result equals, bit for bit, what `solvers[p]` returns from the
-same method with `kernel = 'generic'` (`monte_carlo`, `lookahead`, `monte_carlo_lookahead`, `simulate` and
-`monte_carlo_horizon`, the latter against `solvers[p].monte_carlo`: on its device path, whatever its kernel).
+same method with `kernel = 'generic'` (`monte_carlo`, `lookahead`, `monte_carlo_lookahead`, `simulate`,
+`monte_carlo_horizon` -- against `solvers[p].monte_carlo` -- and `transition_operator`: on its device path, whatever its
+kernel).
 
 Members may differ in every real constant of dyn / cost, in the ends of the state grid, in the perturbation grid
 and weights, in control_steps and control_box.  They must agree in the grid's shape, the dtype, the number of
@@ -44,11 +50,12 @@ import numpy as np
 from . import _native as nat
 from . import codegen
 from . import convergence as conv
+from . import forward
 from . import montecarlo as mc
 from .solver import DPSolver
 from .trace import TraceError, trace_model
 
-__all__ = ['SolverFamily']
+__all__ = ['SolverFamily', 'FamilyTransitionOperator']
 
 
 class _FamilyProblem(object):
@@ -258,6 +265,18 @@ class _FamilyProblem(object):
             nat.ptr(x_final), nat.ptr(occ)))
         return cost_sum, n_out, x_final, occ
 
+    # ---- transition operators (csrc/sdp_family_trans_kernel.h)
+    def load_trans_unit(self, module):
+        nat.check(nat.lib().sdp_family_load_trans_unit(self.h, module.encode()))
+
+    def transop_create(self, pol, t_k):
+        """pol [P][S][nu] at the constants set: the sdp_transop handle of the members' block-diagonal operator (the
+        caller owns it; it does not refer to this handle afterwards)"""
+        assert pol.shape == (self.P, self.S, self.nu) and pol.flags.c_contiguous and pol.dtype == self.dtype
+        h = C.c_void_p()
+        nat.check(nat.lib().sdp_family_transop_create(self.h, nat.ptr(pol), float(t_k), C.byref(h)))
+        return h
+
     def get_value(self):
         J = np.empty((self.P,) + self.shape, dtype=self.dtype)
         nat.check(nat.lib().sdp_family_get_value(self.h, nat.ptr(J)))
@@ -310,6 +329,153 @@ def _structure_message(p, model, first, where='', what=('model', 'dyn / cost')):
 
 
 _BOX = ('control_box', 'control_box')
+
+
+class FamilyTransitionOperator(object):
+    """The transition operators of a family's policies on the device (`SolverFamily.transition_operator`): per chunk of
+    members ONE block-diagonal CSR matrix in device memory -- member p's node s is row p_local * S + s -- owner of
+    one sdp_transop handle per chunk (include/sdp_hip.h: sdp_family_transop_create).  Member p of everything it returns
+    equals, bit for bit, what `solvers[p].transition_operator(pol[p], t_k)` returns on the device:
+    `stodynprog_amd.forward` on member p is the definition.  NOT in the reference API.
+
+    shape     : the members' state grid's
+    P         : members
+    nnz       : entries of all members, P S W 2^d
+    mean_cost : gbar of every member, (P,) + shape
+    info      : entries, bytes, members, chunks, build_ms (entries_ms + sort_ms) and, once used, push_ms and pushes"""
+
+    def __init__(self, parts, shape, dtype, nnz_member):
+        self.parts = [(int(a), int(b), h) for a, b, h in parts]      # [(first, last, sdp_transop handle)]
+        self.shape = tuple(shape)
+        self.dtype = np.dtype(dtype)
+        self.S = int(np.prod(self.shape))
+        self.P = self.parts[-1][1]
+        self.nnz_member = int(nnz_member)
+        self.nnz = self.P * self.nnz_member
+        self.nbytes = sum(forward.operator_bytes((b - a) * self.nnz_member, (b - a) * self.S, self.dtype.itemsize)
+                          for a, b, _ in self.parts)
+        self._csr = None                   # (chunk, its CSR on the host): the chunk `tocsr` read last
+        self.mean_cost = np.empty((self.P,) + self.shape, dtype=self.dtype)
+        entries_ms = sort_ms = 0.0
+        for a, b, h in self.parts:
+            gbar = np.empty((b - a,) + self.shape, dtype=self.dtype)
+            nat.check(nat.lib().sdp_transop_get_mean_cost(h, nat.ptr(gbar)))
+            self.mean_cost[a:b] = gbar
+            e_ms, s_ms = C.c_double(0.0), C.c_double(0.0)
+            nat.check(nat.lib().sdp_transop_build_ms(h, C.byref(e_ms), C.byref(s_ms)))
+            entries_ms, sort_ms = entries_ms + e_ms.value, sort_ms + s_ms.value
+        self.info = dict(entries=self.nnz, bytes=self.nbytes, members=self.P, chunks=len(self.parts), path='device',
+                         build_ms=entries_ms + sort_ms, entries_ms=entries_ms, sort_ms=sort_ms)
+
+    def close(self):
+        for _, _, h in getattr(self, 'parts', ()):
+            nat.lib().sdp_transop_destroy(h)
+        self.parts = []
+        self._csr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.P
+
+    def _parts(self):
+        if not self.parts:
+            raise ValueError('the operator is closed')
+        return self.parts
+
+    def _vectors(self, mu):
+        """[P][S] in the operator's reals, from an array of the grid's shape (every member's) or (P,) + shape"""
+        mu = np.asarray(mu)
+        one, each = self.shape, (self.P,) + self.shape
+        if mu.shape == one and one != each:
+            mu = np.broadcast_to(mu, each)
+        elif mu.shape != each:
+            raise ValueError('mu must have shape {} (the same for all {} members) or {} (member p from mu[p]), not {}'.format(
+                one, self.P, each, mu.shape))
+        return np.ascontiguousarray(mu, dtype=self.dtype).reshape(self.P, self.S)
+
+    def _kernel_ms(self, h):
+        ms = C.c_double(0.0)
+        nat.check(nat.lib().sdp_transop_last_kernel_ms(h, C.byref(ms)))
+        return ms.value
+
+    def _get(self, h, a, b, out):
+        part = np.empty((b - a, self.S), dtype=self.dtype)
+        nat.check(nat.lib().sdp_transop_get(h, nat.ptr(part)))
+        out[a:b] = part.reshape((b - a,) + self.shape)
+
+    def push(self, mu, n_steps=1):
+        """every member's mu after n_steps steps under its policy, (P_p^T)^n mu_p: (P,) + shape.  mu: (P,) + shape,
+        or the grid's shape for all members.  One launch per step pushes all members of a chunk."""
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError('n_steps must not be negative')
+        mu = self._vectors(mu)
+        out = np.empty((self.P,) + self.shape, dtype=self.dtype)
+        ms = 0.0
+        for a, b, h in self._parts():
+            nat.check(nat.lib().sdp_transop_push(h, nat.ptr(np.ascontiguousarray(mu[a:b])), n_steps))
+            ms += self._kernel_ms(h)
+            self._get(h, a, b, out)
+        self.info.update(push_ms=ms, pushes=n_steps)
+        return out
+
+    def stationary(self, mu0=None, tol=1e-12, n_max=10000, check_every=10):
+        """The power iteration of `TransitionOperator.stationary` on every member, one launch per push for all members
+        still running: member p stops at its own first checked push with max |mu_{k+1} - mu_k| <= tol over its slice,
+        or at n_max, and is computed no more.  mu0: (P,) + shape, the grid's shape for all members, or None (uniform).
+        Returns a `forward.FamilyStationary` record (mu, n_done, converged, delta, average_cost, mass, each stacked over
+        the members; res[p] is the solo `forward.Stationary` of member p)."""
+        tol, check_every = conv.validate(tol, check_every)
+        n_max = int(n_max)
+        if n_max < 1:
+            raise ValueError('n_max must be at least 1')
+        if mu0 is None:
+            mu0 = np.broadcast_to(forward.uniform(self.S, self.dtype), (self.P, self.S))
+        else:
+            mu0 = self._vectors(mu0)
+        mu = np.empty((self.P,) + self.shape, dtype=self.dtype)
+        n_done = np.zeros(self.P, dtype=np.int32)
+        delta = np.full(self.P, np.nan)
+        ms = 0.0
+        for a, b, h in self._parts():
+            nat.check(nat.lib().sdp_transop_push(h, nat.ptr(np.ascontiguousarray(mu0[a:b])), 0))
+            done, d = np.zeros(b - a, dtype=np.int32), np.full(b - a, np.nan)
+            nat.check(nat.lib().sdp_transop_push_until_members(h, n_max, check_every, tol, nat.ptr(done), nat.ptr(d)))
+            n_done[a:b], delta[a:b] = done, d
+            ms += self._kernel_ms(h)
+            self._get(h, a, b, mu)
+        self.info.update(push_ms=ms, pushes=int(n_done.max()))
+        return forward.FamilyStationary(mu, n_done, delta, tol, self.mean_cost)
+
+    def set_long_rows(self, min_entries):
+        """`TransitionOperator.set_long_rows` on every chunk: no result depends on it"""
+        for _, _, h in self._parts():
+            nat.check(nat.lib().sdp_transop_set_long_rows(h, int(min_entries)))
+        self.info['long_rows_from'] = int(min_entries)
+
+    def tocsr(self, p):
+        """(indptr int64 [S + 1], indices int32, data) of member p's P^T, in the member's own node ids"""
+        p = int(p)
+        if not 0 <= p < self.P:
+            raise IndexError('member {} of {}'.format(p, self.P))
+        c = next(i for i, (a, b, _) in enumerate(self._parts()) if a <= p < b)
+        a, b, h = self.parts[c]
+        if self._csr is None or self._csr[0] != c:
+            rows, nnz = (b - a) * self.S, (b - a) * self.nnz_member
+            indptr = np.empty(rows + 1, dtype=np.int64)
+            indices = np.empty(nnz, dtype=np.int32)
+            data = np.empty(nnz, dtype=self.dtype)
+            nat.check(nat.lib().sdp_transop_get_csr(h, nat.ptr(indptr), nat.ptr(indices), nat.ptr(data)))
+            self._csr = (c, (indptr, indices, data))
+        indptr, indices, data = self._csr[1]
+        first = (p - a) * self.S
+        lo, hi = int(indptr[first]), int(indptr[first + self.S])
+        return indptr[first:first + self.S + 1] - lo, indices[lo:hi] - np.int32(first), data[lo:hi].copy()
 
 
 class SolverFamily(object):
@@ -421,13 +587,15 @@ class SolverFamily(object):
         (allocated at the first evaluation), its flag of the policy compare and its word of the resident kernel"""
         return int(np.prod(self.dims)) * self.nu * self.dtype.itemsize + 8
 
-    def _chunks(self, tabs, extra=0):
+    def _chunks(self, tabs, extra=0, most=None):
         """[(first, last), ...]: members whose device arrays take at most chunk_bytes together (`extra`: bytes a
-        member takes beside _member_bytes in this call)"""
+        member takes beside _member_bytes in this call; `most`: the most members a chunk may hold whatever their bytes)"""
         step = max(1, int(self.chunk_bytes) // (self._member_bytes(tabs) + extra))
+        if most is not None:
+            step = max(1, min(step, int(most)))
         return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
 
-    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None, horizon=None):
+    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None, horizon=None, trans=None):
         """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims.  evaluation: the
         call evaluates policies, so every handle also loads the family's evaluation unit and the chunks leave room
         for the prescribed policy.  mc_bytes: the call is a Monte Carlo run whose arrays take that many bytes a
@@ -436,15 +604,19 @@ class SolverFamily(object):
         source, bprm, steps, bytes a member takes beside the handle's), so every handle also loads the family's
         lookahead unit and is given its members' box constants and control steps.  horizon: the call is a closed loop over
         a horizon (dict(source, bytes): the horizon unit and the bytes a member takes beside the handle's), so every
-        handle also loads the family's horizon unit (J0 is None then).  Returns the chunks [(first, last), ...] it ran in"""
+        handle also loads the family's horizon unit (J0 is None then).  trans: the call builds transition operators
+        (dict(bytes, most): the bytes a member takes beside the handle's and the most members of a chunk), so every handle
+        also loads the family's transition unit (J0 is None then).  Returns the chunks [(first, last), ...] it ran in"""
         nat.require_gpu()
         module = nat.compile_model(tabs['source'])
         look_module = nat.compile_model(look['source']) if look is not None else None
         policy_module = nat.compile_model(codegen.family_policy_unit(tabs['model'], self.dtype)) if evaluation else None
         mc_module = nat.compile_model(codegen.family_mc_unit(tabs['model'], self.dtype)) if mc_bytes is not None else None
         horizon_module = nat.compile_model(horizon['source']) if horizon is not None else None
+        trans_module = nat.compile_model(codegen.family_trans_unit(tabs['model'], self.dtype)) if trans is not None else None
         chunks = self._chunks(tabs, self._policy_bytes() if evaluation else
-                              int(mc_bytes or 0) + (look['bytes'] if look else 0) + (horizon['bytes'] if horizon else 0))
+                              int(mc_bytes or 0) + (look['bytes'] if look else 0) + (horizon['bytes'] if horizon else 0)
+                              + (trans['bytes'] if trans else 0), trans['most'] if trans else None)
         digest = hashlib.sha256()
         for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
             if tabs[k] is not None:
@@ -470,6 +642,9 @@ class SolverFamily(object):
                 if horizon_module is not None and getattr(prob, 'horizon_module', None) != horizon_module:
                     prob.load_horizon_unit(horizon_module)
                     prob.horizon_module = horizon_module
+                if trans_module is not None and getattr(prob, 'trans_module', None) != trans_module:
+                    prob.load_trans_unit(trans_module)
+                    prob.trans_module = trans_module
                 if look_module is not None:
                     if getattr(prob, 'look_module', None) != look_module:
                         prob.load_lookahead_unit(look_module)
@@ -1263,6 +1438,89 @@ class SolverFamily(object):
         self.backend_info['monte_carlo'] = dict(members=self.P, n_traj=B, chunks=self.backend_info['chunks'],
                                                 launches=self.backend_info['chunks'] * (-(-n_steps // min(spl, 1 << 30))))
         return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
+
+    # ------------------------------------------------------------------ state distributions under the members' policies
+    def _transition_size(self):
+        """(S, nnz, bytes) of ONE member's transition operator (DPSolver._transition_size: the members agree)"""
+        S = int(np.prod(self.dims))
+        nnz = S * max(self.W, 1) * (1 << len(self.dims))
+        return S, nnz, forward.operator_bytes(nnz, S, self.dtype.itemsize)
+
+    def _transition_bytes(self):
+        """bytes of device arrays one member takes in transition_operator beside _member_bytes: its operator
+        (forward.operator_bytes), its entries in emission order (targets and values), the temporaries of the sort (the
+        sorted keys, the positions before and after, and as much again for the sort's own double buffers), the
+        histogram, its policy, its mean costs and two vectors, its flag, its place in the list and its statistics"""
+        S, nnz, nbytes = self._transition_size()
+        rs = self.dtype.itemsize
+        return nbytes + nnz * (4 + rs) + nnz * 24 + 8 * (S + 1) + S * rs * (self.nu + 3) + 32
+
+    def _transition_most(self):
+        """the most members a chunk of transition_operator may hold: entry positions are 32-bit words, rows 32-bit ids,
+        and a reduction launch lists at most 65535 members"""
+        S, nnz, _ = self._transition_size()
+        return max(1, min((2 ** 32 - 1) // nnz, (2 ** 31 - 1) // S, 65535))
+
+    def transition_operator(self, pol, t_k=None):
+        """`DPSolver.transition_operator` of every member in one device call per chunk (kernel sdp_family_transitions,
+        csrc/sdp_family_trans_kernel.h; one sort for all members): a `FamilyTransitionOperator`, member p of everything
+        it returns equal, bit for bit, to what `solvers[p].transition_operator(pol[p], t_k)` returns on the device.
+
+        pol : (P,) + dims + (nu,), or dims + (nu,): every member's policy
+        t_k : time index of a non-stationary family (default 0).  Members symbolic in time get it as the kernel's `t`;
+              members that look data up as data[k] are traced for that step, one row of constants per member.
+        Deterministic members run as W = 1, P = [1].  A family has no host path."""
+        one, each = self.dims + (self.nu,), (self.P,) + self.dims + (self.nu,)
+        # ---- everything that is refused, before a device is touched
+        if np.shape(pol) not in (one, each):
+            raise ValueError('pol must have shape {} (one policy for all {} members) or {} (member p under pol[p]), '
+                             'not {}'.format(one, self.P, each, np.shape(pol)))
+        for p, s in enumerate(self.solvers):
+            _, nnz, nbytes = s._transition_size()
+            if nbytes > s.TRANSITION_MAX_BYTES:
+                raise ValueError('member {}: the transition operator of this grid has nnz = {} entries and takes {} bytes: '
+                                 'more than DPSolver.TRANSITION_MAX_BYTES = {} bytes'.format(p, nnz, nbytes, s.TRANSITION_MAX_BYTES))
+            if nnz >= 1 << 32:
+                raise ValueError('member {}: the transition operator of this grid has nnz = {} entries ({} bytes): entry '
+                                 'positions are 32-bit words, at most 2**32 - 1 entries whatever the cap'.format(p, nnz, nbytes))
+        pol = self._policy(pol)
+        t_trace = None if self.stationnary else (0 if t_k is None else t_k)
+        tabs = self._tables(t_trace)
+        S, nnz, _ = self._transition_size()
+        pol_d = pol.reshape(self.P, S, self.nu)
+        parts = []
+
+        def work(prob, a, b):
+            parts.append((a, b, prob.transop_create(np.ascontiguousarray(pol_d[a:b]), 0 if t_trace is None else t_trace)))
+        try:
+            self._run(tabs, None, work, trans=dict(bytes=self._transition_bytes(), most=self._transition_most()))
+        except Exception:
+            for _, _, h in parts:
+                nat.lib().sdp_transop_destroy(h)
+            raise
+        op = FamilyTransitionOperator(parts, self.dims, self.dtype, nnz)
+        # (the operator's record: push times are added to it as the operator is used)
+        self.backend_info = dict(self.backend_info, transition=op.info)
+        return op
+
+    def stationary_distribution(self, pol, t_k=None, **kw):
+        """`transition_operator(pol, t_k).stationary(**kw)` in one call: the stationary state distribution of every
+        member under its policy (a `forward.FamilyStationary` record).  The operator is closed when done."""
+        unknown = sorted(set(kw) - {'mu0', 'tol', 'n_max', 'check_every'})
+        if unknown:
+            raise TypeError('stationary_distribution got unexpected keyword argument(s) {}'.format(', '.join(unknown)))
+        # (what `stationary` refuses, before an operator is built)
+        conv.validate(kw.get('tol', 1e-12), kw.get('check_every', 10))
+        if int(kw.get('n_max', 10000)) < 1:
+            raise ValueError('n_max must be at least 1')
+        if kw.get('mu0') is not None and np.shape(kw['mu0']) not in (self.dims, (self.P,) + self.dims):
+            raise ValueError('mu must have shape {} (the same for all {} members) or {} (member p from mu[p]), not {}'.format(
+                self.dims, self.P, (self.P,) + self.dims, np.shape(kw['mu0'])))
+        op = self.transition_operator(pol, t_k)
+        try:
+            return op.stationary(**kw)
+        finally:
+            op.close()
 
     def last_kernel_ms(self):
         """HIP-event time of the launches of the last sweep, evaluation or Monte Carlo call of a family that runs as one

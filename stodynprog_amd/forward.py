@@ -59,6 +59,37 @@ Entries = collections.namedtuple('Entries', 'tgt src val mean_cost S W V')
 Stationary = collections.namedtuple('Stationary', 'mu n_done converged delta average_cost mass')
 
 
+class FamilyStationary(object):
+    """What `FamilyTransitionOperator.stationary` returns (stodynprog_amd/family.py): the fields of `Stationary`
+    stacked on a leading member axis.
+
+    mu (P,) + dims, n_done (P,) int, converged (P,) bool, delta (P,), average_cost (P,) float64 (NaN for an operator
+    without mean costs), mass (P,) in the problem's reals.  len(res) == P and res[p] is the `Stationary` of member p:
+    what `finish` makes of the member's last iterate, as the solo call does."""
+
+    def __init__(self, mu, n_done, delta, tol, mean_cost=None):
+        mu = np.asarray(mu)
+        self._members = [finish(mu[p], n_done[p], delta[p], tol, None if mean_cost is None else mean_cost[p])
+                         for p in range(mu.shape[0])]
+        self.mu = mu
+        self.n_done = np.array([m.n_done for m in self._members], dtype=np.int64)
+        self.converged = np.array([m.converged for m in self._members], dtype=bool)
+        self.delta = np.array([m.delta for m in self._members], dtype=np.float64)
+        self.average_cost = np.array([np.nan if m.average_cost is None else m.average_cost for m in self._members],
+                                     dtype=np.float64)
+        self.mass = np.array([m.mass for m in self._members], dtype=mu.dtype)
+
+    def __len__(self):
+        return len(self._members)
+
+    def __getitem__(self, p):
+        return self._members[p]
+
+    def __repr__(self):
+        return 'FamilyStationary({} members, n_done={}, converged={})'.format(len(self), self.n_done.tolist(),
+                                                                           self.converged.tolist())
+
+
 def operator_bytes(nnz, S, itemsize):
     """bytes of an operator of nnz entries on S nodes: values, sources and the row pointers"""
     return int(nnz) * (int(itemsize) + 4) + 8 * (int(S) + 1)
