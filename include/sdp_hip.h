@@ -626,6 +626,47 @@ int sdp_family_montecarlo_lookahead(sdp_family *f, int64_t B, int64_t T, int64_t
                                     void *host_cost_sum, int64_t *host_n_outside, void *host_x_final,
                                     uint64_t *host_occupancy);
 
+/*
+ * Closed loops of a family under lookahead controls over a horizon (csrc/sdp_family_lookahead_horizon_kernel.h).  The
+ * family's unit (codegen.family_lookahead_horizon_unit: kernels sdp_family_simulate_lookahead and, for a stochastic
+ * family, sdp_family_montecarlo_lookahead_h) is loaded beside the sweep unit; its sdp_meta is checked
+ * (SDP_META_F_FAMILY_LOOKAHEAD_HORIZON, the workgroup size, the lanes of a state).  The lanes and the number of box
+ * constants are shared with the lookahead unit of the handle: loading a unit that differs in either drops the other.
+ * sdp_family_set_lookahead_box is to be called after every load, as for the lookahead unit.
+ */
+int sdp_family_load_lookahead_horizon_unit(sdp_family *f, const char *module_path);
+/*
+ * sdp_problem_simulate_lookahead of every member of the handle, together, every lattice made on the device: B
+ * trajectories of T >= 1 steps per member.  host_V is [P][V_steps][S] reals: a time-indexed cost-to-go (V_timed != 0,
+ * V_steps == T, step k looks ahead into slice k: it goes up a chunk of whole steps of all members at a time, at most
+ * chunk_bytes, a larger step a chunk of its own) or one cost-to-go per member (V_timed == 0, V_steps == 1: uploaded
+ * once, read with a step stride of 0); the handle's value array is not read.  host_prm is the table of lifted constants
+ * [P][T][n_prm] (prm_timed != 0) or [P][1][n_prm] (prm_timed == 0), as in sdp_family_simulate; the box is that of
+ * sdp_family_set_lookahead_box, at the time index t0 + k.  host_x0 [P][d][B], host_w [P][T][B] (NULL: a deterministic
+ * family); results host_x [P][T+1][d][B], host_u [P][T][nu][B], host_g and host_q [P][T][B] (q: the minimised expected
+ * value).  A state without a valid lattice gives NaN controls and q, and the trajectory goes on as the model maps them.
+ * Member p of every result has the bits of sdp_problem_simulate_lookahead on problem p alone; no cut changes one.
+ * sdp_family_last_kernel_ms covers the call.  SDP_EINVAL for a NULL pointer, a negative size, T < 1, a cost-to-go or
+ * table of another length, chunk_bytes < 1, missing perturbation sequences, no unit loaded, or no box set.
+ */
+int sdp_family_simulate_lookahead(sdp_family *f, const void *host_V, int64_t V_steps, int32_t V_timed,
+                                  const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes, int64_t B,
+                                  int64_t T, const void *host_x0, const void *host_w, double t0, void *host_x,
+                                  void *host_u, void *host_g, void *host_q);
+/*
+ * sdp_problem_montecarlo_lookahead of every member of the handle, together: the arguments and results of
+ * sdp_family_montecarlo_lookahead with the cost-to-go and the table of sdp_family_simulate_lookahead.  Launches are cut
+ * at the cost-to-go's chunks and at steps_per_launch; the states, the sums, n_outside and the occupancy stay on the
+ * device in between.
+ */
+int sdp_family_montecarlo_lookahead_h(sdp_family *f, const void *host_V, int64_t V_steps, int32_t V_timed,
+                                      const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes,
+                                      int64_t B, int64_t T, int64_t n_burn, const uint64_t *host_seeds,
+                                      uint64_t traj_offset, const void *host_x0, const double *host_cum, int32_t n_law,
+                                      const void *host_law_grid, double t0, int64_t steps_per_launch,
+                                      void *host_cost_sum, int64_t *host_n_outside, void *host_x_final,
+                                      uint64_t *host_occupancy);
+
 /* ---- tabulated backup (models that cannot be traced into device code) ------- */
 /*
  * Replaces the numeric part of DPSolver._value_at_state_vect

@@ -160,6 +160,10 @@ def _declare(lib):
         'sdp_family_lookahead': (C.c_int, [vp, i64, vp, dbl, vp, vp, vp]),
         'sdp_family_montecarlo_lookahead': (C.c_int, [vp, i64, i64, i64, vp, C.c_uint64, vp, vp, i32, vp, dbl, i64, vp,
                                                       vp, vp, vp]),
+        'sdp_family_load_lookahead_horizon_unit': (C.c_int, [vp, C.c_char_p]),
+        'sdp_family_simulate_lookahead': (C.c_int, [vp, vp, i64, i32, vp, i32, i32, i64, i64, i64, vp, vp, dbl, vp, vp, vp, vp]),
+        'sdp_family_montecarlo_lookahead_h': (C.c_int, [vp, vp, i64, i32, vp, i32, i32, i64, i64, i64, i64, vp, C.c_uint64,
+                                                        vp, vp, i32, vp, dbl, i64, vp, vp, vp, vp]),
         'sdp_family_load_trans_unit': (C.c_int, [vp, C.c_char_p]),
         'sdp_family_transop_create': (C.c_int, [vp, vp, dbl, P(vp)]),
         'sdp_transop_push_until_members': (C.c_int, [vp, i32, i32, dbl, vp, vp]),

@@ -986,6 +986,29 @@ def family_lookahead_unit(model, box, dtype, lanes):
     return '\n'.join(head)
 
 
+def family_lookahead_horizon_unit(model, box, dtype, lanes):
+    """The generated source of a family LOOKAHEAD unit OVER A HORIZON (csrc/sdp_family_lookahead_horizon_kernel.h,
+    kernels `sdp_family_simulate_lookahead` and, for a stochastic model, `sdp_family_montecarlo_lookahead_h`): what
+    `family_lookahead_unit` generates, marked SDP_FAMILY_LOOKAHEAD_HORIZON, with the horizon header in the place of
+    the lookahead header (which it includes for the walk, the box and the backup).  The steps of a model traced per
+    step (`data[k]`) share the unit, each with its row of constants; the box function is one for all steps."""
+    if model.param_index is None or getattr(box, 'param_index', None) is None:
+        raise ValueError('a family lookahead unit takes a model and a box with lifted constants (lift_constants)')
+    if model.n_perturb >= 2:
+        raise NotImplementedError('a family unit takes one perturbation variable at most')
+    if box.t_value is not None or box.inexact_ops():
+        raise ValueError('the box function of a lookahead unit is a trace with a symbolic time index and exact operations')
+    real = {'float64': 'double', 'float32': 'float'}[np.dtype(dtype).name]
+    head = _prologue_lines(model, real, lanes, None)
+    at = head.index('#include "sdp_device.h"')
+    head.insert(at, '#define SDP_FAMILY 1          // the helpers of csrc/sdp_family_kernel.h ..')
+    head.insert(at + 1, '#define SDP_FAMILY_LOOKAHEAD_HORIZON 1   // .. and the two closed loops under lookahead controls in the place of sdp_family_sweep')
+    head += ['#define SDP_NBOXPARAMS {}     // constants of the box function, read from the member\'s row'.format(len(box.param_index)),
+             box_function_source(box, at=True), '',
+             '#include "sdp_family_lookahead_horizon_kernel.h"    // brings in sdp_family_lookahead_kernel.h: its helpers, the lattice rule, the draw helpers', '']
+    return '\n'.join(head)
+
+
 def translation_unit(model, dtype, lanes, family=None, debug=None, peer_stores=False, lookahead=None):
     """The generated source of one model code object.  `family`: what the unit is to hold beside the direct node-order
     kernels of csrc/sdp_sweep_kernel.h --
@@ -1727,6 +1750,11 @@ def source_key(source):
     if '#define SDP_FAMILY_LOOKAHEAD ' in source:
         # (it includes sdp_family_kernel.h, above, sdp_mc_kernel.h, one of _HEADERS, and the lattice rule)
         for fn in ('sdp_family_lookahead_kernel.h', 'sdp_lattice_kernel.h'):
+            with open(os.path.join(CSRC, fn), 'rb') as f:
+                h.update(f.read())
+    if '#define SDP_FAMILY_LOOKAHEAD_HORIZON ' in source:
+        # (it includes sdp_family_lookahead_kernel.h for its helpers, and with it what that header includes)
+        for fn in ('sdp_family_lookahead_horizon_kernel.h', 'sdp_family_lookahead_kernel.h', 'sdp_lattice_kernel.h'):
             with open(os.path.join(CSRC, fn), 'rb') as f:
                 h.update(f.read())
     h.update(source.encode())

@@ -91,6 +91,9 @@ SDP_DEV void sdp_flook_backup(const SdpFamilyArgs &f, const SdpMember &m, const 
     sdp_seg_argmin<sdp_real, SDP_LANES>(best, ibest);
 }
 
+#if !defined(SDP_FLOOK_HELPERS_ONLY)
+// (a lookahead unit over a horizon, sdp_family_lookahead_horizon_kernel.h, takes the walk, the box and the backup above and
+// brings its own kernels and its own sdp_meta)
 extern "C" __global__ void __launch_bounds__(SDP_FLOOK_THREADS) sdp_family_lookahead(SdpFamilyLookArgs a)
 {
     constexpr int L = SDP_LANES;
@@ -249,3 +252,4 @@ __constant__ int32_t sdp_meta[SDP_META_WORDS] = {
     SDP_META_MAGIC, (int32_t)sizeof(sdp_real), SDP_D, SDP_NU, SDP_HAS_W, 0, 0, 1,
     SDP_META_F_FAMILY | SDP_META_F_FAMILY_LOOKAHEAD, SDP_NBOXPARAMS, 0, SDP_FLOOK_THREADS, SDP_LANES, 0, 0, 0};
 }
+#endif  // !SDP_FLOOK_HELPERS_ONLY

@@ -3818,6 +3818,11 @@ struct sdp_family {
     int look_lanes = 0, n_box = 0;
     DevBuf bprm, look_steps;
     bool has_look_box = false;
+    // closed loops under lookahead controls over a horizon (sdp_family_load_lookahead_horizon_unit): the unit and its
+    // kernels (f_lh_montecarlo: a stochastic family's only).  look_lanes, n_box and the members' box rows are shared
+    // with the lookahead unit: both are generated from the same lattice plan and the same box function
+    hipModule_t lhmod = nullptr;
+    hipFunction_t f_lh_simulate = nullptr, f_lh_montecarlo = nullptr;
     // transition operators (sdp_family_load_trans_unit): the unit, its kernel and the nodes of a workgroup's tile; an
     // operator owns its arrays (sdp_transop) and outlives the family
     hipModule_t trmod = nullptr;
@@ -3842,6 +3847,7 @@ struct sdp_family {
         if (mcmod) (void)hipModuleUnload(mcmod);
         if (hzmod) (void)hipModuleUnload(hzmod);
         if (lkmod) (void)hipModuleUnload(lkmod);
+        if (lhmod) (void)hipModuleUnload(lhmod);
         if (trmod) (void)hipModuleUnload(trmod);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -4885,16 +4891,22 @@ static int family_horizon_checks(sdp_family *f, const char *what, int64_t pol_st
     return SDP_OK;
 }
 
+// the slices [first, first + n) of every member's time-indexed array (`slice` bytes a step) into the device's [P][per_chunk][slice]
+static int family_horizon_upload_slices(sdp_family *f, DevBuf &dev, const void *host, size_t slice, int64_t steps,
+                                        int64_t per_chunk, int64_t first, int64_t n)
+{
+    for (size_t p = 0; p < (size_t)f->P; ++p)
+        HIP_TRY(hipMemcpy((char *)dev.p + p * (size_t)per_chunk * slice,
+                          (const char *)host + (p * (size_t)steps + (size_t)first) * slice, (size_t)n * slice,
+                          hipMemcpyHostToDevice));
+    return SDP_OK;
+}
+
 // the slices [first, first + n) of every member's policy into the device's [P][per_chunk][nu][S]
 static int family_horizon_upload_policy(sdp_family *f, DevBuf &dpol, const void *host_pol, int64_t pol_steps,
                                         int64_t per_chunk, int64_t first, int64_t n)
 {
-    const size_t slice = (size_t)f->nu * f->S * real_size(f->dtype);
-    for (size_t p = 0; p < (size_t)f->P; ++p)
-        HIP_TRY(hipMemcpy((char *)dpol.p + p * (size_t)per_chunk * slice,
-                          (const char *)host_pol + (p * (size_t)pol_steps + (size_t)first) * slice, (size_t)n * slice,
-                          hipMemcpyHostToDevice));
-    return SDP_OK;
+    return family_horizon_upload_slices(f, dpol, host_pol, (size_t)f->nu * f->S * real_size(f->dtype), pol_steps, per_chunk, first, n);
 }
 
 // workgroups per XCD of a launch whose members have `tiles` tiles each (sdp_family_horizon_kernel.h), at most `cap`
@@ -5116,6 +5128,11 @@ extern "C" int sdp_family_load_lookahead_unit(sdp_family *f, const char *module_
         f->lkmod = nullptr; f->f_lookahead = nullptr; f->f_mc_lookahead = nullptr;
         return fail(SDP_EMODULE, "code object %s was not built for this family's lookahead: %s", module_path, why);
     }
+    // (a unit over a horizon that was built for other lanes or another box function is of an earlier plan: it goes)
+    if (f->lhmod && (f->look_lanes != m[SDP_META_COL_ROWS] || f->n_box != m[SDP_META_UTAB])) {
+        (void)hipModuleUnload(f->lhmod);
+        f->lhmod = nullptr; f->f_lh_simulate = nullptr; f->f_lh_montecarlo = nullptr;
+    }
     f->look_lanes = m[SDP_META_COL_ROWS];
     f->n_box = m[SDP_META_UTAB];
     return SDP_OK;
@@ -5124,7 +5141,8 @@ extern "C" int sdp_family_load_lookahead_unit(sdp_family *f, const char *module_
 extern "C" int sdp_family_set_lookahead_box(sdp_family *f, const double *box_params, int32_t n_box, const double *steps)
 {
     if (!f || !steps || n_box < 0 || (n_box > 0 && !box_params)) return fail(SDP_EINVAL, "sdp_family_set_lookahead_box: bad arguments");
-    if (!f->f_lookahead) return fail(SDP_EINVAL, "no lookahead unit loaded (sdp_family_load_lookahead_unit)");
+    if (!f->f_lookahead && !f->f_lh_simulate)
+        return fail(SDP_EINVAL, "no lookahead unit loaded (sdp_family_load_lookahead_unit, sdp_family_load_lookahead_horizon_unit)");
     if (n_box != f->n_box)
         return fail(SDP_EINVAL, "sdp_family_set_lookahead_box: the unit's box function has %d constant(s) per member, %d given", f->n_box, (int)n_box);
     const size_t P = (size_t)f->P;
@@ -5282,6 +5300,253 @@ extern "C" int sdp_family_montecarlo_lookahead(sdp_family *f, int64_t B, int64_t
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
     f->last_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));
+    if (host_occupancy) HIP_TRY(hipMemcpy(host_occupancy, docc.p, P * (size_t)f->S * 8, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Closed loops of a family under lookahead controls over a horizon (csrc/sdp_family_lookahead_horizon_kernel.h):
+// sdp_problem_simulate_lookahead and sdp_problem_montecarlo_lookahead of every member in one launch per cut of the
+// steps.  The unit is loaded beside the sweep unit; the arrays of a run live for the call (the handle's value arrays and
+// its rows of constants are not read).  The cost-to-go [P][V_steps][S] is time-indexed (V_steps == T: it goes up a chunk
+// of whole steps of all members at a time, at most chunk_bytes, by the rule of sdp_family_simulate for its policy) or one
+// per member (V_steps == 1: uploaded once and read with a step stride of 0); the table of constants [P][rows][n_prm] has
+// rows == T or, for a model that is symbolic in time, rows == 1 and a step stride of 0.  The members' box constants and
+// control steps are those of sdp_family_set_lookahead_box.
+// ---------------------------------------------------------------------------
+extern "C" int sdp_family_load_lookahead_horizon_unit(sdp_family *f, const char *module_path)
+{
+    if (!f || !module_path) return fail(SDP_EINVAL, "NULL argument");
+    if (f->lhmod) { (void)hipModuleUnload(f->lhmod); f->lhmod = nullptr; f->f_lh_simulate = nullptr; f->f_lh_montecarlo = nullptr; }
+    f->has_look_box = false;
+    const size_t rs = real_size(f->dtype);
+    hipError_t e = hipModuleLoad(&f->lhmod, module_path);
+    if (e != hipSuccess) { f->lhmod = nullptr; return fail(SDP_EMODULE, "hipModuleLoad(%s): %s", module_path, hipGetErrorString(e)); }
+    int32_t m[SDP_META_WORDS] = {0};
+    hipDeviceptr_t mptr = nullptr;
+    size_t mbytes = 0;
+    const char *why = nullptr;
+    if (hipModuleGetGlobal(&mptr, &mbytes, f->lhmod, "sdp_meta") != hipSuccess || mbytes != sizeof(m)) {
+        (void)hipGetLastError();
+        why = "it does not declare `sdp_meta`";
+    } else {
+        HIP_TRY(hipMemcpyDtoH(m, mptr, sizeof(m)));
+        if (m[SDP_META_MAGIC_AT] != SDP_META_MAGIC) why = "bad magic";
+        else if (!(m[SDP_META_FLAGS] & SDP_META_F_FAMILY_LOOKAHEAD_HORIZON)) why = "not a family lookahead unit over a horizon";
+        else if (m[SDP_META_THREADS] != 256) why = "built for another workgroup size";
+        else if (m[SDP_META_REAL_BYTES] != (int)rs) why = "built for other reals";
+        else if (m[SDP_META_D] != f->d) why = "built for another number of state variables";
+        else if (m[SDP_META_NU] != f->nu) why = "built for another number of controls";
+        else if ((m[SDP_META_HAS_W] != 0) != (f->W > 0)) why = "built for another kind of perturbation";
+        else if (m[SDP_META_COL_ROWS] < 1 || m[SDP_META_COL_ROWS] > 64 || (m[SDP_META_COL_ROWS] & (m[SDP_META_COL_ROWS] - 1))) why = "its lanes per state are no power of two in 1..64";
+        else if (m[SDP_META_UTAB] < 0) why = "a negative number of box constants";
+    }
+    hipDeviceptr_t pptr = nullptr;
+    size_t pbytes = 0;
+    if (!why) {
+        if (hipModuleGetGlobal(&pptr, &pbytes, f->lhmod, "sdp_model_prm") != hipSuccess) { (void)hipGetLastError(); pbytes = 0; }
+        if (pbytes != (size_t)f->n_params * rs) why = "another number of lifted constants";
+    }
+    if (!why && hipModuleGetFunction(&f->f_lh_simulate, f->lhmod, "sdp_family_simulate_lookahead") != hipSuccess) why = "no sdp_family_simulate_lookahead kernel";
+    if (!why && f->W > 0 && hipModuleGetFunction(&f->f_lh_montecarlo, f->lhmod, "sdp_family_montecarlo_lookahead_h") != hipSuccess)
+        why = "no sdp_family_montecarlo_lookahead_h kernel";
+    if (why) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(f->lhmod);
+        f->lhmod = nullptr; f->f_lh_simulate = nullptr; f->f_lh_montecarlo = nullptr;
+        return fail(SDP_EMODULE, "code object %s was not built for this family's lookahead over a horizon: %s", module_path, why);
+    }
+    // (a lookahead unit that was built for other lanes or another box function is of an earlier plan: it goes)
+    if (f->lkmod && (f->look_lanes != m[SDP_META_COL_ROWS] || f->n_box != m[SDP_META_UTAB])) {
+        (void)hipModuleUnload(f->lkmod);
+        f->lkmod = nullptr; f->f_lookahead = nullptr; f->f_mc_lookahead = nullptr;
+    }
+    f->look_lanes = m[SDP_META_COL_ROWS];
+    f->n_box = m[SDP_META_UTAB];
+    return SDP_OK;
+}
+
+// what both calls check of the cost-to-go and the table, and the steps of cost-to-go one upload holds (of all members)
+static int family_lookahead_horizon_checks(sdp_family *f, const char *what, const void *host_V, int64_t V_steps, int32_t V_timed,
+                                           const void *host_prm, int32_t n_prm, int64_t chunk_bytes, int64_t B, int64_t T,
+                                           int64_t *per_chunk)
+{
+    if (!host_V) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 0) return fail(SDP_EINVAL, "negative size");
+    if (T < 1) return fail(SDP_EINVAL, "%s: %lld steps: at least 1", what, (long long)T);
+    if (!f->f_lh_simulate) return fail(SDP_EINVAL, "%s: no lookahead unit over a horizon loaded (sdp_family_load_lookahead_horizon_unit)", what);
+    if (!f->has_look_box) return fail(SDP_EINVAL, "%s: the members' box constants and control steps are not set (sdp_family_set_lookahead_box)", what);
+    if (V_steps != (V_timed ? T : 1))
+        return fail(SDP_EINVAL, "%s: %lld cost-to-go steps for %lld steps (%s)", what, (long long)V_steps, (long long)T,
+                    V_timed ? "a time-indexed cost-to-go has one per step" : "otherwise there is one");
+    if (chunk_bytes < 1) return fail(SDP_EINVAL, "%s: chunk_bytes = %lld: at least 1", what, (long long)chunk_bytes);
+    if (n_prm != f->n_params || (n_prm > 0 && !host_prm))
+        return fail(SDP_EINVAL, "%s: the family has %d lifted constant(s) per member and step, the table has %d", what,
+                    (int)f->n_params, (int)n_prm);
+    const size_t step_bytes = (size_t)f->P * f->S * real_size(f->dtype);
+    int64_t n = V_timed ? (int64_t)((size_t)chunk_bytes / step_bytes) : T;
+    if (n < 1) n = 1;
+    if (n > T) n = T;
+    *per_chunk = n;
+    return SDP_OK;
+}
+
+// the block of the sweep for a launch over a horizon: the cost-to-go and the table of constants are the call's own
+static void family_lookahead_horizon_block(const sdp_family *f, SdpFamilyArgs &a, const void *dV, const void *dprm, double t0)
+{
+    family_lookahead_block(f, a, t0);
+    a.V = dV;
+    a.prm = dprm;
+}
+
+extern "C" int sdp_family_simulate_lookahead(sdp_family *f, const void *host_V, int64_t V_steps, int32_t V_timed,
+                                             const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes,
+                                             int64_t B, int64_t T, const void *host_x0, const void *host_w, double t0,
+                                             void *host_x, void *host_u, void *host_g, void *host_q)
+{
+    if (!f || !host_x0 || !host_x || !host_u || !host_g || !host_q) return fail(SDP_EINVAL, "NULL argument");
+    int rc;
+    int64_t per_chunk = 0;
+    if ((rc = family_lookahead_horizon_checks(f, "sdp_family_simulate_lookahead", host_V, V_steps, V_timed, host_prm, n_prm,
+                                              chunk_bytes, B, T, &per_chunk))) return rc;
+    if (f->W > 0 && !host_w) return fail(SDP_EINVAL, "a stochastic family needs the perturbation sequences");
+    if (B == 0) return SDP_OK;
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    const size_t slice = (size_t)f->S * rs;
+    const int64_t prm_rows = prm_timed ? T : 1;
+    DevBuf dV, dprm, dw, dx, du, dg, dq;
+    if ((rc = dV.alloc(P * (size_t)(V_timed ? per_chunk : 1) * slice))) return rc;
+    if (n_prm > 0 && (rc = upload(dprm, host_prm, P * (size_t)prm_rows * n_prm * rs))) return rc;
+    if (f->W > 0 && (rc = upload(dw, host_w, P * (size_t)T * B * rs))) return rc;                // [P][T][B]
+    if ((rc = dx.alloc(P * (size_t)(T + 1) * f->d * B * rs))) return rc;
+    if ((rc = du.alloc(P * (size_t)T * f->nu * B * rs))) return rc;
+    if ((rc = dg.alloc(P * (size_t)T * B * rs))) return rc;
+    if ((rc = dq.alloc(P * (size_t)T * B * rs))) return rc;
+    // row 0 of every member's x
+    for (size_t p = 0; p < P; ++p)
+        HIP_TRY(hipMemcpy((char *)dx.p + p * (size_t)(T + 1) * f->d * B * rs, (const char *)host_x0 + p * (size_t)f->d * B * rs,
+                          (size_t)f->d * B * rs, hipMemcpyHostToDevice));
+    SdpFamilyLookSimArgs a;
+    memset(&a, 0, sizeof(a));
+    family_lookahead_horizon_block(f, a.f, dV.p, n_prm > 0 ? dprm.p : nullptr, t0);
+    a.bprm = (const double *)f->bprm.p; a.steps = (const double *)f->look_steps.p;
+    a.w = f->W > 0 ? dw.p : nullptr; a.x = dx.p; a.u = du.p; a.g = dg.p; a.q = dq.p;
+    a.B = B; a.T = T; a.t0 = t0;
+    a.V_step_stride = V_timed ? f->S : 0;
+    a.V_member_stride = (int64_t)(V_timed ? per_chunk : 1) * f->S;
+    a.prm_step_stride = prm_timed ? (int64_t)n_prm : 0;
+    a.prm_member_stride = prm_rows * (int64_t)n_prm;
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    const unsigned blocks = family_lookahead_grid(f, f->f_lh_simulate, B, 0);
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    double kernel_ms = 0;
+    if (!V_timed && (rc = family_horizon_upload_slices(f, dV, host_V, slice, 1, 1, 0, 1))) return rc;
+    for (int64_t k = 0; k < T; k += per_chunk) {
+        const int64_t n = (T - k < per_chunk) ? T - k : per_chunk;
+        // (the kernel of the previous chunk has finished: the stream is synchronised at the end of every round)
+        if (V_timed && (rc = family_horizon_upload_slices(f, dV, host_V, slice, V_steps, per_chunk, k, n))) return rc;
+        a.chunk_first = V_timed ? k : 0; a.step_begin = k; a.step_end = k + n;
+        HIP_TRY(hipEventRecord(f->ev0, f->stream));
+        HIP_TRY(hipModuleLaunchKernel(f->f_lh_simulate, blocks, 1, 1, 256, 1, 1, 0, f->stream, nullptr, extra));
+        HIP_TRY(hipEventRecord(f->ev1, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+        kernel_ms += ms;
+    }
+    f->last_kernel_ms = kernel_ms;
+    HIP_TRY(hipMemcpy(host_x, dx.p, P * (size_t)(T + 1) * f->d * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_u, du.p, P * (size_t)T * f->nu * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_g, dg.p, P * (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_q, dq.p, P * (size_t)T * B * rs, hipMemcpyDeviceToHost));
+    return SDP_OK;
+}
+
+extern "C" int sdp_family_montecarlo_lookahead_h(sdp_family *f, const void *host_V, int64_t V_steps, int32_t V_timed,
+                                                 const void *host_prm, int32_t n_prm, int32_t prm_timed, int64_t chunk_bytes,
+                                                 int64_t B, int64_t T, int64_t n_burn, const uint64_t *host_seeds,
+                                                 uint64_t traj_offset, const void *host_x0, const double *host_cum,
+                                                 int32_t n_law, const void *host_law_grid, double t0, int64_t steps_per_launch,
+                                                 void *host_cost_sum, int64_t *host_n_outside, void *host_x_final,
+                                                 uint64_t *host_occupancy)
+{
+    if (!f || !host_seeds || !host_x0 || !host_cum || !host_law_grid || !host_cost_sum || !host_n_outside || !host_x_final)
+        return fail(SDP_EINVAL, "NULL argument");
+    if (n_burn < 0 || n_burn > T) return fail(SDP_EINVAL, "n_burn = %lld outside [0, %lld]", (long long)n_burn, (long long)T);
+    if (steps_per_launch < 1) return fail(SDP_EINVAL, "steps_per_launch = %lld: at least 1", (long long)steps_per_launch);
+    if (f->W <= 0) return fail(SDP_EINVAL, "a deterministic system has nothing to draw: use sdp_family_simulate_lookahead");
+    if (n_law < 1 || n_law > 4096) return fail(SDP_EINVAL, "a law of %d points: 1 to 4096", (int)n_law);
+    int rc;
+    int64_t per_chunk = 0;
+    if ((rc = family_lookahead_horizon_checks(f, "sdp_family_montecarlo_lookahead_h", host_V, V_steps, V_timed, host_prm, n_prm,
+                                              chunk_bytes, B, T, &per_chunk))) return rc;
+    if (!f->f_lh_montecarlo) return fail(SDP_EINVAL, "the unit has no sdp_family_montecarlo_lookahead_h kernel");
+    if (B == 0) return SDP_OK;
+    if (steps_per_launch > ((int64_t)1 << 30)) steps_per_launch = (int64_t)1 << 30;       // (the kernel counts a launch's steps in 32 bits)
+    const size_t rs = real_size(f->dtype);
+    const size_t P = (size_t)f->P;
+    const size_t slice = (size_t)f->S * rs;
+    const int64_t prm_rows = prm_timed ? T : 1;
+    // (the draw table of one member in LDS: the cumulative sums, then the values)
+    const size_t lds_bytes = (size_t)(n_law - 1) * 8 + (size_t)n_law * rs;
+    if (lds_bytes > 65536)
+        return fail(SDP_EINVAL, "a law of %d points needs %zu bytes of LDS: at most 65536", (int)n_law, lds_bytes);
+    DevBuf dV, dprm, dx, dacc, dout, dcum, dlaw, dseed, docc;
+    if ((rc = dV.alloc(P * (size_t)(V_timed ? per_chunk : 1) * slice))) return rc;
+    if (n_prm > 0 && (rc = upload(dprm, host_prm, P * (size_t)prm_rows * n_prm * rs))) return rc;
+    if ((rc = upload(dx, host_x0, P * (size_t)f->d * B * rs))) return rc;                 // [P][d][B]
+    if ((rc = upload(dcum, host_cum, P * (size_t)n_law * 8))) return rc;
+    if ((rc = upload(dlaw, host_law_grid, P * (size_t)n_law * rs))) return rc;
+    if ((rc = upload(dseed, host_seeds, P * 8))) return rc;
+    if ((rc = dacc.alloc(P * (size_t)B * rs))) return rc;
+    if ((rc = dout.alloc(P * (size_t)B * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(dacc.p, 0, P * (size_t)B * rs, f->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, P * (size_t)B * 8, f->stream));
+    if (host_occupancy) {
+        if ((rc = docc.alloc(P * (size_t)f->S * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(docc.p, 0, P * (size_t)f->S * 8, f->stream));
+    }
+    SdpFamilyLookMcHArgs a;
+    memset(&a, 0, sizeof(a));
+    family_lookahead_horizon_block(f, a.f, dV.p, n_prm > 0 ? dprm.p : nullptr, t0);
+    a.bprm = (const double *)f->bprm.p; a.steps = (const double *)f->look_steps.p;
+    a.cum = (const double *)dcum.p; a.law_grid = dlaw.p; a.seed = (const uint64_t *)dseed.p;
+    a.x = dx.p; a.acc = dacc.p; a.n_outside = (long long *)dout.p;
+    a.occupancy = host_occupancy ? (unsigned long long *)docc.p : nullptr;
+    a.B = B; a.traj_offset = traj_offset; a.n_burn = n_burn; a.t0 = t0; a.n_law = n_law;
+    a.V_step_stride = V_timed ? f->S : 0;
+    a.V_member_stride = (int64_t)(V_timed ? per_chunk : 1) * f->S;
+    a.prm_step_stride = prm_timed ? (int64_t)n_prm : 0;
+    a.prm_member_stride = prm_rows * (int64_t)n_prm;
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    const unsigned lds = (unsigned)lds_bytes;
+    const unsigned blocks = family_lookahead_grid(f, f->f_lh_montecarlo, B, lds);
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    double kernel_ms = 0;
+    if (!V_timed && (rc = family_horizon_upload_slices(f, dV, host_V, slice, 1, 1, 0, 1))) return rc;
+    for (int64_t c = 0; c < T; c += per_chunk) {
+        const int64_t c_end = (T - c < per_chunk) ? T : c + per_chunk;
+        if (V_timed && (rc = family_horizon_upload_slices(f, dV, host_V, slice, V_steps, per_chunk, c, c_end - c))) return rc;
+        a.chunk_first = V_timed ? c : 0;
+        HIP_TRY(hipEventRecord(f->ev0, f->stream));
+        for (int64_t k = c; k < c_end; k += steps_per_launch) {
+            a.step_begin = k;
+            a.step_end = (c_end - k < steps_per_launch) ? c_end : k + steps_per_launch;
+            HIP_TRY(hipModuleLaunchKernel(f->f_lh_montecarlo, blocks, 1, 1, 256, 1, 1, lds, f->stream, nullptr, extra));
+        }
+        HIP_TRY(hipEventRecord(f->ev1, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+        kernel_ms += ms;
+    }
+    f->last_kernel_ms = kernel_ms;
     HIP_TRY(hipMemcpy(host_cost_sum, dacc.p, P * (size_t)B * rs, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_n_outside, dout.p, P * (size_t)B * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host_x_final, dx.p, P * (size_t)f->d * B * rs, hipMemcpyDeviceToHost));

@@ -49,6 +49,9 @@ enum {
                             // workgroup size and SDP_META_COL_ROWS that of sdp_family_simulate
     , SDP_META_F_FAMILY_TRANS = 32768   // a family transition unit (sdp_family_trans_kernel.h): sdp_family_transitions and
                             // nothing else; SDP_META_THREADS is its workgroup size and SDP_META_COL_ROWS the nodes of a tile
+    , SDP_META_F_FAMILY_LOOKAHEAD_HORIZON = 65536   // a family lookahead unit over a horizon (sdp_family_lookahead_horizon_kernel.h):
+                            // sdp_family_simulate_lookahead and, for a stochastic family, sdp_family_montecarlo_lookahead_h;
+                            // SDP_META_THREADS, SDP_META_COL_ROWS and SDP_META_UTAB as in a family lookahead unit
 };
 #define SDP_MAX_PEERS 8     // ranks of a direct exchange: the GPUs of one node
 #define SDP_MAXU 4   // control variables per system
@@ -287,6 +290,55 @@ struct SdpFamilyMcHArgs {
     int32_t pad_;
     int32_t orders[SDP_MAXD];
     int32_t axis_off[SDP_MAXD];
+};
+
+// Closed loops of a family under lookahead controls over a horizon (sdp_family_lookahead_horizon_kernel.h): SdpLookSimArgs
+// and SdpLookMcArgs with a member index in front of every array.  `f` is the block of SdpFamilyLookArgs, but `f.V` and
+// `f.prm` are the bases of two tables addressed by two strides each, in reals, as in SdpFamilySimHArgs: member p at step k
+// of the call looks ahead into the cost-to-go V + p * V_member_stride + (k - chunk_first) * V_step_stride and runs on the
+// row prm + p * prm_member_stride + k * prm_step_stride.  A step stride of 0 is one slice (one cost-to-go for every step)
+// or one row (a model that is symbolic in time) for every step.  `f.t_k` is not read: the time index of step k is t0 + k.
+struct SdpFamilyLookSimArgs {
+    SdpFamilyArgs f;       // f.V [P][steps of this launch's chunk, or 1][S]; f.prm [P][steps of the call, or 1][SDP_NPARAMS]
+    const double *bprm;    // [P][SDP_NBOXPARAMS] constants of the box function, row p for member p
+    const double *steps;   // [P][nu] control step hints
+    const void *w;         // [P][T][B] perturbation sequences of the whole call (null: deterministic members)
+    void *x;               // [P][T+1][d][B] states of the whole call: row step_begin read, rows step_begin + 1 .. step_end written
+    void *u;               // [P][T][nu][B] controls applied
+    void *g;               // [P][T][B] instantaneous costs
+    void *q;               // [P][T][B] minimised expected values
+    int64_t B;             // trajectories of one member
+    int64_t T;             // steps of the whole call
+    int64_t V_member_stride, V_step_stride;
+    int64_t prm_member_stride, prm_step_stride;
+    int64_t step_begin;    // first step of this launch (step of the call)
+    int64_t step_end;      // one past its last step
+    int64_t chunk_first;   // step of the call whose cost-to-go slice is the member's first on the device
+    double t0;             // time index of step 0 of the call
+};
+
+struct SdpFamilyLookMcHArgs {
+    SdpFamilyArgs f;       // as SdpFamilyLookSimArgs
+    const double *bprm;    // as SdpFamilyLookMcArgs from here on
+    const double *steps;
+    const double *cum;
+    const void *law_grid;
+    const uint64_t *seed;
+    void *x;
+    void *acc;
+    long long *n_outside;
+    unsigned long long *occupancy;
+    int64_t B;
+    uint64_t traj_offset;
+    int64_t step_begin;
+    int64_t step_end;
+    int64_t n_burn;
+    double t0;
+    int64_t V_member_stride, V_step_stride;
+    int64_t prm_member_stride, prm_step_stride;
+    int64_t chunk_first;   // step of the call whose cost-to-go slice is the member's first on the device
+    int32_t n_law;
+    int32_t pad_;
 };
 
 // Batched closed-loop simulation (the user loop of the reference's examples, e.g.

@@ -25,6 +25,12 @@ workgroup, every lattice made on the device from the member's traced control_box
 workgroup, and `sdp_family_montecarlo_h`, a tile of 256, each step with the member's policy slice and row of constants
 of that step.
 
+`simulate_lookahead` and `monte_carlo_lookahead_horizon` run the members forward over a horizon under lookahead controls
+-- step k looks ahead into the member's cost-to-go of that step, `J_next[p, t0 + k]`, what `bellman_recursion` returns --
+also for members whose model looks data up as `data[k]` (csrc/sdp_family_lookahead_horizon_kernel.h): kernels
+`sdp_family_simulate_lookahead` and `sdp_family_montecarlo_lookahead_h`, the tile and the lattice of the lookahead kernels
+with the cost-to-go slice and the row of constants of the step.
+
 `transition_operator` and `stationary_distribution` build the transition operators of the members' policies together
 (csrc/sdp_family_trans_kernel.h): one launch of `sdp_family_transitions`, a tile of 256 >> d nodes of one member a
 workgroup, and one stable sort make a block-diagonal CSR per chunk of members (`FamilyTransitionOperator`), which one
@@ -263,6 +269,45 @@ class _FamilyProblem(object):
             self.h, B, int(n_steps), int(n_burn), nat.ptr(seeds), int(traj_offset), nat.ptr(x0), nat.ptr(cum),
             int(cum.shape[1]), nat.ptr(law_grid), float(t0), int(steps_per_launch), nat.ptr(cost_sum), nat.ptr(n_out),
             nat.ptr(x_final), nat.ptr(occ)))
+        return cost_sum, n_out, x_final, occ
+
+    # ---- closed loops under lookahead controls over a horizon (csrc/sdp_family_lookahead_horizon_kernel.h)
+    def load_lookahead_horizon_unit(self, module):
+        nat.check(nat.lib().sdp_family_load_lookahead_horizon_unit(self.h, module.encode()))
+
+    def simulate_lookahead_h(self, V, V_timed, table, prm_timed, chunk_bytes, x0, w, n_steps, t0):
+        """V [P][T or 1][S], table [P][T or 1][n_prm], x0 [P][d][B], w [P][T][B] or None, at the box set: (x [P][T+1][d][B],
+        u [P][T][nu][B], g [P][T][B], q [P][T][B])"""
+        d, B, T = x0.shape[1], x0.shape[2], int(n_steps)
+        assert V.shape[0] == table.shape[0] == x0.shape[0] == self.P and V.shape[2:] == (self.S,)
+        assert w is None or w.shape == (self.P, T, B)
+        assert all(a.flags.c_contiguous and a.dtype == self.dtype for a in (V, table, x0) + (() if w is None else (w,)))
+        x = np.empty((self.P, T + 1, d, B), dtype=self.dtype)
+        u = np.empty((self.P, T, self.nu, B), dtype=self.dtype)
+        g = np.empty((self.P, T, B), dtype=self.dtype)
+        q = np.empty((self.P, T, B), dtype=self.dtype)
+        nat.check(nat.lib().sdp_family_simulate_lookahead(
+            self.h, nat.ptr(V), int(V.shape[1]), int(bool(V_timed)), nat.ptr(table) if table.size else None,
+            int(table.shape[2]), int(bool(prm_timed)), int(chunk_bytes), B, T, nat.ptr(x0), nat.ptr(w), float(t0),
+            nat.ptr(x), nat.ptr(u), nat.ptr(g), nat.ptr(q)))
+        return x, u, g, q
+
+    def montecarlo_lookahead_h(self, V, V_timed, table, prm_timed, chunk_bytes, x0, n_steps, n_burn, seeds, traj_offset,
+                               cum, law_grid, t0, steps_per_launch, occupancy):
+        """V and table as in `simulate_lookahead_h`, the rest as in `montecarlo_lookahead`: what `montecarlo` returns"""
+        d, B = x0.shape[1], x0.shape[2]
+        assert V.shape[0] == table.shape[0] == x0.shape[0] == self.P and V.shape[2:] == (self.S,)
+        assert cum.shape == law_grid.shape and all(a.flags.c_contiguous for a in (V, table, x0, cum, law_grid, seeds))
+        assert all(a.dtype == self.dtype for a in (V, table, x0, law_grid))
+        cost_sum = np.empty((self.P, B), dtype=self.dtype)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, d, B), dtype=self.dtype)
+        occ = np.empty((self.P, self.S), dtype=np.uint64) if occupancy else None
+        nat.check(nat.lib().sdp_family_montecarlo_lookahead_h(
+            self.h, nat.ptr(V), int(V.shape[1]), int(bool(V_timed)), nat.ptr(table) if table.size else None,
+            int(table.shape[2]), int(bool(prm_timed)), int(chunk_bytes), B, int(n_steps), int(n_burn), nat.ptr(seeds),
+            int(traj_offset), nat.ptr(x0), nat.ptr(cum), int(cum.shape[1]), nat.ptr(law_grid), float(t0),
+            int(steps_per_launch), nat.ptr(cost_sum), nat.ptr(n_out), nat.ptr(x_final), nat.ptr(occ)))
         return cost_sum, n_out, x_final, occ
 
     # ---- transition operators (csrc/sdp_family_trans_kernel.h)
@@ -595,7 +640,7 @@ class SolverFamily(object):
             step = max(1, min(step, int(most)))
         return [(a, min(a + step, self.P)) for a in range(0, self.P, step)]
 
-    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None, horizon=None, trans=None):
+    def _run(self, tabs, J0, work, evaluation=False, mc_bytes=None, look=None, horizon=None, trans=None, look_horizon=None):
         """work(prob, first, last) on every chunk, each with its values set from J0 [P] + dims.  evaluation: the
         call evaluates policies, so every handle also loads the family's evaluation unit and the chunks leave room
         for the prescribed policy.  mc_bytes: the call is a Monte Carlo run whose arrays take that many bytes a
@@ -606,17 +651,22 @@ class SolverFamily(object):
         a horizon (dict(source, bytes): the horizon unit and the bytes a member takes beside the handle's), so every
         handle also loads the family's horizon unit (J0 is None then).  trans: the call builds transition operators
         (dict(bytes, most): the bytes a member takes beside the handle's and the most members of a chunk), so every handle
-        also loads the family's transition unit (J0 is None then).  Returns the chunks [(first, last), ...] it ran in"""
+        also loads the family's transition unit (J0 is None then).  look_horizon: the call is a closed loop under lookahead
+        controls over a horizon (what `look` takes, from `_lookahead_horizon_tables`: the bytes count the member's
+        cost-to-go slices, table rows, states and outputs), so every handle also loads that unit and is given its members'
+        box constants and control steps (J0 is None then).  Returns the chunks [(first, last), ...] it ran in"""
         nat.require_gpu()
         module = nat.compile_model(tabs['source'])
         look_module = nat.compile_model(look['source']) if look is not None else None
+        look_horizon_module = nat.compile_model(look_horizon['source']) if look_horizon is not None else None
         policy_module = nat.compile_model(codegen.family_policy_unit(tabs['model'], self.dtype)) if evaluation else None
         mc_module = nat.compile_model(codegen.family_mc_unit(tabs['model'], self.dtype)) if mc_bytes is not None else None
         horizon_module = nat.compile_model(horizon['source']) if horizon is not None else None
         trans_module = nat.compile_model(codegen.family_trans_unit(tabs['model'], self.dtype)) if trans is not None else None
         chunks = self._chunks(tabs, self._policy_bytes() if evaluation else
                               int(mc_bytes or 0) + (look['bytes'] if look else 0) + (horizon['bytes'] if horizon else 0)
-                              + (trans['bytes'] if trans else 0), trans['most'] if trans else None)
+                              + (trans['bytes'] if trans else 0) + (look_horizon['bytes'] if look_horizon else 0),
+                              trans['most'] if trans else None)
         digest = hashlib.sha256()
         for k in ('axes', 'wgrid', 'proba', 'lo', 'hi', 'n'):
             if tabs[k] is not None:
@@ -645,11 +695,20 @@ class SolverFamily(object):
                 if trans_module is not None and getattr(prob, 'trans_module', None) != trans_module:
                     prob.load_trans_unit(trans_module)
                     prob.trans_module = trans_module
-                if look_module is not None:
-                    if getattr(prob, 'look_module', None) != look_module:
-                        prob.load_lookahead_unit(look_module)
-                        prob.look_module = look_module
-                    prob.set_lookahead_box(look['bprm'][first:last], look['steps'][first:last])
+                for which, unit, load in (('look_module', look, prob.load_lookahead_unit),
+                                          ('look_horizon_module', look_horizon, prob.load_lookahead_horizon_unit)):
+                    if unit is None:
+                        continue
+                    # (the two units of a handle share the lanes and the box rows: the library drops the one of another plan)
+                    plan = (tabs['lanes'], unit['bprm'].shape[1])
+                    if getattr(prob, 'look_plan', plan) != plan:
+                        prob.look_module = prob.look_horizon_module = None
+                    prob.look_plan = plan
+                    built = look_module if unit is look else look_horizon_module
+                    if getattr(prob, which, None) != built:
+                        load(built)
+                        setattr(prob, which, built)
+                    prob.set_lookahead_box(unit['bprm'][first:last], unit['steps'][first:last])
                 prob.set_params(tabs['prm'][first:last])
                 if J0 is not None:
                     prob.set_value(J0[first:last])
@@ -990,30 +1049,10 @@ class SolverFamily(object):
         S, d, rs = int(np.prod(self.dims)), len(self.dims), self.dtype.itemsize
         return (self.nu * S + (d + 1) * B) * rs + 8 * B + (8 * S if occupancy else 0) + n_law * (8 + rs) + 8
 
-    def monte_carlo(self, pol, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False, traj_offset=0, t0=0):
-        """`DPSolver.monte_carlo` of every member in one device call per cut of the steps (kernel
-        sdp_family_montecarlo, csrc/sdp_family_mc_kernel.h): a `montecarlo.FamilyMonteCarloResult`, member p of
-        every field equal, bit for bit, to what `solvers[p].monte_carlo` returns on its device path.
-
-        pol   : (P,) + dims + (nu,), what `policy_iteration` or `value_iteration` returns (or dims + (nu,): every
-                member's policy)
-        x0    : (d,) with n_traj given, (B, d) shared by all members, or (P, B, d)
-        seed  : one integer -- every member then sees the same uniform draws (common random numbers: compare two
-                members with `res.paired(p, q)`) -- or a sequence of P integers
-        law   : None (each member's own law), one (grid, proba) for all members, or a sequence of P of them; all
-                with the same number of points
-        n_burn, occupancy, traj_offset, t0: as in the solo call.
-        Not built here: time-indexed policies and models that look data up as data[k] (`monte_carlo_horizon` runs
-        both); deterministic members (`simulate`)."""
+    def _mc_inputs(self, x0, n_steps, n_burn, n_traj, seed, traj_offset):
+        """what every Monte Carlo call checks of its start states, steps, seeds and trajectory ids: (x0 (P, B, d), B,
+        n_steps, n_burn, the members' seeds, steps_per_launch)"""
         d = len(self.dims)
-        # ---- everything that is refused, before a device is touched
-        laws = self._mc_laws(law)
-        pol = np.asarray(pol)
-        one = self.dims + (self.nu,)
-        if pol.ndim > len(one) + 1 and pol.shape[-len(one):] == one:
-            raise NotImplementedError('pol of shape {}: a time-indexed policy (a leading axis beside the members\') is not '
-                                      'what monte_carlo takes: use monte_carlo_horizon'.format(pol.shape))
-        pol = self._policy(pol)
         x0 = np.asarray(x0, dtype=float)
         shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
         if x0.ndim == 1:
@@ -1039,6 +1078,33 @@ class SolverFamily(object):
         spl = int(self.steps_per_launch)
         if spl < 1:
             raise ValueError('steps_per_launch must be at least 1')
+        return x0, B, n_steps, n_burn, seeds, spl
+
+    def monte_carlo(self, pol, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False, traj_offset=0, t0=0):
+        """`DPSolver.monte_carlo` of every member in one device call per cut of the steps (kernel
+        sdp_family_montecarlo, csrc/sdp_family_mc_kernel.h): a `montecarlo.FamilyMonteCarloResult`, member p of
+        every field equal, bit for bit, to what `solvers[p].monte_carlo` returns on its device path.
+
+        pol   : (P,) + dims + (nu,), what `policy_iteration` or `value_iteration` returns (or dims + (nu,): every
+                member's policy)
+        x0    : (d,) with n_traj given, (B, d) shared by all members, or (P, B, d)
+        seed  : one integer -- every member then sees the same uniform draws (common random numbers: compare two
+                members with `res.paired(p, q)`) -- or a sequence of P integers
+        law   : None (each member's own law), one (grid, proba) for all members, or a sequence of P of them; all
+                with the same number of points
+        n_burn, occupancy, traj_offset, t0: as in the solo call.
+        Not built here: time-indexed policies and models that look data up as data[k] (`monte_carlo_horizon` runs
+        both); deterministic members (`simulate`)."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        laws = self._mc_laws(law)
+        pol = np.asarray(pol)
+        one = self.dims + (self.nu,)
+        if pol.ndim > len(one) + 1 and pol.shape[-len(one):] == one:
+            raise NotImplementedError('pol of shape {}: a time-indexed policy (a leading axis beside the members\') is not '
+                                      'what monte_carlo takes: use monte_carlo_horizon'.format(pol.shape))
+        pol = self._policy(pol)
+        x0, B, n_steps, n_burn, seeds, spl = self._mc_inputs(x0, n_steps, n_burn, n_traj, seed, traj_offset)
         tabs = self._tables(None if self.stationnary else 0)
         if tabs['time_specialized']:
             raise NotImplementedError('the members\' model looks data up at a concrete time index (data[k]): monte_carlo '
@@ -1145,20 +1211,10 @@ class SolverFamily(object):
                                             time_specialized=bool(prm_timed), chunks=len(chunks), step_chunks=step_chunks,
                                             launches=launches)
 
-    def simulate(self, pol, x0, w=None, n_steps=None, t0=0):
-        """`DPSolver.simulate` of every member in one device call per cut of the steps (kernel sdp_family_simulate,
-        csrc/sdp_family_horizon_kernel.h): (x (P, T+1, B, d), u (P, T, B, nu), g (P, T, B)), member p equal, bit for
-        bit, to what `solvers[p].simulate(pol[p], x0[p], w[p], n_steps, t0)` returns on its device path.
-
-        pol : dims + (nu,) (one stationary policy for all members), (P,) + dims + (nu,) (one per member), or
-              (P, T_pol) + dims + (nu,), what `bellman_recursion` returns: step k then runs at time index t0 + k with
-              the controls of pol[p, t0 + k].  A time-indexed policy always carries both leading axes.
-        x0  : (d,) -- the results then have no B axis --, (B, d) shared by all members, or (P, B, d)
-        w   : (T,), (T, B) shared by all members, or (P, T, B); None for deterministic members (then give n_steps)
-        Models that are symbolic in time and models that look data up as data[k] (traced per member and step) both
-        run; there is no host path."""
+    def _simulate_inputs(self, x0, w, n_steps):
+        """what every closed loop with prescribed perturbations checks of its start states and sequences: (x0 (P, B, d),
+        w (P, >= T, B) or None, B, T, whether x0 was a single state)"""
         d = len(self.dims)
-        # ---- everything that is refused, before a device is touched
         x0 = np.asarray(x0, dtype=float)
         single = x0.ndim == 1
         if single:
@@ -1190,6 +1246,23 @@ class SolverFamily(object):
             T, w = int(n_steps), None
         if T < 1:
             raise ValueError('need n_steps >= 1')
+        return x0, w, B, T, single
+
+    def simulate(self, pol, x0, w=None, n_steps=None, t0=0):
+        """`DPSolver.simulate` of every member in one device call per cut of the steps (kernel sdp_family_simulate,
+        csrc/sdp_family_horizon_kernel.h): (x (P, T+1, B, d), u (P, T, B, nu), g (P, T, B)), member p equal, bit for
+        bit, to what `solvers[p].simulate(pol[p], x0[p], w[p], n_steps, t0)` returns on its device path.
+
+        pol : dims + (nu,) (one stationary policy for all members), (P,) + dims + (nu,) (one per member), or
+              (P, T_pol) + dims + (nu,), what `bellman_recursion` returns: step k then runs at time index t0 + k with
+              the controls of pol[p, t0 + k].  A time-indexed policy always carries both leading axes.
+        x0  : (d,) -- the results then have no B axis --, (B, d) shared by all members, or (P, B, d)
+        w   : (T,), (T, B) shared by all members, or (P, T, B); None for deterministic members (then give n_steps)
+        Models that are symbolic in time and models that look data up as data[k] (traced per member and step) both
+        run; there is no host path."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        x0, w, B, T, single = self._simulate_inputs(x0, w, n_steps)
         pol_d, timed = self._horizon_policy(pol, T, t0)
         tabs, table, prm_timed = self._horizon_tables(T, t0)
         # ---- member-major device arrays
@@ -1229,31 +1302,7 @@ class SolverFamily(object):
         d = len(self.dims)
         # ---- everything that is refused, before a device is touched
         laws = self._mc_laws(law)
-        x0 = np.asarray(x0, dtype=float)
-        shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
-        if x0.ndim == 1:
-            if x0.shape != (d,):
-                raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
-            if n_traj is None:
-                raise ValueError('give n_traj with a single start state')
-            if int(n_traj) < 1:
-                raise ValueError('n_traj must be at least 1')
-            x0 = np.broadcast_to(x0, (int(n_traj), d))
-        elif x0.ndim not in (2, 3) or x0.shape[-1] != d or (x0.ndim == 3 and x0.shape[0] != self.P):
-            raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
-        elif n_traj is not None and int(n_traj) != x0.shape[-2]:
-            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[-2]))
-        B = x0.shape[-2]
-        if x0.ndim == 2:
-            x0 = np.broadcast_to(x0, (self.P, B, d))
-        n_steps, n_burn = int(n_steps), int(n_burn)
-        if n_steps < 1 or not 0 <= n_burn < n_steps:
-            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
-        seeds = self._mc_seeds(seed)
-        DPSolver._mc_ids(B, traj_offset)
-        spl = int(self.steps_per_launch)
-        if spl < 1:
-            raise ValueError('steps_per_launch must be at least 1')
+        x0, B, n_steps, n_burn, seeds, spl = self._mc_inputs(x0, n_steps, n_burn, n_traj, seed, traj_offset)
         pol_d, timed = self._horizon_policy(pol, n_steps, t0)
         tabs, table, prm_timed = self._horizon_tables(n_steps, t0)
         # ---- member-major device arrays
@@ -1388,31 +1437,7 @@ class SolverFamily(object):
                                  'n_steps=...)'.format(p))
         laws = self._mc_laws(law)
         J0 = self._cost_to_go(J_next)
-        x0 = np.asarray(x0, dtype=float)
-        shapes = '({},) with n_traj, (B, {}) or ({}, B, {})'.format(d, d, self.P, d)
-        if x0.ndim == 1:
-            if x0.shape != (d,):
-                raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
-            if n_traj is None:
-                raise ValueError('give n_traj with a single start state')
-            if int(n_traj) < 1:
-                raise ValueError('n_traj must be at least 1')
-            x0 = np.broadcast_to(x0, (int(n_traj), d))
-        elif x0.ndim not in (2, 3) or x0.shape[-1] != d or (x0.ndim == 3 and x0.shape[0] != self.P):
-            raise ValueError('x0 must have shape {}, not {}'.format(shapes, x0.shape))
-        elif n_traj is not None and int(n_traj) != x0.shape[-2]:
-            raise ValueError('n_traj = {} but x0 holds {} start states'.format(n_traj, x0.shape[-2]))
-        B = x0.shape[-2]
-        if x0.ndim == 2:
-            x0 = np.broadcast_to(x0, (self.P, B, d))
-        n_steps, n_burn = int(n_steps), int(n_burn)
-        if n_steps < 1 or not 0 <= n_burn < n_steps:
-            raise ValueError('need n_steps >= 1 and 0 <= n_burn < n_steps')
-        seeds = self._mc_seeds(seed)
-        DPSolver._mc_ids(B, traj_offset)
-        spl = int(self.steps_per_launch)
-        if spl < 1:
-            raise ValueError('steps_per_launch must be at least 1')
+        x0, B, n_steps, n_burn, seeds, spl = self._mc_inputs(x0, n_steps, n_burn, n_traj, seed, traj_offset)
         dt = self.dtype
         S, n_law, rs = int(np.prod(self.dims)), len(laws[0][1]), self.dtype.itemsize
         extra = (d + 1) * B * rs + 8 * B + (8 * S if occupancy else 0) + n_law * (8 + rs) + 8
@@ -1437,6 +1462,139 @@ class SolverFamily(object):
         self.backend_info.update(lookahead_path='device', lookahead_box='device', box_constants=int(look['bprm'].shape[1]))
         self.backend_info['monte_carlo'] = dict(members=self.P, n_traj=B, chunks=self.backend_info['chunks'],
                                                 launches=self.backend_info['chunks'] * (-(-n_steps // min(spl, 1 << 30))))
+        return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
+
+    # ------------------------------------------------------------------ closed loops under lookahead controls over a horizon
+    def _horizon_cost_to_go(self, J_next, n_steps, t0):
+        """(the cost-to-go as [P][T_c][1][S] in the family's reals -- T_c = n_steps slices of a time-indexed one, the
+        steps t0 .. t0 + n_steps - 1, or the one slice every step looks ahead into --, whether it is time-indexed): from
+        dims, (P,) + dims or (P, T_J) + dims"""
+        J_next = np.asarray(J_next)
+        one = self.dims
+        S = int(np.prod(self.dims))
+        if J_next.shape in (one, (self.P,) + one):
+            each = np.broadcast_to(J_next, (self.P,) + one)
+            return np.ascontiguousarray(each, dtype=self.dtype).reshape(self.P, 1, 1, S), False
+        if J_next.ndim != len(one) + 2 or J_next.shape[0] != self.P or J_next.shape[2:] != one:
+            raise ValueError('J_next must have shape {} (one cost-to-go), {} (one per member) or ({}, T_J) + {} (a '
+                             'time-indexed one per member), not {}'.format(one, (self.P,) + one, self.P, one, J_next.shape))
+        if int(t0) != t0:
+            raise ValueError('t0 = {} must be an integer to index a time-indexed cost-to-go'.format(t0))
+        if t0 < 0 or t0 + n_steps > J_next.shape[1]:
+            raise ValueError('t0 = {} and n_steps = {} need the cost-to-go steps {} .. {}: J_next has T_J = {}'.format(
+                t0, n_steps, t0, t0 + n_steps - 1, J_next.shape[1]))
+        part = J_next[:, int(t0):int(t0) + n_steps]
+        return np.ascontiguousarray(part, dtype=self.dtype).reshape(self.P, n_steps, 1, S), True
+
+    def _lookahead_horizon_tables(self, n_steps, t0):
+        """(tabs, table, prm_timed, look) of a closed loop under lookahead controls over the steps t0 .. t0 + n_steps - 1,
+        no GPU needed: what `_horizon_tables` returns -- so models that look data up as data[k] run, a row of constants
+        per member and step -- and for `_run` the source of the unit, the members' box constants [P][n_box] and control
+        steps [P][nu] in float64 and the bytes of these two rows (the caller adds what else a member takes).  The box is traced with a symbolic
+        time index (`_lookahead_boxes`): its constants are per member, not per step."""
+        boxes = self._lookahead_boxes(None if self.stationnary else t0)
+        tabs, table, prm_timed = self._horizon_tables(n_steps, t0)
+        bprm = np.ascontiguousarray([b.param_values() for b in boxes], dtype=np.float64).reshape(self.P, -1)
+        steps = np.ascontiguousarray([s.control_steps for s in self.solvers], dtype=np.float64).reshape(self.P, self.nu)
+        if np.isnan(steps).any():
+            raise ValueError('member {}: a control step is NaN'.format(int(np.argwhere(np.isnan(steps))[0][0])))
+        look = dict(source=codegen.family_lookahead_horizon_unit(tabs['model'], boxes[0], self.dtype, tabs['lanes']),
+                    bprm=bprm, steps=steps, bytes=8 * (bprm.shape[1] + self.nu))
+        return tabs, table, prm_timed, look
+
+    def simulate_lookahead(self, J_next, x0, w=None, n_steps=None, t0=0):
+        """`DPSolver.simulate_lookahead` of every member in one device call per cut of the steps (kernel
+        sdp_family_simulate_lookahead, csrc/sdp_family_lookahead_horizon_kernel.h): (x (P, T+1, B, d), u (P, T, B, nu),
+        g (P, T, B), q (P, T, B)), member p equal, bit for bit, to what `solvers[p].simulate_lookahead(J_next[p], x0[p],
+        w[p], n_steps, t0)` returns, on its device path or -- models that look data up as data[k] -- its host path.
+
+        J_next : dims (one cost-to-go for all members and steps), (P,) + dims (one per member), or (P, T_J) + dims, a
+                 time-indexed one: step k of the call then looks ahead into J_next[p, t0 + k].  A time-indexed
+                 cost-to-go always carries both leading axes.  From `bellman_recursion`'s (J, pol) with final cost J_fin
+                 (P,) + dims that is `np.concatenate([J[:, 1:], J_fin[:, None]], axis=1)`: step k decides with the
+                 cost-to-go of k + 1.
+        x0, w, n_steps, t0 : as in `simulate` (the single-trajectory form included)
+        q is the minimised expected value of every step.  A state without a valid lattice gives NaN controls and q, and
+        the trajectory goes on as the model maps them.  Models that are symbolic in time and models that look data up as
+        data[k] (traced per member and step) both run; every lattice is made on the device from the member's traced
+        control_box, whose constants are per member, not per step; there is no host path."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        x0, w, B, T, single = self._simulate_inputs(x0, w, n_steps)
+        V_d, timed = self._horizon_cost_to_go(J_next, T, t0)
+        dt = self.dtype
+        rs = dt.itemsize
+        tabs, table, prm_timed, look = self._lookahead_horizon_tables(T, t0)
+        # (a member's cost-to-go slices and table rows, its start states, perturbations, states and the three outputs)
+        look['bytes'] += self._horizon_bytes(V_d, table) + (d * B + (1 if self.W else 0) * T * B + (T + 1) * d * B
+                                                            + T * self.nu * B + 2 * T * B) * rs
+        # ---- member-major device arrays
+        V_s = V_d.reshape(self.P, V_d.shape[1], -1)                                                       # [P][T or 1][S]
+        x0_d = np.ascontiguousarray(np.moveaxis(x0, -1, 1), dtype=dt)                                     # [P][d][B]
+        w_d = np.ascontiguousarray(w[:, :T], dtype=dt) if w is not None else None                        # [P][T][B]
+        x = np.empty((self.P, T + 1, B, d), dtype=dt)
+        u = np.empty((self.P, T, B, self.nu), dtype=dt)
+        g = np.empty((self.P, T, B), dtype=dt)
+        q = np.empty((self.P, T, B), dtype=dt)
+
+        def work(prob, a, b):
+            xs, us, g[a:b], q[a:b] = prob.simulate_lookahead_h(V_s[a:b], timed, table[a:b], prm_timed, self.horizon_chunk_bytes,
+                                                               x0_d[a:b], None if w_d is None else w_d[a:b], T, t0)
+            x[a:b], u[a:b] = np.moveaxis(xs, 2, 3), np.moveaxis(us, 2, 3)
+        chunks = self._run(tabs, None, work, look_horizon=look)
+        self.backend_info.update(lookahead_path='device', lookahead_box='device', box_constants=int(look['bprm'].shape[1]))
+        self._horizon_info(chunks, B, T, V_d, timed, prm_timed, None)
+        if single:
+            return x[:, :, 0], u[:, :, 0], g[:, :, 0], q[:, :, 0]
+        return x, u, g, q
+
+    def monte_carlo_lookahead_horizon(self, J_next, x0, n_steps, seed=0, n_burn=0, n_traj=None, law=None, occupancy=False,
+                                      traj_offset=0, t0=0):
+        """`DPSolver.monte_carlo_lookahead` of every member under a cost-to-go of any of the three shapes
+        `simulate_lookahead` takes, in one device call per cut of the steps (kernel sdp_family_montecarlo_lookahead_h,
+        csrc/sdp_family_lookahead_horizon_kernel.h): a `montecarlo.FamilyMonteCarloResult` with path 'device', member p of
+        every field equal, bit for bit, to what `solvers[p].monte_carlo_lookahead(J_next[p], ...)` returns.  The other
+        arguments are `monte_carlo_lookahead`'s: `law` is the law the PLANT draws from, the expectation inside the backup
+        runs over member p's own law.  Models that are symbolic in time and models that look data up as data[k] both
+        run; a cost-to-go that is not time-indexed on a symbolic model gives the bits of `monte_carlo_lookahead`.
+        Launches are cut at the cost-to-go's uploads (horizon_chunk_bytes) and at steps_per_launch.  Not built:
+        deterministic members (use `simulate_lookahead`)."""
+        d = len(self.dims)
+        # ---- everything that is refused, before a device is touched
+        for p, s in enumerate(self.solvers):
+            if self._law_points(s) == 0:
+                raise ValueError('member {}: a deterministic system has nothing to draw: use simulate_lookahead(J_next, x0, '
+                                 'n_steps=...)'.format(p))
+        laws = self._mc_laws(law)
+        x0, B, n_steps, n_burn, seeds, spl = self._mc_inputs(x0, n_steps, n_burn, n_traj, seed, traj_offset)
+        V_d, timed = self._horizon_cost_to_go(J_next, n_steps, t0)
+        dt = self.dtype
+        S, n_law, rs = int(np.prod(self.dims)), len(laws[0][1]), self.dtype.itemsize
+        tabs, table, prm_timed, look = self._lookahead_horizon_tables(n_steps, t0)
+        # (a member's cost-to-go slices and table rows, and what `monte_carlo_lookahead` counts)
+        look['bytes'] += (self._horizon_bytes(V_d, table) + (d + 1) * B * rs + 8 * B + (8 * S if occupancy else 0)
+                          + n_law * (8 + rs) + 8)
+        # ---- member-major device arrays
+        V_s = V_d.reshape(self.P, V_d.shape[1], -1)                                                       # [P][T or 1][S]
+        x0_d = np.ascontiguousarray(np.moveaxis(x0, -1, 1), dtype=dt)                                     # [P][d][B]
+        cum = np.ascontiguousarray([mc.cumulative(proba) for _, proba in laws])                           # [P][n_law]
+        law_d = np.ascontiguousarray([grid for grid, _ in laws], dtype=dt)
+        seeds_d = np.array(seeds, dtype=np.uint64)
+        cost_sum = np.empty((self.P, B), dtype=dt)
+        n_out = np.empty((self.P, B), dtype=np.int64)
+        x_final = np.empty((self.P, B, d), dtype=dt)
+        occ = np.empty((self.P,) + self.dims, dtype=np.int64) if occupancy else None
+
+        def work(prob, a, b):
+            c, n, xf, o = prob.montecarlo_lookahead_h(V_s[a:b], timed, table[a:b], prm_timed, self.horizon_chunk_bytes,
+                                                      x0_d[a:b], n_steps, n_burn, seeds_d[a:b], traj_offset, cum[a:b],
+                                                      law_d[a:b], t0, spl, occupancy)
+            cost_sum[a:b], n_out[a:b], x_final[a:b] = c, n, np.moveaxis(xf, 1, 2)
+            if occupancy:
+                occ[a:b] = o.astype(np.int64).reshape((b - a,) + self.dims)
+        chunks = self._run(tabs, None, work, look_horizon=look)
+        self.backend_info.update(lookahead_path='device', lookahead_box='device', box_constants=int(look['bprm'].shape[1]))
+        self._horizon_info(chunks, B, n_steps, V_d, timed, prm_timed, min(spl, 1 << 30))
         return mc.FamilyMonteCarloResult(cost_sum, n_out, x_final, occ, n_steps, n_burn, seeds, int(traj_offset), t0, 'device')
 
     # ------------------------------------------------------------------ state distributions under the members' policies

@@ -40,6 +40,7 @@ def digest(source):
 def family(source):
     for name, mark in (('family_policy', '#define SDP_FAMILY_POLICY 1'), ('family_lookahead', '#define SDP_FAMILY_LOOKAHEAD 1'),
                        ('family_horizon', '#define SDP_FAMILY_HORIZON 1'),
+                       ('family_lookahead_horizon', '#define SDP_FAMILY_LOOKAHEAD_HORIZON 1'),
                        ('family', '#define SDP_FAMILY 1'), ('column', '#include "sdp_column_kernel.h"'), ('staged', '#include "sdp_staged_kernel.h"'),
                        ('line', '#define SDP_LINE 1'), ('lead', '#define SDP_LEAD_AXES '),
                        ('lookahead', '#define SDP_LOOKAHEAD 1')):
