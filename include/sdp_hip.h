@@ -394,6 +394,32 @@ int sdp_transop_set_long_rows(sdp_transop *op, int32_t min_entries);
  * (everything is allocated before the events that bracket it) */
 int sdp_transop_build_ms(sdp_transop *op, double *entries_ms, double *sort_ms);
 
+/* ---- the transition operators of the steps of a horizon, and distributions propagated through them --------
+ * (stodynprog_amd/forward.py, `chain_entries` and `propagate`, is the definition).  Step k = 0 .. n_steps - 1 is
+ * sdp_transop_create under slice k of a time-indexed policy at time index t0 + k, in a unit with lifted constants
+ * with row k of a table of them: all steps in ONE launch of kernel sdp_transitions_h (csrc/sdp_trans_horizon_kernel.h)
+ * and ONE stable sort by (step, target).  One operator holds n_steps * S < 2^31 rows and fewer than 2^32 entries; a
+ * caller cuts a longer horizon into parts and hands the last distribution of one to the next (no cut changes a bit).
+ *   host_pol [n_steps][nu][S] reals, control axis first (as sdp_problem_simulate_h takes it)
+ *   host_prm [n_steps][n_params] reals, or NULL with n_params = 0 (a unit without lifted constants) */
+typedef struct sdp_chainop sdp_chainop;
+int sdp_chainop_create(sdp_problem *p, int64_t n_steps, const void *host_pol, const void *host_prm,
+                       int32_t n_params, double t0, sdp_chainop **out);
+int sdp_chainop_destroy(sdp_chainop *op);
+/* host_mu0 [B][S] reals -> host_mu [n_steps + 1][B][S]: mu[0] = mu0, mu[k + 1] = P_k^T mu[k].  1 <= B <= 65535.  The
+ * vectors stay on the device; step k is one launch over the rows of block k for all B vectors (the long rows of the
+ * block in launches of their own, as in sdp_transop_push), queued without a host synchronisation in between.  Per row
+ * acc = 0; acc = acc + data[e] * mu[k][b][source[e]], e ascending: the bits of n_steps solo pushes. */
+int sdp_chainop_propagate(sdp_chainop *op, int64_t B, const void *host_mu0, void *host_mu);
+/* the CSR of step `step` as sdp_transop_get_csr gives a solo operator's: indptr [S + 1], indices and data [S W 2^d]
+ * (any may be NULL) */
+int sdp_chainop_get_csr(sdp_chainop *op, int64_t step, int64_t *indptr, int32_t *indices, void *data);
+/* gbar [n_steps][S] reals */
+int sdp_chainop_get_mean_cost(sdp_chainop *op, void *host_gbar);
+/* HIP-event durations, ms: the build's kernel sdp_transitions_h, its sort + gather + row pointers + local sources,
+ * and the launches of the last sdp_chainop_propagate */
+int sdp_chainop_times(sdp_chainop *op, double *entries_ms, double *sort_ms, double *push_ms);
+
 /* Make the last J_k the next J_next without leaving the device. */
 int sdp_problem_swap(sdp_problem *p);
 

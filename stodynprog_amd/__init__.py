@@ -8,10 +8,10 @@ HIP kernels on gfx950 through the C ABI of include/sdp_hip.h.
     from stodynprog_amd import SysDescription, DPSolver
 """
 from .sysdesc import SysDescription
-from .solver import DPSolver, TransitionOperator
+from .solver import DPSolver, TransitionOperator, HorizonOperator
 from .interp import MlinInterpolator
 from .family import SolverFamily, FamilyTransitionOperator
 
 __version__ = '0.1.0'
-__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator', 'SolverFamily',
-           'FamilyTransitionOperator']
+__all__ = ['SysDescription', 'DPSolver', 'MlinInterpolator', 'TransitionOperator', 'HorizonOperator',
+           'SolverFamily', 'FamilyTransitionOperator']

@@ -178,6 +178,12 @@ def _declare(lib):
         'sdp_transop_last_kernel_ms': (C.c_int, [vp, P(dbl)]),
         'sdp_transop_set_long_rows': (C.c_int, [vp, i32]),
         'sdp_transop_build_ms': (C.c_int, [vp, P(dbl), P(dbl)]),
+        'sdp_chainop_create': (C.c_int, [vp, i64, vp, vp, i32, dbl, P(vp)]),
+        'sdp_chainop_destroy': (C.c_int, [vp]),
+        'sdp_chainop_propagate': (C.c_int, [vp, i64, vp, vp]),
+        'sdp_chainop_get_csr': (C.c_int, [vp, i64, vp, vp, vp]),
+        'sdp_chainop_get_mean_cost': (C.c_int, [vp, vp]),
+        'sdp_chainop_times': (C.c_int, [vp, P(dbl), P(dbl), P(dbl)]),
         'sdp_host_alloc': (C.c_int, [C.c_size_t, P(vp)]),
         'sdp_host_free': (C.c_int, [vp]),
         'sdp_comm_library': (C.c_char_p, []),

@@ -940,6 +940,7 @@ struct sdp_problem {
     hipModule_t mod = nullptr;
     hipFunction_t f_sweep = nullptr, f_evalpol = nullptr, f_simulate = nullptr, f_montecarlo = nullptr, f_transitions = nullptr;
     hipFunction_t f_simulate_h = nullptr, f_montecarlo_h = nullptr;      // the loops under a time-indexed policy (sdp_horizon_kernel.h)
+    hipFunction_t f_transitions_h = nullptr;                             // the operators of the steps of a horizon (sdp_trans_horizon_kernel.h)
     hipFunction_t f_lookahead = nullptr, f_simulate_lookahead = nullptr; // lookahead units only (sdp_lookahead_kernel.h); the second: units with their own box function
     hipFunction_t f_montecarlo_lookahead = nullptr;                      // .. and, of those, the units of a stochastic system
     // several controlled state variables (csrc/sdp_lead_kernel.h): the kernel that reduces V over w, launched
@@ -1248,6 +1249,10 @@ extern "C" int sdp_problem_create(const sdp_problem_desc *desc, sdp_problem **ou
     if (hipModuleGetFunction(&p->f_transitions, p->mod, "sdp_transitions") != hipSuccess) {
         (void)hipGetLastError();
         p->f_transitions = nullptr;
+    }
+    if (hipModuleGetFunction(&p->f_transitions_h, p->mod, "sdp_transitions_h") != hipSuccess) {
+        (void)hipGetLastError();
+        p->f_transitions_h = nullptr;
     }
     // lifted model constants (codegen: `__constant__ sdp_real sdp_model_prm[]`), if any
     if (hipModuleGetGlobal(&p->prm_dev, &p->prm_bytes, p->mod, "sdp_model_prm") != hipSuccess) {
@@ -3347,6 +3352,280 @@ extern "C" int sdp_transop_build_ms(sdp_transop *op, double *entries_ms, double 
     if (!op || !entries_ms || !sort_ms) return fail(SDP_EINVAL, "NULL argument");
     *entries_ms = op->entries_ms;
     *sort_ms = op->sort_ms;
+    return SDP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The transition operators of the steps of a horizon (csrc/sdp_trans_horizon_kernel.h): sdp_transop_create of every
+// step in one launch and one sort, and a batch of distributions pushed through the chain mu_{k+1} = P_k^T mu_k on the
+// device.  stodynprog_amd/forward.py (`chain_entries`, `propagate`) is the definition.  See include/sdp_hip.h.
+// The steps' operators are ONE block-diagonal sdp_transop on n_steps S rows -- node s of step k is row k S + s -- so
+// the CSR build of the solo operator serves it as it is (the family's operators with a step where they have a member);
+// the stable sort and the steps' disjoint rows keep every step's rows in the solo entry order.  Sources are then made
+// local to their step (k_chain_local_sources): block k maps the vectors of step k to those of step k + 1.
+//   k_chain_push, k_chain_push_group : k_push and k_push_group on the rows of ONE block for B vectors, the batch on the
+//              grid's second dimension; a row's adds happen in entry order, one rounded multiply and one rounded add
+//              per entry.  The long-row rule (SDP_PUSH_LONG, SDP_PUSH_WIDE) holds per block.
+// ---------------------------------------------------------------------------
+struct sdp_chainop {
+    sdp_transop *csr = nullptr;            // the block-diagonal operator: row pointers, LOCAL sources, values, gbar, the
+                                           //   list of long rows (global row ids; per block first the mid rows, then the wide)
+    int64_t S = 0, n_steps = 0;
+    std::vector<int64_t> mid_at, n_mid, wide_at, n_wide;     // per block: where its rows start in csr->long_rows
+    double push_ms = 0;
+    ~sdp_chainop() { delete csr; }
+};
+
+__global__ void __launch_bounds__(256) k_chain_local_sources(int32_t *__restrict__ indices, int64_t n, int32_t S)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) indices[k] = indices[k] % S;
+}
+
+// k_push on the S rows row0 .. row0 + S - 1 of the block-diagonal operator, for vector blockIdx.y of [B][S]
+template <typename real>
+__global__ void __launch_bounds__(256) k_chain_push(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                    const real *__restrict__ data, const real *__restrict__ mu,
+                                                    real *__restrict__ out, int64_t row0, int64_t S, int32_t long_min)
+{
+    indptr += row0;
+    mu += (int64_t)blockIdx.y * S;
+    out += (int64_t)blockIdx.y * S;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < S; t += stride) {
+        const int64_t b = indptr[t], e = indptr[t + 1];
+        if (long_min > 0 && e - b >= long_min) continue;
+        real acc = real(0);
+        for (int64_t k = b; k < e; ++k) acc = acc + data[k] * mu[indices[k]];
+        out[t] = acc;
+    }
+}
+
+// k_push_group on the listed rows of one block (global row ids, each in [row0, row0 + S)), for vector blockIdx.y
+template <typename real, int G>
+__global__ void __launch_bounds__(256) k_chain_push_group(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                          const real *__restrict__ data, const real *__restrict__ mu,
+                                                          real *__restrict__ out, const int32_t *__restrict__ rows,
+                                                          int64_t n_rows, int64_t row0, int64_t S)
+{
+    constexpr int PER = 64 / G;                                // rows of a wave
+    mu += (int64_t)blockIdx.y * S;
+    out += (int64_t)blockIdx.y * S;
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1), grp = lane / G;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t w = wave; w * PER < n_rows; w += waves) {     // the same trips in every lane of a wave
+        const int64_t r = w * PER + grp;
+        const bool live = r < n_rows;
+        const int64_t t = live ? rows[r] : row0;
+        int64_t b = 0, e = 0;
+        if (live) { b = indptr[t]; e = indptr[t + 1]; }
+        long long longest = e - b;                             // of the wave's rows: every lane runs that many chunks
+#pragma unroll
+        for (int m = G; m < 64; m <<= 1) {
+            const long long o = __shfl_xor(longest, m, 64);
+            longest = o > longest ? o : longest;
+        }
+        real acc = real(0);
+        for (int64_t off = 0; off < longest; off += G) {
+            const int64_t k = b + off + sub;
+            real p = real(0);
+            if (k < e) p = data[k] * mu[indices[k]];
+            const int64_t left = e - b - off;
+            const int n = left < G ? (left > 0 ? (int)left : 0) : G;      // entries of this group's row in the chunk
+#pragma unroll 16
+            for (int i = 0; i < G; ++i) {
+                const real q = __shfl(p, i, G);
+                acc = i < n ? acc + q : acc;
+            }
+        }
+        if (live && sub == 0) out[t - row0] = acc;
+    }
+}
+
+// workgroups of one launch over `n` units of `per` each for B vectors: at most the `cap` that are resident, all vectors
+// together, the rest in the kernel's stride loop
+static unsigned chain_blocks(int64_t n, int64_t per, int64_t cap, int64_t B)
+{
+    int64_t blocks = (n + per - 1) / per;
+    if (blocks > cap / B) blocks = cap / B;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+extern "C" int sdp_chainop_create(sdp_problem *p, int64_t n_steps, const void *host_pol, const void *host_prm,
+                                  int32_t n_params, double t0, sdp_chainop **out)
+{
+    if (!p || !host_pol || !out) return fail(SDP_EINVAL, "NULL argument");
+    if (n_steps < 1) return fail(SDP_EINVAL, "n_steps = %lld: a chain has at least one step", (long long)n_steps);
+    if (p->comm && p->comm->nranks > 1) return fail(SDP_EINVAL, "a chain of transition operators is built on one GPU");
+    if (!p->f_transitions_h) return fail(SDP_EMODULE, "the model's code object has no sdp_transitions_h kernel (built before the horizon operators)");
+    if (n_params < 0 || (n_params > 0 && !host_prm)) return fail(SDP_EINVAL, "sdp_chainop_create: bad parameter table");
+    const size_t rs = real_size(p->dtype);
+    if ((size_t)n_params * rs != p->prm_bytes)
+        return fail(SDP_EINVAL, "sdp_chainop_create: the code object declares %zu parameter(s) per step, the table has %d",
+                    p->prm_bytes / rs, (int)n_params);
+    const int64_t S = p->S, W = p->W > 0 ? p->W : 1, V = (int64_t)1 << p->d;
+    if (n_steps >= ((int64_t)1 << 31) / S + 1 || n_steps * S >= (int64_t)1 << 31)
+        return fail(SDP_EINVAL, "%lld steps of %lld nodes: the rows of their operators are 32-bit ids (at most 2^31 - 1 rows)", (long long)n_steps, (long long)S);
+    const int64_t rows = n_steps * S;
+    const int64_t nnz = rows * W * V;
+    if (nnz >= (int64_t)1 << 32)
+        return fail(SDP_EINVAL, "operators of %lld entries together: entry positions are 32-bit words (at most 2^32 - 1 entries)", (long long)nnz);
+    std::unique_ptr<sdp_chainop> ch(new sdp_chainop());
+    ch->S = S; ch->n_steps = n_steps;
+    int rc;
+    if ((rc = transop_new(p->dtype, rows, nnz, &ch->csr))) return rc;
+    sdp_transop *op = ch->csr;
+    DevBuf dpol, dprm, done, tgt, val;
+    if ((rc = upload(dpol, host_pol, (size_t)rows * p->nu * rs))) return rc;              // [n_steps][nu][S]
+    if (n_params > 0 && (rc = upload(dprm, host_prm, (size_t)n_steps * n_params * rs))) return rc;
+    if (p->W <= 0) {                                       // a deterministic system: the law of one point of weight 1
+        const double one8 = 1.0;
+        const float one4 = 1.0f;
+        if ((rc = upload(done, p->dtype == SDP_F32 ? (const void *)&one4 : (const void *)&one8, rs))) return rc;
+    }
+    if ((rc = tgt.alloc((size_t)nnz * 4))) return rc;
+    if ((rc = val.alloc((size_t)nnz * rs))) return rc;
+    if ((rc = op->gbar.alloc((size_t)rows * rs))) return rc;
+    SdpTransHArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pol = dpol.p; a.prm = n_params > 0 ? dprm.p : nullptr; a.axes = p->axes.p;
+    a.wtab = p->W > 0 ? p->wgrid.p : nullptr;
+    a.proba = p->W > 0 ? p->proba.p : done.p;
+    a.tgt = (int32_t *)tgt.p; a.val = val.p; a.gbar = op->gbar.p;
+    a.S = S; a.step_begin = 0; a.step_end = n_steps; a.chunk_first = 0; a.t0 = t0; a.W = (int32_t)W;
+    for (int k = 0; k < SDP_MAXD; ++k) { a.orders[k] = p->orders[k]; a.axis_off[k] = p->axis_off[k]; }
+    size_t size = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                     HIP_LAUNCH_PARAM_END};
+    // a tile of 256 >> d nodes of one step is a workgroup: at most the workgroups that are resident, the rest in the
+    // kernel's stride loop
+    const int64_t tile = 256 >> p->d;
+    int64_t blocks = n_steps * ((S + tile - 1) / tile);
+    if (blocks > (int64_t)p->cus * 8) blocks = (int64_t)p->cus * 8;
+    HIP_TRY(hipStreamSynchronize(p->stream));        // lifted constants set on the problem stream
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    HIP_TRY(hipModuleLaunchKernel(p->f_transitions_h, (unsigned)blocks, 1, 1, 256, 1, 1, 0, op->stream, nullptr, extra));
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    if ((rc = transop_build_csr(op, (const int32_t *)tgt.p, val.p, nullptr, (uint32_t)(W * V)))) return rc;
+    float ms = 0, ms_local = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    hipLaunchKernelGGL(k_chain_local_sources, dim3(stream_blocks(op, nnz)), dim3(256), 0, op->stream, (int32_t *)op->indices.p, nnz, (int32_t)S);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    HIP_TRY(hipEventElapsedTime(&ms_local, op->ev0, op->ev1));
+    op->entries_ms = ms;
+    op->sort_ms += ms_local;
+    op->last_kernel_ms = op->entries_ms + op->sort_ms;
+    op->has_gbar = true;
+    // the list of long rows is ascending within its two halves (transop_list_long_rows), so a block's rows are one run of each
+    ch->mid_at.assign((size_t)n_steps, 0); ch->n_mid.assign((size_t)n_steps, 0);
+    ch->wide_at.assign((size_t)n_steps, 0); ch->n_wide.assign((size_t)n_steps, 0);
+    for (int64_t k = 0; k < n_steps; ++k)
+        for (int64_t t = k * S; t < (k + 1) * S; ++t) {
+            const int64_t len = op->h_indptr[(size_t)t + 1] - op->h_indptr[(size_t)t];
+            if (len >= SDP_PUSH_WIDE) ++ch->n_wide[(size_t)k];
+            else if (len >= SDP_PUSH_LONG) ++ch->n_mid[(size_t)k];
+        }
+    int64_t at = 0;
+    for (int64_t k = 0; k < n_steps; ++k) { ch->mid_at[(size_t)k] = at; at += ch->n_mid[(size_t)k]; }
+    for (int64_t k = 0; k < n_steps; ++k) { ch->wide_at[(size_t)k] = at; at += ch->n_wide[(size_t)k]; }
+    *out = ch.release();
+    return SDP_OK;
+}
+
+template <typename real>
+static int chainop_launch_steps(sdp_chainop *ch, int64_t B, real *mu)
+{
+    sdp_transop *op = ch->csr;
+    const int64_t S = ch->S;
+    const int64_t *indptr = (const int64_t *)op->indptr.p;
+    const int32_t *indices = (const int32_t *)op->indices.p;
+    const real *data = (const real *)op->data.p;
+    const int32_t *rows = (const int32_t *)op->long_rows.p;
+    for (int64_t k = 0; k < ch->n_steps; ++k) {
+        const real *in = mu + k * B * S;
+        real *outp = mu + (k + 1) * B * S;
+        const int64_t n_mid = ch->n_mid[(size_t)k], n_wide = ch->n_wide[(size_t)k];
+        // the short rows of block k, one lane each
+        if (n_mid + n_wide < S) {
+            hipLaunchKernelGGL((k_chain_push<real>), dim3(chain_blocks(S, 256, (int64_t)op->cus * 8, B), (unsigned)B), dim3(256), 0,
+                               op->stream, indptr, indices, data, in, outp, k * S, S, (int32_t)SDP_PUSH_LONG);
+            HIP_TRY(hipGetLastError());
+        }
+        // its long rows: four to a wave (sixteen to a workgroup), the widest one to a wave
+        if (n_mid > 0) {
+            hipLaunchKernelGGL((k_chain_push_group<real, 16>), dim3(chain_blocks(n_mid, 16, (int64_t)op->cus * 64, B), (unsigned)B), dim3(256), 0,
+                               op->stream, indptr, indices, data, in, outp, rows + ch->mid_at[(size_t)k], n_mid, k * S, S);
+            HIP_TRY(hipGetLastError());
+        }
+        if (n_wide > 0) {
+            hipLaunchKernelGGL((k_chain_push_group<real, 64>), dim3(chain_blocks(n_wide, 4, (int64_t)op->cus * 64, B), (unsigned)B), dim3(256), 0,
+                               op->stream, indptr, indices, data, in, outp, rows + ch->wide_at[(size_t)k], n_wide, k * S, S);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return SDP_OK;
+}
+
+extern "C" int sdp_chainop_propagate(sdp_chainop *ch, int64_t B, const void *host_mu0, void *host_mu)
+{
+    if (!ch || !host_mu0 || !host_mu) return fail(SDP_EINVAL, "NULL argument");
+    if (B < 1 || B > 65535) return fail(SDP_EINVAL, "B = %lld vectors: 1 to 65535 (the batch is the grid's second dimension)", (long long)B);
+    sdp_transop *op = ch->csr;
+    const size_t rs = real_size(op->dtype);
+    const size_t vec = (size_t)B * ch->S * rs;
+    DevBuf mu;
+    int rc;
+    if ((rc = mu.alloc((size_t)(ch->n_steps + 1) * vec))) return rc;
+    HIP_TRY(hipMemcpyAsync(mu.p, host_mu0, vec, hipMemcpyHostToDevice, op->stream));
+    HIP_TRY(hipEventRecord(op->ev0, op->stream));
+    rc = op->dtype == SDP_F32 ? chainop_launch_steps<float>(ch, B, (float *)mu.p) : chainop_launch_steps<double>(ch, B, (double *)mu.p);
+    if (rc) { (void)hipStreamSynchronize(op->stream); return rc; }
+    HIP_TRY(hipEventRecord(op->ev1, op->stream));
+    HIP_TRY(hipMemcpyAsync(host_mu, mu.p, (size_t)(ch->n_steps + 1) * vec, hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, op->ev0, op->ev1));
+    ch->push_ms = ms;
+    return SDP_OK;
+}
+
+extern "C" int sdp_chainop_get_csr(sdp_chainop *ch, int64_t step, int64_t *indptr, int32_t *indices, void *data)
+{
+    if (!ch) return fail(SDP_EINVAL, "NULL argument");
+    if (step < 0 || step >= ch->n_steps) return fail(SDP_EINVAL, "step %lld outside [0, %lld)", (long long)step, (long long)ch->n_steps);
+    sdp_transop *op = ch->csr;
+    const int64_t *row = op->h_indptr.data() + (size_t)(step * ch->S);
+    const int64_t first = row[0], n = row[ch->S] - first;
+    if (indptr)
+        for (int64_t t = 0; t <= ch->S; ++t) indptr[t] = row[t] - first;
+    if (indices && n) HIP_TRY(hipMemcpyAsync(indices, (const int32_t *)op->indices.p + first, (size_t)n * 4, hipMemcpyDeviceToHost, op->stream));
+    if (data && n) HIP_TRY(hipMemcpyAsync(data, (const char *)op->data.p + (size_t)first * real_size(op->dtype), (size_t)n * real_size(op->dtype), hipMemcpyDeviceToHost, op->stream));
+    HIP_TRY(hipStreamSynchronize(op->stream));
+    return SDP_OK;
+}
+
+extern "C" int sdp_chainop_get_mean_cost(sdp_chainop *ch, void *host_gbar)
+{
+    if (!ch) return fail(SDP_EINVAL, "NULL argument");
+    return sdp_transop_get_mean_cost(ch->csr, host_gbar);
+}
+
+extern "C" int sdp_chainop_times(sdp_chainop *ch, double *entries_ms, double *sort_ms, double *push_ms)
+{
+    if (!ch || !entries_ms || !sort_ms || !push_ms) return fail(SDP_EINVAL, "NULL argument");
+    *entries_ms = ch->csr->entries_ms;
+    *sort_ms = ch->csr->sort_ms;
+    *push_ms = ch->push_ms;
+    return SDP_OK;
+}
+
+extern "C" int sdp_chainop_destroy(sdp_chainop *ch)
+{
+    if (ch) { (void)hipStreamSynchronize(ch->csr->stream); delete ch; }
     return SDP_OK;
 }
 

@@ -452,6 +452,30 @@ struct SdpTransArgs {
     int32_t axis_off[SDP_MAXD];
 };
 
+// Entries of the transition operators of the steps of a horizon (sdp_trans_horizon_kernel.h, kernel `sdp_transitions_h`):
+// SdpTransArgs with a step index in front of every array.  Step k of the call reads slice k - chunk_first of the policy
+// and, in a unit with lifted constants, row k of a table of them; its time index is t0 + k.  The operators form ONE
+// block-diagonal operator: node s of step k is row (k - step_begin) S + s.
+struct SdpTransHArgs {
+    const void *pol;       // [steps of this launch's chunk][nu][S], control axis first: step k reads slice k - chunk_first
+    const void *prm;       // [steps of the call][SDP_NPARAMS] lifted constants, row k for step k (null: none)
+    const void *axes;      // concatenated state-grid axes, like SdpSweepArgs
+    const void *wtab;      // as SdpTransArgs
+    const void *proba;
+    int32_t *tgt;          // [step_end - step_begin][S W 2^d] target rows, (k - step_begin) S + node
+    void *val;             // [step_end - step_begin][S W 2^d] weights (reals)
+    void *gbar;            // [step_end - step_begin][S] mean cost of step k under its policy slice (reals)
+    int64_t S;             // state nodes
+    int64_t step_begin;    // first step of this launch (step of the call)
+    int64_t step_end;      // one past its last step
+    int64_t chunk_first;   // step of the call whose policy slice is pol[0]
+    double t0;             // time index of step 0 of the call
+    int32_t W;             // points of the flat law (>= 1)
+    int32_t pad_;
+    int32_t orders[SDP_MAXD];
+    int32_t axis_off[SDP_MAXD];
+};
+
 // Entries of the transition operators of a family's policies (sdp_family_trans_kernel.h, kernel
 // `sdp_family_transitions`): SdpTransArgs with a member index in front of every array.  `f` is the block of the sweep
 // with `f.pol` the PRESCRIBED policies [P][S][nu] (read, not written); `f.V`, `f.J`, `f.idx`, the box arrays and

@@ -139,6 +139,7 @@ template <bool H, typename Args> SDP_DEV void sdp_montecarlo_loop(const Args &a)
 #include "sdp_multiw_kernel.h"  // the kernels below and sdp_meta for several perturbation variables (w a vector)
 #include "sdp_trans_kernel.h"   // sdp_transitions on the flat law
 #include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy
+#include "sdp_trans_horizon_kernel.h" // sdp_transitions_h: the entries of the operators of the steps of a horizon
 #if defined(SDP_LOOKAHEAD)
 #include "sdp_lookahead_kernel.h" // sdp_lookahead: the backup at arbitrary states of a batch (lookahead units only)
 #endif
@@ -267,6 +268,7 @@ extern "C" __global__ void __launch_bounds__(64) sdp_simulate(SdpSimArgs a)
 #endif
 #include "sdp_trans_kernel.h"   // sdp_transitions: the entries of the policy's transition operator (deterministic units too)
 #include "sdp_horizon_kernel.h" // sdp_simulate_h, sdp_montecarlo_h: the two loops under a time-indexed policy (every unit)
+#include "sdp_trans_horizon_kernel.h" // sdp_transitions_h: the entries of the operators of the steps of a horizon
 #if defined(SDP_LOOKAHEAD)
 #include "sdp_lookahead_kernel.h" // sdp_lookahead: the backup at arbitrary states of a batch (lookahead units only)
 #endif

@@ -44,6 +44,21 @@ push number check_every, 2 check_every, .. and after push number n_max, delta = 
 max(dmax, -dmin) of `convergence.diff_stats` (order-independent; NaN never converges); the iteration stops at the
 first checked delta <= tol, or at n_max.  No renormalisation and no damping: a periodic chain does not converge and
 returns converged = False.
+
+Over a horizon.  Under a time-indexed policy (what `bellman_recursion` returns) or a non-stationary model every step has
+its own operator: step k = 0 .. T - 1 of a run that starts at time index t0 is `entries(solver, pol_k, t0 + k)`, pol_k
+the policy slice pol[t0 + k] (a stationary policy: the same array at every step) -- `chain_entries`; nothing about one
+step is defined again.  The chain mu_0 given, mu_{k+1} = push(P_k^T, mu_k) -- `propagate` -- is the forward pass of a
+finite-horizon problem without sampling noise: the distribution of the state at every step, the expected cost
+<mu_k, gbar_k> of every step, and their total.  With J_T = J_fin and J_k = gbar_k + P_k J_{k+1}, the backward pass of
+`eval_policy` step by step,
+
+    <mu_0, J_0> = sum_k <mu_k, gbar_k> + <mu_T, J_fin>
+
+because <mu_k, P_k J_{k+1}> = <P_k^T mu_k, J_{k+1}> = <mu_{k+1}, J_{k+1}>: exact in exact arithmetic, since nothing is
+clamped (P_k^T is the exact adjoint where the model leaves the grid, too).  `DPSolver.horizon_operator` builds the
+operators of all steps in one device call (kernel `sdp_transitions_h`, csrc/sdp_trans_horizon_kernel.h; the library's
+`sdp_chainop`) and gives the bits of `chain_entries`, `csr` and `propagate`.
 """
 import collections
 import itertools
@@ -57,6 +72,7 @@ _I32_MIN = -2 ** 31
 
 Entries = collections.namedtuple('Entries', 'tgt src val mean_cost S W V')
 Stationary = collections.namedtuple('Stationary', 'mu n_done converged delta average_cost mass')
+Propagation = collections.namedtuple('Propagation', 'mu step_cost terminal_cost total_cost mass')
 
 
 class FamilyStationary(object):
@@ -295,3 +311,61 @@ def finish(mu, n_done, delta, tol, mean_cost):
         avg = None if mean_cost is None else float(np.dot(mu.ravel(), np.asarray(mean_cost).ravel()))
         mass = mu.sum()
     return Stationary(mu, int(n_done), bool(delta <= tol), float(delta), avg, mass)
+
+
+def chain_entries(solver, pol, n_steps, t0=0, time_index='real'):
+    """The `Entries` of the steps k = 0 .. n_steps - 1 of a horizon that starts at time index t0 (module text): step k is
+    `entries(solver, pol_k, t0 + k, time_index)` with pol_k = pol[t0 + k] for a time-indexed policy, shape
+    (T_pol,) + dims + (nu,), and pol itself for a stationary one."""
+    pol = np.asarray(pol)
+    timed = pol.ndim == len(solver.state_grid) + 2
+    n_steps = int(n_steps)
+    if timed and (int(t0) != t0 or t0 < 0 or t0 + n_steps > pol.shape[0]):
+        raise ValueError('t0 = {} and n_steps = {} need the policy steps {} .. {}: the policy has shape {}'.format(
+            t0, n_steps, t0, t0 + n_steps - 1, pol.shape))
+    return [entries(solver, pol[int(t0) + k] if timed else pol, t0 + k, time_index) for k in range(n_steps)]
+
+
+def propagate(ops, mean_costs, mu0, J_fin=None):
+    """mu0 pushed through the chain of operators ops[k] = (indptr, indices, data), k = 0 .. T - 1 (module text):
+    mu[0] = mu0 in the reals of the operators, mu[k + 1] = push(ops[k], mu[k], 1).  mu0 has the grid's shape `dims`, or
+    (B,) + dims for a batch; mean_costs[k] is gbar of step k (grid shape or flat), J_fin a terminal cost on the grid.
+
+    Returns Propagation(mu, step_cost, terminal_cost, total_cost, mass): mu (T + 1,) + dims or (T + 1, B) + dims, the time
+    axis first; step_cost[k] = dot(mu[k], mean_costs[k]), shape (T[, B]); terminal_cost = dot(mu[T], J_fin), or 0;
+    total_cost their sum; mass[k] = mu[k].sum(), shape (T + 1[, B]).  The dot products are float64 arithmetic of numpy
+    (not bit-pinned, as `finish` treats average_cost); mu is."""
+    T = len(ops)
+    if T < 1 or len(mean_costs) != T:
+        raise ValueError('{} operators and {} mean costs: a chain has at least one step and one mean cost per step'.format(
+            T, len(mean_costs)))
+    dt = ops[0][2].dtype
+    S = len(ops[0][0]) - 1
+    mu0 = np.asarray(mu0)
+    if mu0.size == 0 or mu0.size % S or (mu0.size != S and (mu0.ndim < 2 or mu0[0].size != S)):
+        raise ValueError('mu0 of shape {} is neither one vector of the operators\' {} nodes nor a batch of them'.format(
+            mu0.shape, S))
+    batch = mu0.size != S
+    mu = np.empty((T + 1,) + mu0.shape, dtype=dt)
+    mu[0] = mu0
+    for k in range(T):
+        if batch:
+            for b in range(mu0.shape[0]):
+                mu[k + 1, b] = push(ops[k], mu[k, b], 1)
+        else:
+            mu[k + 1] = push(ops[k], mu[k], 1)
+    return finish_chain(mu, mean_costs, J_fin, batch)
+
+
+def finish_chain(mu, mean_costs, J_fin, batch):
+    """the record `propagate` returns, from the distributions of all steps"""
+    T = mu.shape[0] - 1
+    lead = mu.shape[:2] if batch else mu.shape[:1]
+    flat = mu.reshape(lead + (-1,)).astype(np.float64)
+    with np.errstate(all='ignore'):
+        step_cost = np.stack([flat[k] @ np.asarray(mean_costs[k], dtype=np.float64).ravel() for k in range(T)])
+        terminal = (flat[T] @ np.asarray(J_fin, dtype=np.float64).ravel() if J_fin is not None
+                    else np.zeros(lead[1:], dtype=np.float64))
+        total = step_cost.sum(axis=0) + terminal
+        mass = mu.reshape(lead + (-1,)).sum(axis=-1)
+    return Propagation(mu, step_cost, terminal, total, mass)

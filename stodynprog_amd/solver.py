@@ -350,6 +350,143 @@ class TransitionOperator(object):
         return indptr, indices, data
 
 
+class HorizonOperator(object):
+    """The transition operators of the steps of a horizon on the device (`DPSolver.horizon_operator`): step k is the
+    operator of the policy slice of time index t0 + k, and `propagate` pushes state distributions through the chain
+    mu_{k+1} = P_k^T mu_k.  `stodynprog_amd.forward` (`chain_entries`, `csr`, `propagate`) is the definition of every
+    number it returns.  NOT in the reference API.
+
+    shape     : the state grid's
+    n_steps   : steps of the chain
+    nnz       : entries of all steps, n_steps S W 2^d
+    mean_cost : gbar of every step, shape (n_steps,) + shape
+    path      : 'device' (the entries of all steps of a part from ONE launch of kernel sdp_transitions_h and one sort:
+                a sdp_chainop handle per part) or 'host' (callables evaluated on the host step by step, a solo
+                `TransitionOperator` per step: models the horizon kernels do not run)
+    parts     : the runs of steps (first, count) that each are one device operator; the distribution is handed from
+                part to part on the host, and no cut changes a bit"""
+
+    # Steps per part.  None: as many as the library's limits allow (plan_parts); a test sets a small number to reach the
+    # cut at a tiny size.
+    part_steps = None
+    MAX_ROWS = (1 << 31) - 1           # rows of one device operator: 32-bit row ids
+    MAX_ENTRIES = (1 << 32) - 1        # .. and its entries: 32-bit entry positions
+    MAX_BATCH = 65535                  # vectors of one device call (the grid's second dimension)
+
+    @classmethod
+    def plan_parts(cls, n_steps, S, nnz_step, part_steps=None):
+        """the runs (first, count) a horizon of n_steps steps is cut into: `part_steps` steps each (the last one what is
+        left), by default the most that keep a part within MAX_ROWS rows and MAX_ENTRIES entries"""
+        run = min(cls.MAX_ROWS // int(S), cls.MAX_ENTRIES // int(nnz_step)) if part_steps is None else int(part_steps)
+        if run < 1:
+            raise ValueError('a part of a horizon holds at least one step: part_steps = {}, or one step of {} rows and {} '
+                             'entries is beyond {} rows or {} entries'.format(part_steps, S, nnz_step, cls.MAX_ROWS,
+                                                                            cls.MAX_ENTRIES))
+        return [(k, min(run, int(n_steps) - k)) for k in range(0, int(n_steps), run)]
+
+    def __init__(self, shape, dtype, n_steps, nnz_step, path, parts, handles, mean_cost, times):
+        self.shape = tuple(shape)
+        self.dtype = np.dtype(dtype)
+        self.S = int(np.prod(self.shape))
+        self.n_steps = int(n_steps)
+        self.nnz_step = int(nnz_step)
+        self.nnz = self.n_steps * self.nnz_step
+        self.path = path
+        self.parts = list(parts)
+        self._h = list(handles)            # device: a sdp_chainop per part; host: a TransitionOperator per step
+        self.mean_cost = mean_cost
+        self.nbytes = self.n_steps * forward.operator_bytes(self.nnz_step, self.S, self.dtype.itemsize)
+        self.info = dict(path=path, n_steps=self.n_steps, parts=len(self.parts), nnz=self.nnz, bytes=self.nbytes,
+                         entries_ms=times[0], sort_ms=times[1])
+
+    def close(self):
+        handles, self._h = getattr(self, '_h', None) or [], []
+        for h in handles:
+            if self.path == 'device':
+                nat.lib().sdp_chainop_destroy(h)
+            else:
+                h.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handles(self):
+        if not self._h:
+            raise ValueError('the operator is closed')
+        return self._h
+
+    def vectors(self, mu0):
+        """(mu0 as [B][S] in the operator's reals, whether it is a batch)"""
+        return _horizon_vectors(mu0, self.shape, self.dtype)
+
+    def propagate(self, mu0, J_fin=None):
+        """mu0 -- shape `shape`, or (B,) + shape for a batch -- pushed through the chain: a `forward.Propagation` record
+        with mu (n_steps + 1[, B]) + shape, step_cost (n_steps[, B]), terminal_cost = dot(mu[-1], J_fin) or 0,
+        total_cost and mass.  The vectors stay on the device between the steps of a part."""
+        handles = self._handles()
+        cur, batch = self.vectors(mu0)
+        B = cur.shape[0]
+        if J_fin is not None and np.shape(J_fin) != self.shape:
+            raise ValueError('J_fin must have the shape of the grid, {}, not {}'.format(self.shape, np.shape(J_fin)))
+        mu = np.empty((self.n_steps + 1, B, self.S), dtype=self.dtype)
+        mu[0] = cur
+        push_ms = 0.0
+        if self.path == 'device':
+            for h, (first, count) in zip(handles, self.parts):
+                for b0 in range(0, B, self.MAX_BATCH):
+                    b1 = min(B, b0 + self.MAX_BATCH)
+                    start = np.ascontiguousarray(mu[first, b0:b1])
+                    out = np.empty((count + 1, b1 - b0, self.S), dtype=self.dtype)
+                    nat.check(nat.lib().sdp_chainop_propagate(h, b1 - b0, nat.ptr(start), nat.ptr(out)))
+                    mu[first + 1:first + count + 1, b0:b1] = out[1:]
+                    push_ms += _chainop_times(h)[2]
+        else:
+            for k, op in enumerate(handles):
+                for b in range(B):
+                    mu[k + 1, b] = op.push(mu[k, b], 1).reshape(-1)
+                    push_ms += op.info['push_ms']
+        self.info['push_ms'] = push_ms
+        mu = mu.reshape((self.n_steps + 1, B) + self.shape)
+        return forward.finish_chain(mu if batch else mu[:, 0], self.mean_cost, J_fin, batch)
+
+    def tocsr(self, k):
+        """(indptr int64 [S + 1], indices int32, data) of step k's P^T: what `transition_operator(pol_k, t0 + k).tocsr()`
+        gives"""
+        k = int(k)
+        if not 0 <= k < self.n_steps:
+            raise ValueError('step {} outside [0, {})'.format(k, self.n_steps))
+        handles = self._handles()
+        if self.path != 'device':
+            return handles[k].tocsr()
+        for h, (first, count) in zip(handles, self.parts):
+            if first <= k < first + count:
+                indptr = np.empty(self.S + 1, dtype=np.int64)
+                indices = np.empty(self.nnz_step, dtype=np.int32)
+                data = np.empty(self.nnz_step, dtype=self.dtype)
+                nat.check(nat.lib().sdp_chainop_get_csr(h, k - first, nat.ptr(indptr), nat.ptr(indices), nat.ptr(data)))
+                return indptr, indices, data
+
+
+def _horizon_vectors(mu0, shape, dtype):
+    """mu0 of shape `shape` or (B,) + shape as ([B][S] in `dtype`, whether it is a batch); a ValueError names the shapes"""
+    mu0 = np.asarray(mu0)
+    shape = tuple(shape)
+    if mu0.shape == shape:
+        return np.ascontiguousarray(mu0, dtype=dtype).reshape(1, -1), False
+    if mu0.ndim == len(shape) + 1 and mu0.shape[1:] == shape and mu0.shape[0] >= 1:
+        return np.ascontiguousarray(mu0, dtype=dtype).reshape(mu0.shape[0], -1), True
+    raise ValueError('mu0 must have shape {} (one distribution) or (B,) + {} (a batch), not {}'.format(shape, shape, mu0.shape))
+
+
+def _chainop_times(h):
+    entries_ms, sort_ms, push_ms = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    nat.check(nat.lib().sdp_chainop_times(h, C.byref(entries_ms), C.byref(sort_ms), C.byref(push_ms)))
+    return entries_ms.value, sort_ms.value, push_ms.value
+
+
 class DPSolver(object):
     # Diagnostic / A-B switches of the generated kernels (codegen.DEBUG_NAMES): None in the product.
     # Tests and tools/ set a dict here (on an instance, or on the class for a block of solvers);
@@ -2599,6 +2736,104 @@ class DPSolver(object):
         op = self.transition_operator(pol, t_k)
         try:
             return op.stationary(**kw)
+        finally:
+            op.close()
+
+    def horizon_operator(self, pol, n_steps=None, t0=0):
+        """The transition operators of the steps of a horizon, as one `HorizonOperator`: step k = 0 .. n_steps - 1 is
+        `transition_operator(pol_k, t0 + k)` -- its CSR, its mean cost, its push, bit for bit -- with all steps built in
+        one device call (kernel sdp_transitions_h and one sort).  `forward.chain_entries` and `forward.propagate` are
+        the definition.  NOT in the reference API.
+
+        pol     : a TIME-INDEXED policy of shape (T_pol,) + state_dims + (nb_control,), as bellman_recursion returns
+                  (pol_k = pol[t0 + k]; n_steps defaults to T_pol - t0), or a stationary one of shape state_dims +
+                  (nb_control,) (pol_k = pol; give n_steps: a non-stationary model, or a receding schedule)
+        n_steps : steps of the chain
+        t0      : time index of step 0, an integer
+
+        The device path serves every model `simulate` runs a time-indexed policy of on the device (a symbolic time index,
+        or `data[k]` steps of one structure with their constants lifted per step); any other model takes the host path:
+        per step the entries of the definition, uploaded, and the existing solo operators chained.  The operators take
+        n_steps times the bytes of one (`forward.operator_bytes`), capped by DPSolver.TRANSITION_MAX_BYTES: continue a
+        longer horizon from mu[-1].  One GPU only."""
+        dims = self._shape()
+        self._check_supported()
+        if self.comm is not None:
+            raise NotImplementedError('horizon_operator runs on one GPU (no communicator)')
+        pol, timed = self._check_policy_shape(pol)
+        if int(t0) != t0:
+            raise ValueError('t0 = {} must be an integer: it indexes the steps of a horizon'.format(t0))
+        t0 = int(t0)
+        if timed and not 0 <= t0 < pol.shape[0]:
+            raise ValueError('t0 = {} is outside the time-indexed policy of shape {}: T_pol = {} steps of shape {}'.format(
+                t0, pol.shape, pol.shape[0], pol.shape[1:]))
+        if n_steps is None:
+            if not timed:
+                raise ValueError('a stationary policy, shape {}, needs n_steps; a time-indexed one has shape (T_pol,) + {} '
+                                 'and runs to its end'.format(pol.shape, pol.shape))
+            n_steps = pol.shape[0] - t0
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError('n_steps = {}: a horizon has at least one step'.format(n_steps))
+        self._check_horizon(pol, timed, n_steps, t0)
+        S, nnz_step, step_bytes = self._transition_size()
+        if n_steps * step_bytes > self.TRANSITION_MAX_BYTES:
+            raise ValueError('the operators of {} steps have {} entries each and take {} bytes together: more than '
+                             'DPSolver.TRANSITION_MAX_BYTES = {} bytes, which n_steps = {} fits (continue from mu[-1])'.format(
+                                 n_steps, nnz_step, n_steps * step_bytes, self.TRANSITION_MAX_BYTES,
+                                 self.TRANSITION_MAX_BYTES // step_bytes))
+        parts = HorizonOperator.plan_parts(n_steps, S, nnz_step, HorizonOperator.part_steps)
+        t_trace = None if self.sys.stationnary else t0
+        model = self._trace_now(t_trace)
+        # (the policy is handed over slice by slice whatever its form: the table of a time-indexed run)
+        table = self._horizon_table(model, True, n_steps, t0)
+        if table is not None:
+            prob = self._problem(t_trace, model)
+            pol_d = self._horizon_policy(pol, timed, n_steps, t0)                    # [n_steps][nu][S]
+            n_params = table.shape[1]
+            handles, times = [], [0.0, 0.0]
+            gbar = np.empty((n_steps,) + dims, dtype=self.dtype)
+            try:
+                for first, count in parts:
+                    h = C.c_void_p()
+                    rows = np.ascontiguousarray(table[first:first + count]) if n_params else None
+                    nat.check(nat.lib().sdp_chainop_create(prob.h, count, nat.ptr(pol_d[first:first + count]), nat.ptr(rows),
+                                                           n_params, float(t0 + first), C.byref(h)))
+                    handles.append(h)
+                    nat.check(nat.lib().sdp_chainop_get_mean_cost(h, nat.ptr(gbar[first:first + count])))
+                    ms = _chainop_times(h)
+                    times = [times[0] + ms[0], times[1] + ms[1]]
+            except Exception:
+                for h in handles:
+                    nat.lib().sdp_chainop_destroy(h)
+                raise
+            op = HorizonOperator(dims, self.dtype, n_steps, nnz_step, 'device', parts, handles, gbar, times)
+        else:
+            # a model the horizon kernels do not run: the entries of every step from the definition, on the host
+            steps, times = [], [0.0, 0.0]
+            gbar = np.empty((n_steps,) + dims, dtype=self.dtype)
+            try:
+                for k, e in enumerate(forward.chain_entries(self, pol, n_steps, t0, time_index='int')):
+                    steps.append(TransitionOperator.from_coo(dims, e.tgt, e.src, e.val, None, 'host'))
+                    gbar[k] = e.mean_cost.reshape(dims)
+                    times[1] += steps[-1].info['sort_ms']
+            except Exception:
+                for o in steps:
+                    o.close()
+                raise
+            op = HorizonOperator(dims, self.dtype, n_steps, nnz_step, 'host', [(k, 1) for k in range(n_steps)], steps, gbar,
+                                 times)
+        self.backend_info = dict(getattr(self, 'backend_info', None) or {}, horizon_operator=op.info)
+        return op
+
+    def propagate(self, pol, mu0, n_steps=None, t0=0, J_fin=None):
+        """`horizon_operator(pol, n_steps, t0).propagate(mu0, J_fin)` in one call: the distribution of the state at every
+        step of a horizon from mu0 (shape state_dims, or (B,) + state_dims), the expected cost of every step and their
+        total (a `forward.Propagation` record)."""
+        _horizon_vectors(mu0, self._shape(), self.dtype)
+        op = self.horizon_operator(pol, n_steps, t0)
+        try:
+            return op.propagate(mu0, J_fin)
         finally:
             op.close()
 
